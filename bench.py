@@ -2,6 +2,7 @@
 """bench.py -- MPC solves/s of the batched shooting solver (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype f64|f32] [--gt SC] [--in-flight F]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic two-vehicle intersection
 scenarios per GPU (SURVEY.md section 8d generator), inputs already resident in HBM:
@@ -11,12 +12,25 @@ scenarios per GPU (SURVEY.md section 8d generator), inputs already resident in H
 
 The headline (`value`, `dtype`) is the float64 entry igt_solve_batch_f64 -- the reference's own precision
 (kinematic_bicycle_model_frenet.py:70-127 and mpc.py are float64 end to end) -- on BASELINE configs[1]
-(B = 4096 per GPU, SURVEY 8d's lattice candidates).  The same JSON line carries, timed in the same run:
+(B = 4096 per GPU, SURVEY 8d's lattice candidates).  A plain run sets up, settles and warms up, times the K steps and
+prints the line (`ms_per_step` = wall time of the K timed steps / K).  With `--full` the same JSON line also carries,
+timed in the same run:
+  * `roofline`, `valu_roofline`, `kernels_ms`, `pipelined` -- per-kernel durations (HIP events, solves of their own after
+                              the timed region) and the committed counter summaries they are read against;
+  * `overlap_checked` / `exchange_checked` -- the untimed self-checks of the timed regime (a failed check prints no line);
   * `one_solve_in_flight`  -- the same workload with every step waiting for the previous one (what a closed MPC loop
                               sees), with the kernel durations the `roofline` block refers to;
   * `tracking_family`      -- the same batch through IGT_CAND_TRACK, the family MPC_Planner / igtmpc.evaluate use;
   * `f32_path`             -- the float32 entry;
-  * `configs`              -- BASELINE configs[2] (B = 65 536) and configs[4] (gt_mpc, B = 65 536; lattice and tracking).
+  * `configs`              -- BASELINE configs[2] (B = 65 536) and configs[4] (gt_mpc, B = 65 536; lattice and tracking);
+  * `cpu_baseline`         -- the oracle's C restatement on this host's cores;
+  * `same_per_gpu_work_as_n1` (N > 1) -- configs[1]'s batch per GPU beside configs[3]'s.
+
+`--dump-outputs DIR`: after the timed steps, what the last timed step returned to its caller -- x, u, cost, argmin, status
+of rank 0's scenarios -- is written as DIR/<name>.npy in float32 / float64 (integers as float64; the +inf / NaN markers of
+a scenario without a feasible candidate written as zeros, `status` names it); above 64 MB in all, a fixed seeded sample
+of scenario rows (DIR/sample_rows.npy).  The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 
 Steps are pipelined (`--in-flight F`, default 4): step t is enqueued on handle / stream t mod F -- every handle owns
 its workspace and its output buffers, the inputs are read-only -- so the emit pass (one roll-out of latency) and the
@@ -84,6 +98,36 @@ def source_hash():
             with open(os.path.join(d, fn), 'rb') as f:
                 h.update(fn.encode() + b'\0' + f.read())
     return h.hexdigest()[:16]
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_SEED = 2026
+
+
+def write_outputs(dirpath, arrays, limit=DUMP_LIMIT_BYTES):
+    """`--dump-outputs`: the solve's outputs (x, u, cost, argmin, status; one row per scenario) as dirpath/<name>.npy,
+    floating point kept, integers as float64.  A scenario without a feasible candidate (status != 0) comes back with
+    cost = +inf and NaN x / u (include/igtmpc.h, igt_solve_batch_*): markers, not values -- its x, u and cost rows are
+    written as zeros and `status` names them; a non-finite value in any other row is left as it is.  Above `limit` bytes
+    in all, one fixed seeded sample of rows is taken from every array; the rows taken go to sample_rows.npy."""
+    import numpy as np
+    none = np.asarray(arrays['status']) != 0
+    out = {}
+    for k, v in arrays.items():
+        v = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+        if k in ('x', 'u', 'cost'):
+            v = np.where(none.reshape((-1,) + (1,) * (v.ndim - 1)), v.dtype.type(0), v)
+        out[k] = v
+    total = sum(v.nbytes for v in out.values())
+    if total > limit:
+        B = len(none)
+        rows = np.sort(np.random.default_rng([DUMP_SEED, B]).choice(B, int(B * limit / total * 0.99), replace=False))
+        out = {k: v[rows] for k, v in out.items()}
+        out['sample_rows'] = rows.astype(np.float64)          # the 1 % left over holds it
+    os.makedirs(dirpath, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(dirpath, f'{k}.npy'), np.ascontiguousarray(v))
+    return sorted(out)
 
 
 def host_cores():
@@ -216,7 +260,7 @@ def rehearse_cpu(args, world, rank):
                                exchange=dict(chk, lanes=args.in_flight) if world > 1 else None)
         same = fake(default_batch(1)) if (world > 1 and B != default_batch(1) and not args.batch and not args.gt) else None
         line = assemble_line(args, fake(B), n_gpus=world, world=world, backend=dist.get_backend(), exchange=world > 1,
-                             same_work=same, n_layers=3 if args.gt else 0)
+                             same_work=same if args.full else None, n_layers=3 if args.gt else 0, full=args.full)
         line.update({'rehearsal': True, 'backend': dist.get_backend(), 'corrupted_gather_refused': not chk_bad['ok'],
                      'tokens': [int(x.item()) for x in got], 'max_over_ranks_s': float(t.item()),
                      'spawned_by_bench': os.environ.get('IGT_BENCH_SPAWNED') == '1'})
@@ -244,12 +288,10 @@ def pmc_profile(dtype, gt, B, cand='lattice'):
                 f'{tj.get("source_hash")}; not measured by this run)')
 
 
-def assemble_line(args, head, n_gpus, world, backend, exchange, other=None, serial=None, tracking=None, same_work=None,
-                  configs=None, cpu=None, n_layers=0):
-    """The one JSON line, from the measurements (a pure function: tests/test_host_logic.py builds the N = 8 gt_mpc line
-    from placeholders)."""
-    B = head['B']
-    other_dtype = 'f32' if args.dtype == 'f64' else 'f64'
+def kernel_figures(args, head, serial):
+    """`--full`: the per-kernel blocks of the line -- HIP-event kernel durations of solves run after the timed region, and
+    the committed counter summaries of the same command."""
+    B, F = head['B'], head['in_flight']
     # kernel durations of the roofline block: measured with ONE solve in flight (HIP events on the launch stream) --
     # `serial` when the headline is pipelined, the headline itself when it is not
     ref = serial if serial is not None else head
@@ -280,6 +322,29 @@ def assemble_line(args, head, n_gpus, world, backend, exchange, other=None, seri
         cpi = d.get('busy_cycles_per_valu_instruction') or 4.0
         valu['busy_fraction_of_whole_step'] = (d['valu_instructions_per_launch'] * cpi /
                                                (SIMDS * head['ms_per_step'] * 1e-3 * clk * 1e9))
+    return {
+        'roofline': {'bound': 'hbm', 'achieved': ach, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                     'frac': ach / HBM_PEAK_GBS if ach else None, 'traffic': traffic, 'traffic_source': pmc_src,
+                     'kernel': f'search kernel of igt_solve_batch_{args.dtype} (+ value kernels in gt mode)',
+                     'kernel_ms': search_ms, 'algorithmic_bytes_per_solve': rd + 12,
+                     'regime': 'one solve in flight: kernel_ms is the search kernel alone on the GPU (HIP events on its '
+                               'launch stream), the figure `one_solve_in_flight.ms_per_step` is made of; the headline '
+                               '`value` overlaps %d solves, see `pipelined`' % F if F > 1 else 'one solve in flight',
+                     'note': 'BASELINE.json names the HBM roofline; the path is vector-ALU-bound (arithmetic intensity ~1e4 '
+                             'flop/B) -- the bound that applies is `valu_roofline`'},
+        'valu_roofline': valu,
+        'kernels_ms': {'search': search_ms, 'emit': emit_ms, 'regime': 'one solve in flight'},
+        'whole_solve_bytes': rd + head['wr'],
+    }
+
+
+def assemble_line(args, head, n_gpus, world, backend, exchange, other=None, serial=None, tracking=None, same_work=None,
+                  configs=None, cpu=None, n_layers=0, full=True):
+    """The one JSON line, from the measurements (a pure function: tests/test_host_logic.py builds the N = 8 gt_mpc line
+    from placeholders).  `full` = False: a plain run's line, the headline and its configuration without the figures of
+    kernel_figures() and the self-checks."""
+    B = head['B']
+    other_dtype = 'f32' if args.dtype == 'f64' else 'f64'
     arith = {'f64': 'float64 throughout (stage derivatives, state, cost, verdicts)',
              'f32': 'float32 stage derivatives + float64 state accumulators, cost and verdicts'}
     F = head['in_flight']
@@ -302,23 +367,15 @@ def assemble_line(args, head, n_gpus, world, backend, exchange, other=None, seri
                    'cost': (f'gt_mpc value net V_GT_sc{args.gt} ({n_layers - 1} hidden layers, igtmpc.shipped_value_net, identity '
                             f'normalisation)') if args.gt else 'mpc progress cost',
                    'feasible_fraction': head['feasible']},
-        'roofline': {'bound': 'hbm', 'achieved': ach, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                     'frac': ach / HBM_PEAK_GBS if ach else None, 'traffic': traffic, 'traffic_source': pmc_src,
-                     'kernel': f'search kernel of igt_solve_batch_{args.dtype} (+ value kernels in gt mode)',
-                     'kernel_ms': search_ms, 'algorithmic_bytes_per_solve': rd + 12,
-                     'regime': 'one solve in flight: kernel_ms is the search kernel alone on the GPU (HIP events on its '
-                               'launch stream), the figure `one_solve_in_flight.ms_per_step` is made of; the headline '
-                               '`value` overlaps %d solves, see `pipelined`' % F if F > 1 else 'one solve in flight',
-                     'note': 'BASELINE.json names the HBM roofline; the path is vector-ALU-bound (arithmetic intensity ~1e4 '
-                             'flop/B) -- the bound that applies is `valu_roofline`'},
-        'valu_roofline': valu,
-        'kernels_ms': {'search': search_ms, 'emit': emit_ms, 'regime': 'one solve in flight'},
-        'whole_solve_bytes': rd + head['wr'],
         'precision': {'f64': 'igt_solve_batch_f64: <= 1e-9 of the float64 oracle on every trajectory (curvature '
                              'break-point straddlers included)',
                       'f32': 'igt_solve_batch_f32: <= 1e-5*max(1,|ref|) except trajectories whose curvature switch is '
                              'decided inside float32 noise (share measured in tests/test_gpu_parity.py)'},
     }
+    if not full:
+        line['ranks_seen'] = world if exchange else 1
+        return line
+    line.update(kernel_figures(args, head, serial))
     # self-checks of the timed regime (untimed, after it): lanes bit-equal to a solve alone; gathered vectors complete
     line['overlap_checked'] = head.get('overlap_checked')
     ex = head.get('exchange')
@@ -391,10 +448,19 @@ def main():
                          'output buffers), so the emit pass and the drain tail of one step overlap the search pass of the next')
     ap.add_argument('--settle-ms', type=float, default=150.0,
                     help='untimed steps of the same work before the warm-up, until this much wall time has passed')
+    ap.add_argument('--full', action='store_true',
+                    help='also the per-kernel / roofline figures, the self-checks of the timed regime, the other precision, '
+                         'the one-in-flight and tracking runs, the other BASELINE configs and the CPU baseline (the --no-* '
+                         'switches leave parts out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0; at most 64 MB, a seeded row "
+                         'sample above that)')
     ap.add_argument('--rehearse-cpu', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if 'WORLD_SIZE' not in os.environ:
         if args.gpus > 1:
@@ -437,9 +503,10 @@ def main():
     batches = {}
     checks_log = []          # one entry per measurement: the untimed self-checks of the regime it timed
 
-    def measure(dtype, Bm, steps, warmup, in_flight=None, cand_mode='lattice', gt=None, settle_ms=None):
-        """settle + W untimed + K timed steps of the `dtype` entry point at Bm scenarios per GPU, then per-kernel HIP
-        events (one solve at a time, and -- pipelined runs -- with the lanes overlapping)."""
+    def measure(dtype, Bm, steps, warmup, in_flight=None, cand_mode='lattice', gt=None, settle_ms=None, dump=False):
+        """settle + W untimed + K timed steps of the `dtype` entry point at Bm scenarios per GPU; `dump`: a host copy of
+        what the last timed step returned.  --full: then the self-checks of the timed regime and per-kernel HIP events (one
+        solve at a time, and -- pipelined runs -- with the lanes overlapping)."""
         gt = args.gt if gt is None else gt
         npdt = np.float64 if dtype == 'f64' else np.float32
         td = torch.float64 if dtype == 'f64' else torch.float32
@@ -479,12 +546,13 @@ def main():
         # it and the warm-up steps: the first torch kernel of a process takes the host milliseconds to load, the device idles
         # and clocks down meanwhile, and W = 5 warm-up steps (1 ms) do not bring the clock back -- the 20-step region behind them
         # then runs 5 % slower (profiles/r04_idle_gap_before_warmup.txt; same box, alternating: 22.5 against 21.3 M solves/s)
-        for o in outs:
-            o['argmin'].fill_(-5)
-        if exchange:
-            for g in gathered:
-                g.fill_(-5.0)
-        torch.cuda.synchronize(dev)
+        if args.full:
+            for o in outs:
+                o['argmin'].fill_(-5)
+            if exchange:
+                for g in gathered:
+                    g.fill_(-5.0)
+            torch.cuda.synchronize(dev)
         step_no = [0]
         drain_hint = os.environ.get('IGT_BENCH_NO_DRAIN_HINT') != '1'      # A/B switch (tools only)
 
@@ -560,63 +628,71 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
 
-        # ---- untimed self-check of the regime just timed: every lane's outputs -- written by solves
-        # that overlapped the other lanes' -- must be, bit for bit, what ONE solve of the same batch gives with the device to
-        # itself; and every lane's gathered action vector must hold every rank's u*[:, :, 0] (checksums all-reduced from the
-        # shards, igtmpc.sharding.verify_gathered).  A line whose check fails is not printed (main()).
-        torch.cuda.synchronize(dev)
-        solvers[0].set_concurrency(1)
-        alone = solvers[0].solve(*dargs)                   # fresh output buffers, current stream, nothing else in flight
-        torch.cuda.synchronize(dev)
-        solvers[0].set_concurrency(F)
-        bits = lambda t: t.contiguous().view(torch.int64 if t.element_size() == 8 else torch.int32)
-        overlap_checked = all(bool(torch.equal(bits(o[k]), bits(alone[k]))) for o in outs for k in ('x', 'u', 'cost', 'argmin', 'status'))
-        exch = None
-        if exchange:
-            from igtmpc.sharding import verify_gathered
-            u0_alone = alone['u'][:, :, 0].contiguous()
-            res = [verify_gathered(u0_alone, g) for g in gathered]
-            exch = dict(ok=all(r['ok'] for r in res), ranks_seen=res[0]['ranks_seen'],
-                        per_rank_B_local=res[0]['per_rank_B_local'], lanes=F)
-        feasible = float((alone['status'] == 0).float().mean().item())
-        del alone
-        checks_log.append(dict(dtype=dtype, B=Bm, in_flight=F, cand=cand_mode, gt=gt, overlap_checked=overlap_checked, exchange=exch))
-
-        # per-kernel durations: HIP events recorded by the library on the launch stream, same workload.
-        # (1) pipelined runs: every lane profiles its own kernels while the other lanes' kernels overlap them
-        lane_s, lane_e = None, None
-        if F > 1:
-            for sv in solvers:
-                sv.set_concurrency(F)
-                sv.set_profiling(True)
-            ls, le = [], []
-            n_prof = max(4 * F, min(steps, 48))
-            for t_ in range(n_prof):
-                q = t_ % F
-                if t_ >= F:
-                    a, e = solvers[q].kernel_ms()
-                    ls.append(a); le.append(e)
-                with torch.cuda.stream(lanes[q]):
-                    solvers[q].solve(*dargs, out=outs[q])
-            torch.cuda.synchronize(dev)
-            for sv in solvers:
-                sv.set_profiling(False)
-            lane_s, lane_e = float(np.mean(ls)), float(np.mean(le))
-        # (2) one solve at a time (with the whole device to itself: two waves per SIMD again)
-        solver.set_concurrency(1)
-        solver.set_profiling(True)
-        ks, ke = [], []
-        for _ in range(max(8, min(steps, 50))):
-            solver.solve(*dargs, out=out)
-            a, e = solver.kernel_ms()
-            ks.append(a)
-            ke.append(e)
-        solver.set_profiling(False)
-        rd, wr = solver.algorithmic_bytes_per_solve()
+        # what the last timed step returned to its caller (lane (steps issued - 1) mod F), copied to the host, untimed
+        outputs = None
+        if dump:
+            q = (step_no[0] - 1) % F
+            outputs = {k: outs[q][k].cpu().numpy() for k in ('x', 'u', 'cost', 'argmin', 'status')}
         res = dict(dtype=dtype, B=Bm, elapsed=elapsed, steps=steps, value=Bm * n_gpus * steps / elapsed,
-                   ms_per_step=elapsed / steps * 1e3, search_ms=float(np.mean(ks)), emit_ms=float(np.mean(ke)),
-                   lane_search_ms=lane_s, lane_emit_ms=lane_e, in_flight=F, settle_steps=n_settle, host_issue_ms=issued / steps * 1e3,
-                   rd=rd, wr=wr, feasible=feasible, batch=batch, overlap_checked=overlap_checked, exchange=exch)
+                   ms_per_step=elapsed / steps * 1e3, search_ms=None, emit_ms=None, lane_search_ms=None, lane_emit_ms=None,
+                   in_flight=F, settle_steps=n_settle, host_issue_ms=issued / steps * 1e3, rd=None, wr=None, feasible=None,
+                   batch=batch, overlap_checked=None, exchange=None, outputs=outputs)
+        if args.full:
+            # ---- untimed self-check of the regime just timed: every lane's outputs -- written by solves
+            # that overlapped the other lanes' -- must be, bit for bit, what ONE solve of the same batch gives with the device to
+            # itself; and every lane's gathered action vector must hold every rank's u*[:, :, 0] (checksums all-reduced from the
+            # shards, igtmpc.sharding.verify_gathered).  A line whose check fails is not printed (main()).
+            torch.cuda.synchronize(dev)
+            solvers[0].set_concurrency(1)
+            alone = solvers[0].solve(*dargs)                   # fresh output buffers, current stream, nothing else in flight
+            torch.cuda.synchronize(dev)
+            solvers[0].set_concurrency(F)
+            bits = lambda t: t.contiguous().view(torch.int64 if t.element_size() == 8 else torch.int32)
+            overlap_checked = all(bool(torch.equal(bits(o[k]), bits(alone[k]))) for o in outs for k in ('x', 'u', 'cost', 'argmin', 'status'))
+            exch = None
+            if exchange:
+                from igtmpc.sharding import verify_gathered
+                u0_alone = alone['u'][:, :, 0].contiguous()
+                vg = [verify_gathered(u0_alone, g) for g in gathered]
+                exch = dict(ok=all(r['ok'] for r in vg), ranks_seen=vg[0]['ranks_seen'],
+                            per_rank_B_local=vg[0]['per_rank_B_local'], lanes=F)
+            feasible = float((alone['status'] == 0).float().mean().item())
+            del alone
+            checks_log.append(dict(dtype=dtype, B=Bm, in_flight=F, cand=cand_mode, gt=gt, overlap_checked=overlap_checked, exchange=exch))
+
+            # per-kernel durations: HIP events recorded by the library on the launch stream, same workload.
+            # (1) pipelined runs: every lane profiles its own kernels while the other lanes' kernels overlap them
+            lane_s, lane_e = None, None
+            if F > 1:
+                for sv in solvers:
+                    sv.set_concurrency(F)
+                    sv.set_profiling(True)
+                ls, le = [], []
+                n_prof = max(4 * F, min(steps, 48))
+                for t_ in range(n_prof):
+                    q = t_ % F
+                    if t_ >= F:
+                        a, e = solvers[q].kernel_ms()
+                        ls.append(a); le.append(e)
+                    with torch.cuda.stream(lanes[q]):
+                        solvers[q].solve(*dargs, out=outs[q])
+                torch.cuda.synchronize(dev)
+                for sv in solvers:
+                    sv.set_profiling(False)
+                lane_s, lane_e = float(np.mean(ls)), float(np.mean(le))
+            # (2) one solve at a time (with the whole device to itself: two waves per SIMD again)
+            solver.set_concurrency(1)
+            solver.set_profiling(True)
+            ks, ke = [], []
+            for _ in range(max(8, min(steps, 50))):
+                solver.solve(*dargs, out=out)
+                a, e = solver.kernel_ms()
+                ks.append(a)
+                ke.append(e)
+            solver.set_profiling(False)
+            rd, wr = solver.algorithmic_bytes_per_solve()
+            res.update(search_ms=float(np.mean(ks)), emit_ms=float(np.mean(ke)), lane_search_ms=lane_s, lane_emit_ms=lane_e,
+                       rd=rd, wr=wr, feasible=feasible, overlap_checked=overlap_checked, exchange=exch)
         # ordered teardown ("exit-time abort"): nothing of this measurement is left to interpreter or
         # static destructors -- device idle, exchange buffers and lane streams dropped, handles destroyed, cache released
         torch.cuda.synchronize(dev)
@@ -629,29 +705,30 @@ def main():
         torch.cuda.empty_cache()
         return res
 
-    head = measure(args.dtype, B, args.steps, args.warmup, cand_mode=args.cand)
+    head = measure(args.dtype, B, args.steps, args.warmup, cand_mode=args.cand, dump=bool(args.dump_outputs))
+    # everything below the headline is --full only
     cpu = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and not args.gt:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and not args.gt:
         cpu = cpu_baseline(head['batch'], N, C)       # before the other measurements replace the resident batch
     other_dtype = 'f32' if args.dtype == 'f64' else 'f64'
     # one solve at a time (every step waits for the previous one's emit pass), for comparison with the pipelined headline
     serial = measure(args.dtype, B, args.steps, args.warmup, in_flight=1, cand_mode=args.cand) \
-        if args.in_flight > 1 and not args.no_secondary else None
+        if args.full and args.in_flight > 1 and not args.no_secondary else None
     # the candidate family the planner and the closed-loop driver use by default (state-feedback steering):
     # the headline stays on SURVEY 8d's lattice, this is the same batch through the family that gives the better answers
-    tracking = None if (args.no_secondary or args.cand == 'track') else \
+    tracking = None if (not args.full or args.no_secondary or args.cand == 'track') else \
         measure(args.dtype, B, args.steps, args.warmup, cand_mode='track')
     # the driver computes scaling efficiency from the per-N values; at N = 8 the per-GPU batch is configs[3]'s 32 768,
     # not configs[1]'s 4096, so the same-per-GPU-work figure is measured beside it in the same run
     same_work = None
-    if n_gpus > 1 and B != default_batch(1) and not args.batch and not args.gt:
+    if args.full and n_gpus > 1 and B != default_batch(1) and not args.batch and not args.gt:
         same_work = measure(args.dtype, default_batch(1), args.steps, args.warmup, cand_mode=args.cand)
-    other = None if args.no_secondary else measure(other_dtype, B, args.steps, args.warmup, cand_mode=args.cand)
+    other = None if (not args.full or args.no_secondary) else measure(other_dtype, B, args.steps, args.warmup, cand_mode=args.cand)
 
     # the other single-GPU BASELINE configurations, driver-timed in the same run (default invocation only):
     # configs[2] = 65 536 scenarios; configs[4] = gt_mpc at 65 536 (V_GT_sc1; lattice and tracking candidates)
     configs = []
-    if n_gpus == 1 and not args.no_configs and not args.batch and not args.gt and args.cand == 'lattice':
+    if args.full and n_gpus == 1 and not args.no_configs and not args.batch and not args.gt and args.cand == 'lattice':
         ks, kw = max(8, min(args.steps, 16)), 3
         for name, kwm in (('configs[2]', dict(Bm=65536, cand_mode='lattice', gt=0)),
                           ('configs[4]', dict(Bm=65536, cand_mode='lattice', gt=1)),
@@ -686,9 +763,11 @@ def main():
     if rank == 0:
         n_layers = len(shipped_value_net(args.gt)['layers']) if args.gt else 0
         line = assemble_line(args, head, n_gpus, world, backend, exchange, other=other, serial=serial, tracking=tracking,
-                             same_work=same_work, configs=configs, cpu=cpu, n_layers=n_layers)
+                             same_work=same_work, configs=configs, cpu=cpu, n_layers=n_layers, full=args.full)
         line['config']['settle_steps'] = head['settle_steps']
         line['host_issue_ms_per_step'] = head.get('host_issue_ms')      # host time to enqueue one step; near ms_per_step: host-bound
+        if args.dump_outputs:
+            line['outputs_written'] = write_outputs(args.dump_outputs, head['outputs'])
         print(json.dumps(line), flush=True)
     # ordered exit: measurements dropped, device idle, process group destroyed -- before the interpreter starts tearing down
     del head, serial, tracking, same_work, other, batches

@@ -186,7 +186,7 @@ def test_bench_gpus_2_without_torchrun_variables_spawns_two_ranks():
     """`python bench.py --gpus 2` with no torchrun variables must start 2 ranks itself (never silently run one):
     rehearsed on CPU over gloo -- the ranks meet, all-gather a token, and rank 0 reports what it saw."""
     import json
-    r = _run_bench('--gpus', '2', '--rehearse-cpu')
+    r = _run_bench('--gpus', '2', '--rehearse-cpu', '--full')          # the exchange's self-check is reported with --full
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
     assert line['ranks_seen'] == 2 and line['tokens'] == [0, 1] and line['spawned_by_bench'] is True
@@ -276,6 +276,45 @@ def test_bench_names_the_configuration_it_runs():
     assert 'configs[4]' in bm.workload_name(65536, 1, 1)
     assert 'custom' in bm.workload_name(12345, 1, 0) and 'configs' not in bm.workload_name(12345, 1, 0).split(':')[0].replace('custom batch', '')
     assert len(bm.source_hash()) == 16
+
+
+def test_bench_dump_outputs_writes_floats_within_the_limit(tmp_path):
+    """`bench.py --dump-outputs DIR`: every array as DIR/<name>.npy in float32 / float64 (integers as float64, exactly); the
+    +inf / NaN markers of a scenario without a feasible candidate (status 1, include/igtmpc.h) written as zeros, every other
+    value as it is; above the limit, one fixed seeded sample of rows, the same in every array and from run to run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod4', os.path.join(ROOT, 'bench.py'))
+    bm = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bm)
+    B = 1000
+    rng = np.random.default_rng(0)
+    status = (np.arange(B) % 3 == 1).astype(np.int32)
+    arrs = dict(x=rng.standard_normal((B, 7, 21)), u=rng.standard_normal((B, 2, 20)).astype(np.float32),
+                cost=rng.standard_normal(B), argmin=np.where(status == 0, np.arange(B) % 256, -1).astype(np.int32),
+                status=status)
+    none = status != 0
+    arrs['x'][none], arrs['u'][none], arrs['cost'][none] = np.nan, np.nan, np.inf        # what the library returns for them
+    names = bm.write_outputs(str(tmp_path / 'all'), arrs)
+    assert names == ['argmin', 'cost', 'status', 'u', 'x']
+    got = {k: np.load(tmp_path / 'all' / f'{k}.npy') for k in names}
+    assert got['x'].dtype == np.float64 and got['u'].dtype == np.float32 and got['argmin'].dtype == np.float64
+    assert all(np.isfinite(v).all() for v in got.values())
+    assert all(np.array_equal(got[k][~none], arrs[k][~none]) for k in names)
+    assert all((got[k][none] == 0).all() for k in ('x', 'u', 'cost'))
+    assert np.array_equal(got['status'], status) and (got['argmin'][none] == -1).all()
+    bad = dict(arrs, cost=arrs['cost'].copy())
+    bad['cost'][0] = np.nan                                                           # a feasible row's NaN is a fault: kept
+    bm.write_outputs(str(tmp_path / 'bad'), bad)
+    assert np.isnan(np.load(tmp_path / 'bad' / 'cost.npy')[0])
+    limit = sum(v.nbytes for v in arrs.values()) // 4
+    for run in ('a', 'b'):
+        names = bm.write_outputs(str(tmp_path / run), arrs, limit=limit)
+        assert 'sample_rows' in names
+        assert sum(os.path.getsize(tmp_path / run / f'{k}.npy') - 128 for k in names) <= limit
+    rows = np.load(tmp_path / 'a' / 'sample_rows.npy').astype(np.int64)
+    assert 0 < len(rows) < B and np.array_equal(rows, np.load(tmp_path / 'b' / 'sample_rows.npy'))
+    assert np.array_equal(np.load(tmp_path / 'a' / 'status.npy'), status[rows])       # the rows are the ones named
+    assert np.array_equal(np.load(tmp_path / 'a' / 'x.npy'), got['x'][rows])
 
 
 def test_public_header_is_plain_c(tmp_path):

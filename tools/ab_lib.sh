@@ -2,7 +2,7 @@
 # A/B on one box: bench.py with another build of the library (IGT_LIB_PATH) against the tree's, alternating.
 #   usage: tools/ab_lib.sh <other.so> [bench args]
 OTHER=$1; shift
-ARGS="${@:---steps 40 --warmup 5 --no-cpu-baseline --no-configs --no-secondary}"
+ARGS="--full ${@:---steps 40 --warmup 5 --no-cpu-baseline --no-configs --no-secondary}"
 cat > /tmp/ab_line.py <<'PY'
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -31,15 +31,15 @@ if [ "$WHAT" = all ] || [ "$WHAT" = pmc ]; then
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = bench ]; then
   # 2. bench lines: the driver's command (20 steps, 5 warm-up) and the long one, then the other configurations on their own
-  python3 bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_b4096_driver_args.json 2> $O/${TAG}_bench_b4096_driver_args.err
-  python3 bench.py > $O/${TAG}_bench_b4096.json 2> $O/${TAG}_bench_b4096.err
+  python3 bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_b4096_driver_args.json 2> $O/${TAG}_bench_b4096_driver_args.err
+  python3 bench.py --full > $O/${TAG}_bench_b4096.json 2> $O/${TAG}_bench_b4096.err
   echo "[collect] bench 4096 done"
-  python3 bench.py --batch 65536 --steps 40 --warmup 5 --no-cpu-baseline --in-flight 1 > $O/${TAG}_bench_b65536.json 2> $O/${TAG}_bench_b65536.err
-  python3 bench.py --gt 1 --steps 30 --warmup 5 --in-flight 1 > $O/${TAG}_bench_gt_sc1_b65536.json 2> $O/${TAG}_bench_gt1.err
-  python3 bench.py --gt 3 --steps 30 --warmup 5 --in-flight 1 > $O/${TAG}_bench_gt_sc3_b65536.json 2> $O/${TAG}_bench_gt3.err
+  python3 bench.py --full --batch 65536 --steps 40 --warmup 5 --no-cpu-baseline --in-flight 1 > $O/${TAG}_bench_b65536.json 2> $O/${TAG}_bench_b65536.err
+  python3 bench.py --full --gt 1 --steps 30 --warmup 5 --in-flight 1 > $O/${TAG}_bench_gt_sc1_b65536.json 2> $O/${TAG}_bench_gt1.err
+  python3 bench.py --full --gt 3 --steps 30 --warmup 5 --in-flight 1 > $O/${TAG}_bench_gt_sc3_b65536.json 2> $O/${TAG}_bench_gt3.err
   echo "[collect] bench 65536 / gt done"
   for F in 1 2 3 4; do
-    python3 bench.py --in-flight $F --no-cpu-baseline --no-configs 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('in-flight $F: f64 %.3f ms/step (%.2f M solves/s)   f32 %.3f ms/step (%.2f M solves/s)' % (d['ms_per_step'], d['value']/1e6, d['f32_path']['ms_per_step'], d['f32_path']['value']/1e6))"
+    python3 bench.py --full --in-flight $F --no-cpu-baseline --no-configs 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('in-flight $F: f64 %.3f ms/step (%.2f M solves/s)   f32 %.3f ms/step (%.2f M solves/s)' % (d['ms_per_step'], d['value']/1e6, d['f32_path']['ms_per_step'], d['f32_path']['value']/1e6))"
   done > $O/${TAG}_inflight_sweep.txt
   echo "[collect] in-flight sweep done"
 fi

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 for sc in 1 3; do
   O=gpurun_out/gt_trace_sc$sc; rm -rf $O; mkdir -p $O
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --gt $sc --batch ${BATCH:-65536} --steps 10 --warmup 3 --no-cpu-baseline > $O/log.txt 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --full --gt $sc --batch ${BATCH:-65536} --steps 10 --warmup 3 --no-cpu-baseline > $O/log.txt 2>&1
   python3 - <<PY
 import csv,glob
 for f in glob.glob("$O/**/*kernel_stats.csv",recursive=True):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timeline of the timed region of a `bench.py --steps K --warmup W` run from a rocprofv3 --kernel-trace directory:
+"""Timeline of the timed region of a `bench.py --full --steps K --warmup W` run from a rocprofv3 --kernel-trace directory:
 which kernel of which lane (HIP stream = queue) ran when, relative to the first kernel of the region, and how long the
 region took next to the K steps before it (the settle phase: a full pipeline).
 
