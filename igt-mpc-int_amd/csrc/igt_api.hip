@@ -139,6 +139,15 @@ int validate(const igt_params& p, std::string& why) {
     if (p.C < 64 || p.C % 64) { why = "C must be a positive multiple of 64"; return -1; }
     if (p.n_obs < 0 || p.n_obs > IGT_MAX_OBS) { why = "n_obs must be in [0, IGT_MAX_OBS]"; return -1; }
     if (!(p.dt > 0) || !(p.l_r > 0) || !(p.l_f > 0)) { why = "dt, l_r, l_f must be positive"; return -1; }
+    {
+        const double lim[] = {p.dt, p.l_r, p.l_f, p.v_min, p.v_max, p.a_min, p.a_max, p.df_max, p.jerk_limit,
+                              p.steer_rate_limit, p.ey_lim, p.d_min, p.w_u, p.feas_tol};
+        for (double x : lim)
+            if (!std::isfinite(x)) { why = "dt, l_r, l_f, v_min, v_max, a_min, a_max, df_max, jerk_limit, steer_rate_limit, ey_lim, d_min, w_u and feas_tol must be finite"; return -1; }
+    }
+    if (!(p.jerk_limit > 0)) { why = "jerk_limit must be in (0, inf)"; return -1; }
+    if (!(p.steer_rate_limit >= 0)) { why = "steer_rate_limit must be in [0, inf)"; return -1; }
+    if (!(p.df_max < 1.5707963267948966)) { why = "df_max must be in [0, pi/2)"; return -1; }
     if (p.cand_mode == IGT_CAND_LATTICE) {
         const int g = isqrt_exact(p.C);
         if (g < 2 || 64 % g) { why = "lattice candidates need C = G*G with G in {2,4,8,16,32,64}; use IGT_CAND_TABLE"; return -1; }

@@ -95,10 +95,12 @@ __device__ __forceinline__ double track_steer(const KP& P, double df_prev, doubl
 // (continuous in D, so a last-bit difference in the square root moves nothing; D < 0: a = D, one step back under the limit).
 // A candidate with a large offset therefore accelerates as hard as the limits allow and eases off so as to arrive at v_max
 // with a = 0 -- the NLP optimum's longitudinal shape (profiles/r04_nlp_gap.txt) -- where it used to fail the speed
-// box and leave the winner to a lower row.  D is clipped to 1000 (far from the cap, or no cap: trk_vmax = +inf).
+// box and leave the winner to a lower row.  D is clipped to 1000 (far from the cap).  No cap (trk_vmax = +inf) is no cap at all,
+// as in the oracle: the clipped D would otherwise leave a finite one, sqrt(2000 rate_a) (13.4 m/s^2 at the defaults).
 // n comes from a float square root and is then set right by the two float64 comparisons that define it (r n (n + 1) / 2 <= D <
 // r (n + 1) (n + 2) / 2); the quotient is rcp_nr's (1 ulp).
 __device__ __forceinline__ double track_speed_cap(const KP& P, double v) {
+    if (!(P.trk_vmax < (double)INFINITY)) return (double)INFINITY;
     const double D = fmin((P.trk_vmax - v) * P.inv_dt, 1000.0);
     const double Dp = fmax(D, 0.0);
     const double hr = 0.5 * P.rate_a;
@@ -115,10 +117,12 @@ __device__ __forceinline__ double track_accel_target_uncapped(const KP& P, int k
 // the UNCAPPED target is tried first: if it leaves the speed inside the cap -- S(a_try) <= D, the cap's own inequality, a
 // product and a floor -- the cap, being no smaller than a_try, would have changed nothing (a target above the cap is then out
 // of the step's reach anyway), and the wave skips the square root and the quotient unless one of its lanes needs them.
-// Which lanes take which branch decides nothing: both give the same a_k where both apply.
+// Which lanes take which branch decides nothing: both give the same a_k where both apply.  Without the cap (trk_vmax = +inf,
+// wave-uniform) a_try is the answer.
 __device__ __forceinline__ double track_accel_next(const KP& P, int k, double base, double off, double v, double a_prev) {
     const double tu = track_accel_target_uncapped(P, k, base, off);
     const double a_try = clampd(a_prev + clampd(tu - a_prev, -P.rate_a, P.rate_a), P.a_min, P.a_max);
+    if (!(P.trk_vmax < (double)INFINITY)) return a_try;
     const double D = fmin((P.trk_vmax - v) * P.inv_dt, 1000.0);
     const double n = fmax(floor(a_try * P.inv_rate_a), 0.0);
     const double S = fma(n + 1.0, a_try, -(0.5 * P.rate_a) * n * (n + 1.0));

@@ -361,6 +361,9 @@ __device__ __forceinline__ void rollout_pair(const KP& P, const Scenario<T>& S, 
                     // a sum over them still bounds what the row can gain (the cap only ever acts near v_max > 0).  The capped
                     // recurrence costs a square root and a quotient per step, twice per lane here, ahead of every unit; the float64
                     // path reads the sums accel_rows_kernel leaves instead.
+                    // The uncapped |v| is not an upper bound everywhere though: a feasible row's capped v_k, k < N, is only >= -tol,
+                    // and v_N is not box-checked (v_N >= v_N-1 + dt a_min >= -tol - |a_min| dt).  So |v_k capped| <= |v_k uncapped| + tol
+                    // for k < N and + |a_min| dt more at k = N: those margins are added to the steps' terms below.
                     if (P.v_min >= 0.0) {
                         const double ta = track_accel_target_uncapped(P, k, ba, da[q]);
                         a2 = clampd(a2 + clampd(ta - a2, -P.rate_a, P.rate_a), P.a_min, P.a_max);
@@ -371,6 +374,7 @@ __device__ __forceinline__ void rollout_pair(const KP& P, const Scenario<T>& S, 
                     rem[q] += fmax(fabs(v2), fabs(vn));
                     v2 = vn;
                 }
+                if (P.v_min >= 0.0) rem[q] += fma((double)P.N, P.tol, fabs(P.a_min) * P.dt);
                 rem[q] *= seg_scale * (1.0 + 1e-6);
             }
         } else {

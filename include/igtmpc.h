@@ -91,7 +91,11 @@ enum {
 typedef struct igt_handle igt_handle;
 
 /* The constants MPC_Planner.__init__ hard-codes (mpc.py:45-62) plus the
- * discretisation (N, dt, n_rk4) and the candidate family. */
+ * discretisation (N, dt, n_rk4) and the candidate family.
+ * igt_create refuses (IGT_E_INVALID) anything outside these ranges: every double
+ * below is finite; dt, l_r, l_f > 0; v_min <= v_max; a_min <= a_max;
+ * 0 <= df_max < pi/2 (the steering model takes tan(df)); jerk_limit > 0;
+ * steer_rate_limit >= 0; feas_tol >= 0. */
 typedef struct igt_params {
     int32_t N;         /* horizon                      (mpc.py:38; evaluate.py:69)  */
     int32_t n_rk4;     /* RK4 sub-steps per control step (evaluate.py:109 -> 4)     */
@@ -101,13 +105,13 @@ typedef struct igt_params {
     int32_t cost_mode; /* IGT_COST_*  */
     double dt;         /* fourwayint.yaml:2  */
     double l_r, l_f;   /* mpc.py:49-50       */
-    double v_min, v_max, a_min, a_max, df_max; /* mpc.py:57-62 */
-    double jerk_limit;       /* mpc.py:56 */
-    double steer_rate_limit; /* mpc.py:55 */
+    double v_min, v_max, a_min, a_max, df_max; /* mpc.py:57-62; v_min <= v_max, a_min <= a_max, 0 <= df_max < pi/2 */
+    double jerk_limit;       /* mpc.py:56; > 0 */
+    double steer_rate_limit; /* mpc.py:55; >= 0 */
     double ey_lim;           /* mpc.py:61 */
     double d_min;            /* 2*ca_radius, mpc.py:45 */
     double w_u;              /* 0.05, mpc.py:362 */
-    double feas_tol;         /* inequality verdicts are g <= feas_tol */
+    double feas_tol;         /* inequality verdicts are g <= feas_tol; >= 0 */
     int32_t refine_iters;    /* IGT_CAND_RAMP_HOLD / IGT_CAND_TRACK: extra search passes around the winner (0..4) */
     int32_t reserved;
     double track_ke;         /* IGT_CAND_TRACK: lateral-error gain of the steering feedback [1/m]          (0.3)  */
@@ -119,7 +123,7 @@ typedef struct igt_params {
     double track_vcap;       /* IGT_CAND_TRACK: > 0: the acceleration targets also stay under the speed cap -- the largest
                                 a_k from which a jerk-limited ramp to a = 0 (mpc.py:301-304) still keeps v <= v_max
                                 (mpc.py:316-317): a candidate with a large offset accelerates at the limits and arrives
-                                at v_max with a = 0 instead of failing the speed box; 0 = off                  (1.0)  */
+                                at v_max with a = 0 instead of failing the speed box; 0 = off: no cap at all  (1.0)  */
 } igt_params;
 
 /* Fills *p with the reference's numbers: N=20, dt=0.1, n_rk4=4, C=256, n_obs=1,

@@ -301,6 +301,17 @@ def test_bad_arguments_fail_loudly(igt):
         igt.BatchSolver(N=0)
     with pytest.raises(igt.IgtError):
         igt.BatchSolver(C=576)          # 24 x 24 lattice does not tile 64 lanes
+    # the limits' ranges (include/igtmpc.h igt_params): each refusal names the range it checks
+    for bad, msg in ((dict(jerk_limit=0.0), 'jerk_limit must be in (0, inf)'), (dict(jerk_limit=-0.5), 'jerk_limit must be in (0, inf)'),
+                     (dict(steer_rate_limit=-0.1), 'steer_rate_limit must be in [0, inf)'),
+                     (dict(df_max=np.pi / 2), 'df_max must be in [0, pi/2)'), (dict(df_max=2.0), 'df_max must be in [0, pi/2)'),
+                     (dict(dt=np.inf), 'must be finite'), (dict(v_max=np.inf), 'must be finite'), (dict(a_min=-np.inf), 'must be finite'),
+                     (dict(jerk_limit=np.inf), 'must be finite'), (dict(ey_lim=np.nan), 'must be finite'),
+                     (dict(w_u=np.inf), 'must be finite')):
+        with pytest.raises(igt.IgtError, match=msg.replace('(', r'\(').replace(')', r'\)').replace('[', r'\[')):
+            igt.BatchSolver(**bad)
+    for edge in (dict(steer_rate_limit=0.0), dict(df_max=1.5), dict(jerk_limit=1e-3)):
+        igt.BatchSolver(**edge).close()
     with igt.BatchSolver(cand_mode='table') as s:
         b = _batch(4, np.float32)
         with pytest.raises(igt.IgtError):
