@@ -173,7 +173,7 @@ igt::KP make_kp(const igt_params& p, int F) {
     k.G = p.cand_mode == IGT_CAND_TABLE ? 1 : isqrt_exact(p.C);
     k.refine_it = 0;
     k.df_small = p.df_max < 0.78 ? 1 : 0;
-    { const char* e = getenv("IGT_DEV_FLAGS"); k.dev = (e ? atoi(e) : 0) & 0x1FFFFFFF; }      // bits 29 and 30 are set by the launchers
+    { const char* e = getenv("IGT_DEV_FLAGS"); k.dev = (e ? atoi(e) : 0) & igt::DEV_ENV_MASK; }      // (the launch-time bits are the launchers')
     k.dt = p.dt;
     k.h = p.dt / p.n_rk4;                      // frenet.py:93
     k.l_r = p.l_r;
@@ -243,16 +243,45 @@ template <typename T> const igt::DevNet<T>& net_of(const igt_handle* h);
 template <> const igt::DevNet<float>& net_of<float>(const igt_handle* h) { return h->net_f; }
 template <> const igt::DevNet<double>& net_of<double>(const igt_handle* h) { return h->net_d; }
 
-struct Arena {   // carves 256-byte aligned pieces out of the staging buffer
+// Carves 256-byte aligned pieces out of a device buffer.  Every buffer is laid out by one carve function per entry point, run
+// twice: first on an arena with no base, which only adds up the bytes (arena_bytes; the pointers it hands out are offsets and
+// are never used), then -- once ensure_stage / ensure_work has made the buffer that large -- on the buffer itself.
+struct Arena {
     char* base;
     size_t off;
     template <typename U> U* take(size_t n) {
         off = (off + 255) & ~(size_t)255;
-        U* p = reinterpret_cast<U*>(base + off);
+        U* p = reinterpret_cast<U*>(reinterpret_cast<uintptr_t>(base) + off);
         off += n * sizeof(U);
         return p;
     }
 };
+template <class Carve> size_t arena_bytes(const Carve& carve) {
+    Arena sizing{nullptr, 0};
+    carve(sizing);
+    return sizing.off;
+}
+
+// The argument checks solve and rollout-all share (each entry point checks its own outputs).  B == 0: IGT_OK with *empty set,
+// nothing else is checked.
+int check_batch(const igt_handle* h, int32_t B, const void* x0, const void* u_prev, const void* kparams, const void* flags,
+                const void* obs_xy, const void* tv_sv, const void* enc, const void* u_ws, bool* empty) {
+    *empty = false;
+    if (!h) return fail(IGT_E_INVALID, "null handle");
+    if (B < 0) return fail(IGT_E_INVALID, "B < 0");
+    if (B == 0) { *empty = true; return IGT_OK; }
+    if (!x0 || !u_prev || !kparams || !flags) return fail(IGT_E_INVALID, "null buffer");
+    const igt_params& p = h->p;
+    if (p.n_obs > 0 && !obs_xy) return fail(IGT_E_INVALID, "obs_xy is null but n_obs > 0");
+    if (p.cand_mode == IGT_CAND_TABLE && !h->table_set) return fail(IGT_E_STATE, "candidate table not set");
+    if (u_ws && p.cand_mode != IGT_CAND_RAMP_HOLD && p.cand_mode != IGT_CAND_TRACK)
+        return fail(IGT_E_INVALID, "a warm start needs IGT_CAND_RAMP_HOLD or IGT_CAND_TRACK (the families whose targets are centred on it)");
+    if (p.cost_mode == IGT_COST_VALUE_NET) {
+        if (!h->net_set) return fail(IGT_E_STATE, "value net not set (igt_set_value_net)");
+        if (!tv_sv || !enc) return fail(IGT_E_INVALID, "tv_sv / enc required for the value-net cost");
+    }
+    return IGT_OK;
+}
 
 // the queue builder of small float batches zeroes the search kernel's unit counters itself
 template <typename T>
@@ -264,21 +293,12 @@ template <typename T>
 int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* kparams, const uint32_t* flags,
                const T* obs_xy, const T* tv_sv, const T* enc, const T* u_ws, T* x_out, T* u_out, T* cost_out,
                int32_t* argmin_out, int32_t* status_out, int mem, void* stream) {
-    if (!h) return fail(IGT_E_INVALID, "null handle");
-    if (B < 0) return fail(IGT_E_INVALID, "B < 0");
-    if (B == 0) return IGT_OK;
-    if (!x0 || !u_prev || !kparams || !flags || !x_out || !u_out || !cost_out || !argmin_out || !status_out)
-        return fail(IGT_E_INVALID, "null buffer");
+    bool empty;
+    if (int rc = check_batch(h, B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, u_ws, &empty)) return rc;
+    if (empty) return IGT_OK;
+    if (!x_out || !u_out || !cost_out || !argmin_out || !status_out) return fail(IGT_E_INVALID, "null buffer");
     const igt_params& p = h->p;
-    if (p.n_obs > 0 && !obs_xy) return fail(IGT_E_INVALID, "obs_xy is null but n_obs > 0");
-    if (p.cand_mode == IGT_CAND_TABLE && !h->table_set) return fail(IGT_E_STATE, "candidate table not set");
-    if (u_ws && p.cand_mode != IGT_CAND_RAMP_HOLD && p.cand_mode != IGT_CAND_TRACK)
-        return fail(IGT_E_INVALID, "a warm start needs IGT_CAND_RAMP_HOLD or IGT_CAND_TRACK (the families whose targets are centred on it)");
     const bool value = p.cost_mode == IGT_COST_VALUE_NET;
-    if (value) {
-        if (!h->net_set) return fail(IGT_E_STATE, "value net not set (igt_set_value_net)");
-        if (!tv_sv || !enc) return fail(IGT_E_INVALID, "tv_sv / enc required for the value-net cost");
-    }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const size_t n_x = (size_t)B * 7, n_u = (size_t)B * 2, n_k = (size_t)B * 3;
@@ -295,21 +315,25 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
         A.tv_sv = tv_sv; A.enc = enc; A.u_ws = u_ws;
         A.x_out = x_out; A.u_out = u_out; A.cost_out = cost_out; A.argmin_out = argmin_out; A.status_out = status_out;
     } else if (mem == IGT_MEM_HOST) {
-        const size_t bytes = (n_x + 3 * n_u + n_k + n_obs + n_xo + 2 * n_uo + B) * sizeof(T) + (size_t)B * 12 + 24 * 256;
-        if (int rc = ensure_stage(h, bytes)) return rc;
+        T *dx0, *dup, *dk, *dob, *dtv, *den, *dws, *dxo, *duo, *dco;
+        uint32_t* dfl;
+        int32_t *dam, *dst;
+        size_t in_span = 0;
+        const auto carve = [&](Arena& ar) {      // inputs first, outputs behind them: each group is one contiguous span
+            dx0 = ar.take<T>(n_x); dup = ar.take<T>(n_u); dk = ar.take<T>(n_k);
+            dfl = ar.take<uint32_t>(B); dob = ar.take<T>(n_obs ? n_obs : 1);
+            dtv = ar.take<T>(n_u); den = ar.take<T>(n_u);
+            dws = u_ws ? ar.take<T>(n_uo) : nullptr;
+            in_span = ar.off;
+            dxo = ar.take<T>(n_xo); duo = ar.take<T>(n_uo); dco = ar.take<T>(B);
+            dam = ar.take<int32_t>(B); dst = ar.take<int32_t>(B);
+        };
+        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
         Arena ar{(char*)h->d_stage, 0};
-        // inputs first, outputs behind them: each group is one contiguous span of the arena
-        T* dx0 = ar.take<T>(n_x); T* dup = ar.take<T>(n_u); T* dk = ar.take<T>(n_k);
-        uint32_t* dfl = ar.take<uint32_t>(B); T* dob = ar.take<T>(n_obs ? n_obs : 1);
-        T* dtv = ar.take<T>(n_u); T* den = ar.take<T>(n_u);
-        T* dws = u_ws ? ar.take<T>(n_uo) : nullptr;
-        const size_t in_span = ar.off;
-        T* dxo = ar.take<T>(n_xo);
+        carve(ar);
         out_begin = (size_t)((char*)dxo - (char*)h->d_stage);
-        T* duo = ar.take<T>(n_uo); T* dco = ar.take<T>(B);
-        int32_t* dam = ar.take<int32_t>(B); int32_t* dst = ar.take<int32_t>(B);
         out_end = ar.off;
-        packed = bytes <= PACK_BYTES;
+        packed = out_end <= PACK_BYTES;
         if (packed) {
             char* hs = (char*)h->h_stage;
             auto put = [&](const void* src, const void* d, size_t nbytes) {
@@ -348,7 +372,7 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     // units per scenario of the search kernel: 128-candidate slices (float, two candidates per lane) or 64 (double)
     const size_t Wk = sizeof(T) == 4 ? ((size_t)p.C + 127) / 128 : (size_t)p.C / 64;
     const size_t W = compact ? 1 : (value ? (size_t)p.C / 64 : Wk);
-    const bool exact64 = sizeof(T) == 8 && (h->kp.dev & 1024);      // developer switch: oracle-order double kernels
+    const bool exact64 = sizeof(T) == 8 && (h->kp.dev & igt::DEV_EXACT64);      // developer switch: oracle-order double kernels
     // small float batches: emit in 4 pieces from checkpoints of the search pass.  Measured (search + emit): +15 % at
     // B = 1024, +12 % at 2048, +3 % at 4096, -1 % at 8192 -- but the records are ~150 MB of HBM writes per B = 4096 solve
     // against ~1 MB of algorithmic traffic, so they are only spent where emit latency dominates.
@@ -360,7 +384,6 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
         if (sizeof(T) == 4 && v >= 1 && v <= igt::SEG_MAX_PARTS && p.N % v == 0 && p.N >= 2 * v) ck_parts = v;
     }
     const bool use_ckpt = ck_parts > 1;
-    const size_t ckpt_bytes = use_ckpt ? (size_t)(ck_parts - 1) * B * Wk * igt::SEG_UNIT_DOUBLES * 8 + 256 : 0;
     // small double batches -- no more units than the chip has SIMDs, B <= 256 at 256 candidates -- : the search pass keeps
     // every trajectory and emit copies the winner's (igt_kernels_common.h CaptureSink; 97 KB of stores per unit at N = 20,
     // hidden behind a lone wave's dependent chains; with several units per SIMD they are not: a closed loop of 512
@@ -369,34 +392,29 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     if (h->dev_traj_max >= 0) traj_max_units = (size_t)std::min(h->dev_traj_max, 8192) * Wk;   // sweeps: a batch size
     const bool capture = sizeof(T) == 8 && !exact64 && (size_t)B * Wk <= traj_max_units && (p.C % 64) == 0;
     const size_t traj_doubles = capture ? (size_t)B * Wk * igt::traj_unit_doubles(p.N) : 0;
+    // double path, progress cost: the unit winners' horizon checkpoints for the emit in pieces (records behind the partials)
+    const bool ck_records = sizeof(T) == 8 && !value && !exact64 && p.N >= 8;
+    const bool trace = (h->kp.dev & igt::DEV_TRACE) != 0;      // developer trace: 32 B per unit behind the counters
+    const size_t n_rec = value ? (size_t)B * p.C : 0;
     double* d_cpar = nullptr;
-    {
-        const size_t n_rec = value ? (size_t)B * p.C : 0;
-        // double path, progress cost: the unit winners' horizon checkpoints for the emit in pieces (24 doubles per unit)
-        const bool ck_ok = sizeof(T) == 8 && !value && !exact64 && p.N >= 8;
-        const size_t ck_doubles = ck_ok ? (size_t)B * W * igt::CK_RECORD_DOUBLES : 0;
-        // double path: the acceleration rows' travel sums [B, G] (accel_rows_kernel -> the tracking family's incumbent bound)
-        const size_t rows_doubles = sizeof(T) == 8 ? (size_t)B * (p.cand_mode == IGT_CAND_TABLE ? 1 : isqrt_exact(p.C)) : 0;
-        const size_t need = traj_doubles * 8 + 256 + (size_t)B * 16 + (ck_doubles + rows_doubles) * 8 + 256 + (size_t)B * W * 12 + (size_t)B * 56 + 8192 + ckpt_bytes + (size_t)(B + 8) * Wk * 36 + 256 + n_rec * (2 * sizeof(T) + 16) +
-                            (value ? (size_t)B * igt::VN_H * sizeof(T) + (size_t)B * Wk * 8 + (size_t)B * 8 + n_rec * 4 + 512 : 0) + 20 * 256;
-        if (int rc = ensure_work(h, need, st)) return rc;
-        Arena wa{(char*)h->d_work, 0};
-        A.part_J = wa.take<double>((size_t)B * W + (sizeof(T) == 8 ? (size_t)2 * B : (size_t)B) + rows_doubles + ck_doubles);  // double path: + [B] live-row masks + [B] incumbents + [B G] row sums + checkpoint records (igt_kernels_f64.hip); float path: + [B] incumbents
-        A.ck_ok = ck_ok;
+    const auto carve = [&](Arena& wa) {
+        A.part_J = wa.take<double>(igt::PartJTail<T>(nullptr, B, (int)W, h->kp.G).doubles(ck_records));
+        const igt::PartJTail<T> tail(A.part_J, B, (int)W, h->kp.G);
+        A.incumbents = tail.incumbents();
+        if constexpr (sizeof(T) == 8) {
+            A.row_mask = tail.masks();
+            A.row_rems = tail.row_rems();
+            A.ck_records = ck_records ? tail.ck_records() : nullptr;
+        }
         A.part_c = wa.take<int32_t>((size_t)B * W);
         d_cpar = wa.take<double>((size_t)B * 4);
-        const bool trace = (h->kp.dev & 256) != 0;      // developer trace: 32 B per unit behind the counters
-        A.work_counter = wa.take<unsigned>(1024 + (trace ? (size_t)((B + 7) / 8) * 8 * Wk * 8 : 0));
-        A.n_cu = h->n_cu;
-        A.waves_per_simd = h->concurrency >= 3 ? 1 : 2;      // two solves in flight do not overlap on this runtime (igtmpc.h)
+        A.work_counter = wa.take<unsigned>(igt::WORK_COUNTER_WORDS + (trace ? (size_t)((B + 7) / 8) * 8 * Wk * 8 : 0));
         // small batches: the search pass leaves horizon checkpoints, emit rolls the winner's four quarters at once
         A.ckpt = use_ckpt ? wa.take<double>((size_t)(ck_parts - 1) * B * Wk * igt::SEG_UNIT_DOUBLES) : nullptr;
-        A.ck_parts = ck_parts;
         // small batches: the search queues are sorted longest unit first (build_queues_kernel; 3-5 % up to B = 4096,
         // nothing from 8192 on)
         A.queue_order = B <= 6144 ? wa.take<unsigned>((size_t)((B + 7) / 8) * 8 * Wk) : nullptr;
         if constexpr (sizeof(T) == 8) A.traj = capture ? wa.take<double>(traj_doubles) : nullptr;
-        if constexpr (sizeof(T) == 8) A.row_mask = reinterpret_cast<unsigned long long*>(A.part_J + (size_t)B * W);
         if (value) {
             A.rec_J = wa.take<double>(n_rec);
             A.rec_sN = wa.take<T>(n_rec);
@@ -412,7 +430,13 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
                 A.live_idx = wa.take<unsigned>(n_rec);
             }
         }
-    }
+    };
+    if (int rc = ensure_work(h, arena_bytes(carve), st)) return rc;
+    Arena wa{(char*)h->d_work, 0};
+    carve(wa);
+    A.n_cu = h->n_cu;
+    A.waves_per_simd = h->concurrency >= 3 ? 1 : 2;      // two solves in flight do not overlap on this runtime (igtmpc.h)
+    A.ck_parts = ck_parts;
     if (h->prof) HIPCHK(hipEventRecord(h->ev[0], st));
     igt::KP kp = h->kp;
     for (int it = 0; it <= p.refine_iters; ++it) {
@@ -450,12 +474,12 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     HIPCHK(igt::launch_emit<T>(kp, B, (int)W, A, st));
     if (h->prof) { HIPCHK(hipEventRecord(h->ev[2], st)); h->ev_recorded = true; }
 
-    if (h->kp.dev & 256) {      // developer trace -> $IGT_DEV_TRACE (binary u64[units][4])
+    if (h->kp.dev & igt::DEV_TRACE) {      // developer trace -> $IGT_DEV_TRACE (binary u64[units][4])
         if (const char* path = std::getenv("IGT_DEV_TRACE")) {
             HIPCHK(hipStreamSynchronize(st));
             const size_t n = (size_t)((B + 7) / 8) * 8 * Wk * 4;
             std::vector<unsigned long long> tr(n);
-            HIPCHK(hipMemcpy(tr.data(), reinterpret_cast<char*>(A.work_counter) + 4096, n * 8, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(tr.data(), igt::unit_trace(A.work_counter), n * 8, hipMemcpyDeviceToHost));
             if (FILE* f = std::fopen(path, "wb")) { std::fwrite(tr.data(), 8, n, f); std::fclose(f); }
         }
     }
@@ -483,20 +507,12 @@ template <typename T>
 int rollout_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* kparams, const uint32_t* flags,
                  const T* obs_xy, const T* tv_sv, const T* enc, const T* u_ws, T* X_all, T* U_all, T* cost_all,
                  uint32_t* viol_all, int mem, void* stream) {
-    if (!h) return fail(IGT_E_INVALID, "null handle");
-    if (B < 0) return fail(IGT_E_INVALID, "B < 0");
-    if (B == 0) return IGT_OK;
-    if (!x0 || !u_prev || !kparams || !flags || !cost_all || !viol_all) return fail(IGT_E_INVALID, "null buffer");
+    bool empty;
+    if (int rc = check_batch(h, B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, u_ws, &empty)) return rc;
+    if (empty) return IGT_OK;
+    if (!cost_all || !viol_all) return fail(IGT_E_INVALID, "null buffer");
     const igt_params& p = h->p;
-    if (p.n_obs > 0 && !obs_xy) return fail(IGT_E_INVALID, "obs_xy is null but n_obs > 0");
-    if (p.cand_mode == IGT_CAND_TABLE && !h->table_set) return fail(IGT_E_STATE, "candidate table not set");
-    if (u_ws && p.cand_mode != IGT_CAND_RAMP_HOLD && p.cand_mode != IGT_CAND_TRACK)
-        return fail(IGT_E_INVALID, "a warm start needs IGT_CAND_RAMP_HOLD or IGT_CAND_TRACK (the families whose targets are centred on it)");
     const bool value = p.cost_mode == IGT_COST_VALUE_NET;
-    if (value) {
-        if (!h->net_set) return fail(IGT_E_STATE, "value net not set (igt_set_value_net)");
-        if (!tv_sv || !enc) return fail(IGT_E_INVALID, "tv_sv / enc required for the value-net cost");
-    }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const size_t n_x = (size_t)B * 7, n_u = (size_t)B * 2, n_k = (size_t)B * 3;
@@ -512,23 +528,26 @@ int rollout_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T
         A.tv_sv = tv_sv; A.enc = enc; A.u_ws = u_ws;
     } else if (mem == IGT_MEM_HOST) {
         const size_t n_ws = u_ws ? (size_t)B * 2 * p.N : 0;
-        const size_t bytes = (n_x + 3 * n_u + n_k + n_obs + (X_all ? n_X : 0) + (U_all ? n_U : 0) + n_c + n_ws) * sizeof(T) +
-                             n_c * 4 + (size_t)B * 4 + 24 * 256;
-        if (int rc = ensure_stage(h, bytes)) return rc;
+        T *dx0, *dup, *dk, *dob, *dtv, *den, *dws;
+        uint32_t* dfl;
+        const auto carve = [&](Arena& ar) {
+            dx0 = ar.take<T>(n_x); dup = ar.take<T>(n_u); dk = ar.take<T>(n_k);
+            dfl = ar.take<uint32_t>(B); dob = ar.take<T>(n_obs ? n_obs : 1);
+            dX = X_all ? ar.take<T>(n_X) : nullptr;
+            dU = U_all ? ar.take<T>(n_U) : nullptr;
+            dc = ar.take<T>(n_c); dv = ar.take<uint32_t>(n_c);
+            dtv = ar.take<T>(n_u); den = ar.take<T>(n_u);
+            dws = u_ws ? ar.take<T>(n_ws) : nullptr;
+        };
+        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
         Arena ar{(char*)h->d_stage, 0};
-        T* dx0 = ar.take<T>(n_x); T* dup = ar.take<T>(n_u); T* dk = ar.take<T>(n_k);
-        uint32_t* dfl = ar.take<uint32_t>(B); T* dob = ar.take<T>(n_obs ? n_obs : 1);
-        dX = X_all ? ar.take<T>(n_X) : nullptr;
-        dU = U_all ? ar.take<T>(n_U) : nullptr;
-        dc = ar.take<T>(n_c); dv = ar.take<uint32_t>(n_c);
-        T* dtv = ar.take<T>(n_u); T* den = ar.take<T>(n_u);
+        carve(ar);
         if (value) {
             HIPCHK(hipMemcpyAsync(dtv, tv_sv, n_u * sizeof(T), hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(den, enc, n_u * sizeof(T), hipMemcpyHostToDevice, st));
         }
         A.tv_sv = dtv; A.enc = den;
         if (u_ws) {
-            T* dws = ar.take<T>(n_ws);
             HIPCHK(hipMemcpyAsync(dws, u_ws, n_ws * sizeof(T), hipMemcpyHostToDevice, st));
             A.u_ws = dws;
         }
@@ -542,14 +561,16 @@ int rollout_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T
         return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
     }
     if (value) {   // records -> value_kernel fills cost_all / viol_all with the terminal term included
-        const size_t need = n_c * (2 * sizeof(T) + 12) + (size_t)B * igt::VN_H * sizeof(T) + 8 * 256;
-        if (int rc = ensure_work(h, need, st)) return rc;
+        const auto carve = [&](Arena& wa) {
+            A.rec_J = wa.take<double>(n_c);
+            A.rec_sN = wa.take<T>(n_c);
+            A.rec_vN = wa.take<T>(n_c);
+            A.rec_viol = wa.take<uint32_t>(n_c);
+            A.p_vec = wa.take<T>((size_t)B * igt::VN_H);
+        };
+        if (int rc = ensure_work(h, arena_bytes(carve), st)) return rc;
         Arena wa{(char*)h->d_work, 0};
-        A.rec_J = wa.take<double>(n_c);
-        A.rec_sN = wa.take<T>(n_c);
-        A.rec_vN = wa.take<T>(n_c);
-        A.rec_viol = wa.take<uint32_t>(n_c);
-        A.p_vec = wa.take<T>((size_t)B * igt::VN_H);
+        carve(wa);
     }
     HIPCHK(igt::launch_rollout_all<T>(h->kp, B, A, dX, dU, dc, dv, st));
     if (value) HIPCHK(igt::launch_value<T>(h->kp, B, net_of<T>(h), A, dc, dv, st));
@@ -576,9 +597,11 @@ int frenet_step_impl(igt_handle* h, int32_t n, const T* x, const T* u, const T* 
     const T *dx = x, *du = u, *dk = kparams;
     T* dout = x_next;
     if (mem == IGT_MEM_HOST) {
-        if (int rc = ensure_stage(h, (2 * n_x + n_u + n_k) * sizeof(T) + 8 * 256)) return rc;
+        T *a, *b, *c;
+        const auto carve = [&](Arena& ar) { a = ar.take<T>(n_x); b = ar.take<T>(n_u); c = ar.take<T>(n_k); dout = ar.take<T>(n_x); };
+        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
         Arena ar{(char*)h->d_stage, 0};
-        T* a = ar.take<T>(n_x); T* b = ar.take<T>(n_u); T* c = ar.take<T>(n_k); dout = ar.take<T>(n_x);
+        carve(ar);
         HIPCHK(hipMemcpyAsync(a, x, n_x * sizeof(T), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(b, u, n_u * sizeof(T), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(c, kparams, n_k * sizeof(T), hipMemcpyHostToDevice, st));
@@ -616,13 +639,17 @@ int forecast_impl(igt_handle* h, int32_t B, const T* ego_xyh, const T* opp, cons
     const int32_t *dr = opp_route, *dhp = has_plan;
     T *dout = obs_xy, *dtv = tv_sv;
     if (mem == IGT_MEM_HOST) {
-        const size_t bytes = (n_e + n_o + n_pairs + (plans ? n_px + n_pu : 0) + n_out + n_tv) * sizeof(T) + n_pairs * 8 + 16 * 256;
-        if (int rc = ensure_stage(h, bytes)) return rc;
+        T *a0, *a1, *a2, *a5, *a6;
+        int32_t *a3, *a4;
+        const auto carve = [&](Arena& ar) {
+            a0 = ar.take<T>(n_e); a1 = ar.take<T>(n_o); a2 = ar.take<T>(n_pairs);
+            a3 = ar.take<int32_t>(n_pairs); a4 = ar.take<int32_t>(n_pairs);
+            a5 = ar.take<T>(plans ? n_px : 1); a6 = ar.take<T>(plans ? n_pu : 1);
+            dout = ar.take<T>(n_out); dtv = ar.take<T>(n_tv);
+        };
+        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
         Arena ar{(char*)h->d_stage, 0};
-        T* a0 = ar.take<T>(n_e); T* a1 = ar.take<T>(n_o); T* a2 = ar.take<T>(n_pairs);
-        int32_t* a3 = ar.take<int32_t>(n_pairs); int32_t* a4 = ar.take<int32_t>(n_pairs);
-        T* a5 = ar.take<T>(plans ? n_px : 1); T* a6 = ar.take<T>(plans ? n_pu : 1);
-        dout = ar.take<T>(n_out); dtv = ar.take<T>(n_tv);
+        carve(ar);
         HIPCHK(hipMemcpyAsync(a0, ego_xyh, n_e * sizeof(T), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(a1, opp, n_o * sizeof(T), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(a2, opp_a, n_pairs * sizeof(T), hipMemcpyHostToDevice, st));
@@ -659,9 +686,11 @@ int cartesian_impl(igt_handle* h, int32_t n, int32_t steps, const T* z0, const T
     const T *dz = z0, *du = u;
     T* dout = z_out;
     if (mem == IGT_MEM_HOST) {
-        if (int rc = ensure_stage(h, (n_z + n_u + n_o) * sizeof(T) + 8 * 256)) return rc;
+        T *a, *b;
+        const auto carve = [&](Arena& ar) { a = ar.take<T>(n_z); b = ar.take<T>(n_u ? n_u : 1); dout = ar.take<T>(n_o); };
+        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
         Arena ar{(char*)h->d_stage, 0};
-        T* a = ar.take<T>(n_z); T* b = ar.take<T>(n_u ? n_u : 1); dout = ar.take<T>(n_o);
+        carve(ar);
         HIPCHK(hipMemcpyAsync(a, z0, n_z * sizeof(T), hipMemcpyHostToDevice, st));
         if (n_u) HIPCHK(hipMemcpyAsync(b, u, n_u * sizeof(T), hipMemcpyHostToDevice, st));
         dz = a; du = b;
@@ -745,7 +774,7 @@ int igt_create(const igt_params* p, int device, igt_handle** out) {
     if (validate(*p, why)) return fail(IGT_E_INVALID, why);
 #if !IGT_DEV_KERNELS
     if (const char* e = getenv("IGT_DEV_FLAGS"))
-        if (atoi(e) & IGT_DEV_KERNEL_FLAGS)
+        if (atoi(e) & igt::DEV_KERNEL_FLAGS)
             return fail(IGT_E_INVALID, "IGT_DEV_FLAGS selects developer kernels (32 / 1024 / 2048) that this library is built without; "
                                        "load libigtmpc_dev.so (built with IGT_DEV_KERNELS=1)");
 #endif

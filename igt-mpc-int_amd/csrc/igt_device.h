@@ -24,18 +24,48 @@
 #ifndef IGT_DEV_KERNELS
 #define IGT_DEV_KERNELS 0
 #endif
-#define IGT_DEV_KERNEL_FLAGS (32 | 1024 | 2048)
 
 namespace igt {
+
+// The bits of KP::dev.  IGT_DEV_FLAGS sets the developer switches (A/B measurements only, results do not depend on them); their
+// values are part of the interface -- DESIGN.md, profiles/ and tools/ cite them by number, igtmpc/_lib.py mirrors them (a test
+// checks the two lists agree).  The launch-time bits are set by the launchers on their copy of KP, never by the environment.
+enum DevFlag : int {
+    DEV_NO_SLICES = 1,                 // units in index order, not steering slices / acceleration-row units
+    DEV_NO_EARLY_EXIT = 2,             // a unit rolls the whole horizon even when all its candidates have failed
+    DEV_NO_STEER_TABLE = 4,            // float64 search: every lane computes its steering, no table in LDS
+    DEV_NO_QUEUE_ORDER = 16,           // the search queues in index order, not longest unit first
+    DEV_WAVES3 = 32,                   // developer kernels: the 3-waves-per-SIMD builds of the search
+    DEV_TRACE = 256,                   // unit trace (written to $IGT_DEV_TRACE; unit_trace)
+    DEV_NO_STEAL = 512,                // a wave takes units from its own queue only
+    DEV_EXACT64 = 1024,                // developer kernels: the oracle-order float64 kernels
+    DEV_LITERAL = 2048,                // developer kernels: the literal north_star mapping
+    DEV_LATE_ITEMS = 15 << 12,         // field: items per wave at the end of a queue whose index is fetched late (dev_late_items)
+    DEV_NO_FAR = 65536,                // no roll-out without the Cartesian rows for obstacles out of reach
+    DEV_NO_PRUNE = 131072,             // float64 value-net cost: no pruning of the entries before the network
+    DEV_STEER_SLICES = 262144,         // tracking family: steering slices instead of acceleration-row units
+    DEV_NO_CAPTURE = 524288,           // small float64 batches: emit rolls the winner again instead of copying its trajectory
+    DEV_KEEP_QUEUES = 1048576,         // small float64 batches that keep trajectories still run the queues (search_is_static)
+    DEV_ALL_ROWS = 2097152,            // float64: units of all acceleration rows, no live-row masks (packs_live_rows)
+    DEV_WHOLE_COLUMNS = 4194304,       // live-row steering slices: a unit holds whole columns
+    DEV_NO_BOUND = 8388608,            // tracking family: no incumbent bound in the search
+    DEV_NO_SEG_EMIT = 16777216,        // float64 emit rolls the winner in one piece, not from the search's checkpoints
+    DEV_SEPARATE_QUEUES = 33554432,    // float64: the queues are sorted by build_queues_kernel, not inside accel_rows_kernel
+    // launch-time bits: what the search kernels find behind the partials (igt_launch.h PartJTail)
+    DEV_LAUNCH_INCUMBENTS = 1 << 28,   // float: the [B] incumbents
+    DEV_LAUNCH_CKPT = 1 << 29,         // float64: the checkpoint records for emit_seg_f64_kernel
+    DEV_LAUNCH_LIVE_ROWS = 1 << 30,    // float64: the live-row masks of accel_rows_kernel
+};
+// the kernels only libigtmpc_dev.so carries (the shipped library refuses these flags)
+constexpr int DEV_KERNEL_FLAGS = DEV_WAVES3 | DEV_EXACT64 | DEV_LITERAL;
+// what IGT_DEV_FLAGS may set: every bit below the launch-time ones
+constexpr int DEV_ENV_MASK = DEV_LAUNCH_INCUMBENTS - 1;
+__host__ __device__ inline unsigned dev_late_items(int dev) { return ((unsigned)dev & DEV_LATE_ITEMS) >> 12; }
 
 struct KP {  // kernel parameters (by value -> SGPRs)
     int N, n_rk4, C, n_obs, cand_mode, cost_mode, F, G, hi_order, refine_it;
     int df_small;   // df_max < pi/4: generated steering angles need no range reduction
-    // developer switches (env IGT_DEV_FLAGS; A/B measurements only, results do not depend on them):
-    //   1 slices along the acceleration axis, 2 no early exit, 4 no steering table (f64 search), 8 / 32 force 2 / 3 search waves per SIMD,
-    //   16 no longest-first queue order, 256 unit trace (with IGT_DEV_TRACE=<file>), 512 no stealing between queues,
-    //   bits 12-15: items per wave at the end of a queue whose index is fetched late (default 4)
-    int dev;
+    int dev;        // DevFlag bits: IGT_DEV_FLAGS, and the launch-time bits
     double dt, h, l_r, lr_ratio, v_min, v_max, a_min, a_max, df_max;
     double rate_a, rate_df, ey_lim, dmin2, w_u, tol;
     double trk_ke, trk_span, trk_blim;      // IGT_CAND_TRACK: lateral gain [1/m], span of the slip-angle offsets, |beta| limit

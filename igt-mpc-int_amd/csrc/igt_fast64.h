@@ -388,10 +388,10 @@ __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>&
                                             const unsigned long long* inc = nullptr, double* ck = nullptr, int seg_k0 = 0,
                                             int seg_k1 = 0, const double* __restrict__ rem_rows = nullptr) {
     constexpr bool BOUND = CAND == CAND_TRACK && BOOK && UNIFORM && EARLY_EXIT;
-    // search on units of live acceleration rows (igt_kernels_f64.hip accel_rows_kernel; launch-time bit 30 of KP::dev): the speed
+    // search on units of live acceleration rows (igt_kernels_f64.hip accel_rows_kernel; DEV_LAUNCH_LIVE_ROWS): the speed
     // box and the terminal set read the row's (a, v) recurrence alone and were judged there, with these statements -- every lane
     // that holds a candidate holds one of a row that passed: not judged again (74 half-planes per lane at the last step)
-    const bool rows_judged = BOOK && EARLY_EXIT && UNIFORM && CAND != CAND_TABLE && (P.dev & (1 << 30)) != 0;
+    const bool rows_judged = BOOK && EARLY_EXIT && UNIFORM && CAND != CAND_TABLE && (P.dev & DEV_LAUNCH_LIVE_ROWS) != 0;
     constexpr int CKF = CAND == CAND_TRACK ? 8 : 5;            // fields this family writes
     constexpr bool KEEP_PSI = Sink::kKeepsStates;
     // search only needs feasible-or-not: |ey|, box v and collision are folded into one running maximum, compared with
@@ -570,7 +570,7 @@ __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>&
         if (BOOK && UNIFORM && EARLY_EXIT) {
             // search only: once every candidate of the slice has failed a verdict, nothing rolled further can win
             const bool lost = (viol != 0) | (LEAN && gmax > P.tol);
-            if (__all(lost) && !(P.dev & 2)) { dead = true; break; }
+            if (__all(lost) && !(P.dev & DEV_NO_EARLY_EXIT)) { dead = true; break; }
         }
         if (BOOK && XY && k >= 1) {                                                  // collision, mpc.py:223-226
             for (int o = 0; o < P.n_obs; ++o) {

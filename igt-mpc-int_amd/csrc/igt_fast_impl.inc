@@ -513,7 +513,7 @@ __device__ __forceinline__ void rollout_pair(const KP& P, const Scenario<T>& S, 
             bool lost = true;
 #pragma unroll
             for (int q = 0; q < NV; ++q) lost &= (viol[q] != 0) | (LEAN && gmax[q] > tol);
-            if (__all(lost) && !(P.dev & 2)) { dead = true; break; }
+            if (__all(lost) && !(P.dev & DEV_NO_EARLY_EXIT)) { dead = true; break; }
         }
         if (BOOK && XY) {                                              // collision, mpc.py:223-226 (k >= 1)
             // obstacle 0 of the NEXT state is requested now and used one trip later: a scalar load's latency is

@@ -100,16 +100,15 @@ struct PairSink {
 // steering column: (i, j) and (i + G/2, j).  Otherwise: chunks of 64 in index order, two per slice.
 template <int CAND>
 __device__ __forceinline__ bool steering_slices(const KP& P, int W) {
-    return CAND != CAND_TABLE && P.G * P.G == P.C && W * 128 == P.C && P.G % W == 0 && !(P.dev & 1);
+    return CAND != CAND_TABLE && P.G * P.G == P.C && W * 128 == P.C && P.G % W == 0 && !(P.dev & DEV_NO_SLICES);
 }
 // Tracking family (its steering is a feedback on the rolled state: its candidates fail on what the ACCELERATION row decides,
 // igt_kernels_f64.hip): unit p takes the G / W acceleration rows G-1 - p G/W downwards with all G steering offsets -- the rows
 // that make most progress in unit 0, whose best cost is the incumbent the later units are pruned against (igt_device.h,
-// igt_fast64.h BOUND).  A lane holds (row, j) and (row - 64 / G, j).  G in {16, 32, 64}; IGT_DEV_FLAGS = 262144: steering slices.
-constexpr int DEV_INCUMBENTS = 1 << 30;      // launch-time bit of KP::dev (float kernels): [B] incumbent keys behind the partials
+// igt_fast64.h BOUND).  A lane holds (row, j) and (row - 64 / G, j).  G in {16, 32, 64}; DEV_STEER_SLICES: steering slices.
 template <int CAND>
 __device__ __forceinline__ bool accel_units(const KP& P, int W) {
-    return CAND == CAND_TRACK && P.G * P.G == P.C && W * 128 == P.C && P.G >= 16 && P.G <= 64 && !(P.dev & (1 | 262144));
+    return CAND == CAND_TRACK && P.G * P.G == P.C && W * 128 == P.C && P.G >= 16 && P.G <= 64 && !(P.dev & (DEV_NO_SLICES | DEV_STEER_SLICES));
 }
 template <int CAND>
 __device__ __forceinline__ void slice_candidates(const KP& P, int W, int p, int lane, int (&cidx)[2]) {
@@ -157,7 +156,7 @@ __device__ __forceinline__ void candidate_slot(const KP& P, int W, int c, int& p
 // candidate index).
 template <int CAND, bool HI, bool VALUE, bool CKPT>
 __device__ __forceinline__ void search_unit(const KP& P, int W, int b, int p, double* __restrict__ ckpt, int ck_parts,
-                                            int n_units,
+                                            int B,
                                             const float* __restrict__ x0,
                                             const float* __restrict__ u_prev, const float* __restrict__ kparams,
                                             const uint32_t* __restrict__ flags, const float* __restrict__ obs,
@@ -167,7 +166,7 @@ __device__ __forceinline__ void search_unit(const KP& P, int W, int b, int p, do
                                             float* __restrict__ rec_vN, double* __restrict__ rec_J,
                                             uint32_t* __restrict__ rec_viol, unsigned* __restrict__ rec_count,
                                             int32_t* __restrict__ rec_b) {
-    const int gw = b * W + p;
+    const int gw = b * W + p, n_units = B * W;
     const int lane = threadIdx.x & 63;
     Scenario<float> S;
     load_scenario<float>(S, P, b, x0, u_prev, kparams, flags, obs, cpar);
@@ -177,12 +176,13 @@ __device__ __forceinline__ void search_unit(const KP& P, int W, int b, int p, do
     double J[2], sN[2], vN[2];
     unsigned viol[2];
     const Ckpt ck{CKPT && ck_parts > 1 ? ckpt : nullptr, (size_t)n_units, gw, lane, ck_parts > 1 ? P.N / ck_parts : 0};
-    // the scenario's incumbent (tracking family, progress cost): [B] keys behind the [B W] partials
-    unsigned long long* inc = (CAND == CAND_TRACK && !VALUE && (P.dev & DEV_INCUMBENTS))
-                                  ? reinterpret_cast<unsigned long long*>(part_J + n_units) + b : nullptr;
+    // the scenario's incumbent (tracking family, progress cost): behind the partials (PartJTail)
+    unsigned long long* inc = (CAND == CAND_TRACK && !VALUE && (P.dev & DEV_LAUNCH_INCUMBENTS))
+                                  ? PartJTail<float>(part_J, B, W, P.G).incumbents() + b
+                                  : nullptr;
     // units whose obstacles are out of every speed-feasible candidate's reach roll without the Cartesian rows (igt_device.h
     // obstacles_out_of_reach); the builds that leave checkpoints for emit need x, y
-    if (!CKPT && !(P.dev & 65536) && obstacles_out_of_reach<float>(P, S, lane))
+    if (!CKPT && !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<float>(P, S, lane))
         rollout_pair<CAND, HI, true, true, float, NullSink, true, false, false, false>(P, S, cidx, table, cinf, sink, J, viol, sN, vN, ck,
                                                                                        Seg{0, 0, nullptr, 0}, inc);
     else
@@ -247,9 +247,9 @@ __device__ __forceinline__ void search_unit(const KP& P, int W, int b, int p, do
 template <int CAND, bool HI, bool VALUE, bool CKPT>
 __device__ __forceinline__ void search_waves_f32(IGT_SEARCH_ARGS) {
     search_waves(P, B, W, queues, work_counter, order, order_stride, [&](int b, int p) {
-        search_unit<CAND, HI, VALUE, CKPT>(P, W, b, p, ckpt, ck_parts, B * W, x0, u_prev, kparams, flags, obs, table, cinf, cpar,
+        search_unit<CAND, HI, VALUE, CKPT>(P, W, b, p, ckpt, ck_parts, B, x0, u_prev, kparams, flags, obs, table, cinf, cpar,
                                            part_J, part_c, rec_sN, rec_vN, rec_J, rec_viol, rec_count, rec_b);
-    }, CAND == CAND_TRACK && !VALUE && (P.dev & DEV_INCUMBENTS) != 0);      // unit-rank-major items: every unit 0 before any unit 1
+    }, CAND == CAND_TRACK && !VALUE && (P.dev & DEV_LAUNCH_INCUMBENTS) != 0);      // unit-rank-major items: every unit 0 before any unit 1
 }
 #if IGT_DEV_KERNELS
 template <int CAND, bool HI, bool VALUE>
@@ -591,7 +591,7 @@ __global__ __launch_bounds__(256) void cartesian_euler_kernel(int n, int steps, 
 // whether launch_search_fast will run build_queues_kernel (which also zeroes the unit counters)
 bool search_builds_queues(const KP& P, int B, const SolveArgs<float>& A) {
     const int W = (P.C + 127) / 128;
-    return A.queue_order && W <= 256 && ((B + 7) / 8) * W <= QB_THREADS * QB_TRIPS && !(P.dev & 16);
+    return A.queue_order && W <= 256 && ((B + 7) / 8) * W <= QB_THREADS * QB_TRIPS && !(P.dev & DEV_NO_QUEUE_ORDER);
 }
 template <int CAND, bool HI, bool VALUE>
 static hipError_t launch_search_fast(const KP& P, int B, const SolveArgs<float>& A, hipStream_t st) {
@@ -599,8 +599,8 @@ static hipError_t launch_search_fast(const KP& P, int B, const SolveArgs<float>&
     const size_t total = (size_t)B * W;
     // persistent waves on per-XCD queues, 2 per SIMD.  The 3-per-SIMD build (168 VGPRs, a spill around each unit) was
     // ahead on big batches in round 1; with the sub-step variants unrolled it spills 228 B/lane and is behind at every
-    // size but one (B = 32 768: +0.7 %) -- it stays selectable for A/B runs (IGT_DEV_FLAGS = 32)
-    const bool o3 = IGT_DEV_KERNELS && (P.dev & 32) != 0;
+    // size but one (B = 32 768: +0.7 %) -- it stays selectable for A/B runs (DEV_WAVES3)
+    const bool o3 = IGT_DEV_KERNELS && (P.dev & DEV_WAVES3) != 0;
     const size_t slots = (size_t)A.n_cu * 4 * (o3 ? 3 : (A.waves_per_simd == 1 ? 1 : 2));
     const size_t grid = total < slots ? total : slots;
     const unsigned* order = nullptr;
@@ -609,10 +609,11 @@ static hipError_t launch_search_fast(const KP& P, int B, const SolveArgs<float>&
     if constexpr (CAND == CAND_TRACK && !VALUE) {
         // tracking family, progress cost: units of acceleration rows, pruned against the scenario's incumbent (igt_fast64.h
         // BOUND).  The [B] keys behind the partials start every pass at "none" (all ones: above every cost's key).
-        if (P.G * P.G == P.C && W * 128 == P.C && P.G >= 16 && P.G <= 64 && !(P.dev & (1 | 262144 | 8388608)) && W > 1) {
-            hipError_t e = hipMemsetAsync(A.part_J + total, 0xff, (size_t)B * 8, st);
+        if (P.G * P.G == P.C && W * 128 == P.C && P.G >= 16 && P.G <= 64 &&
+            !(P.dev & (DEV_NO_SLICES | DEV_STEER_SLICES | DEV_NO_BOUND)) && W > 1) {
+            hipError_t e = hipMemsetAsync(A.incumbents, 0xff, (size_t)B * 8, st);
             if (e != hipSuccess) return e;
-            Pr.dev |= DEV_INCUMBENTS;
+            Pr.dev |= DEV_LAUNCH_INCUMBENTS;
         }
     }
     if (search_builds_queues(P, B, A)) {                     // small batches: longest units first
@@ -692,14 +693,14 @@ hipError_t launch_value(const KP& P, int B, const DevNet<T>& net, const SolveArg
 template <>
 hipError_t launch_value<double>(const KP& P, int B, const DevNet<double>& net, const SolveArgs<double>& A,
                                 double* cost_all, uint32_t* viol_all, hipStream_t st) {
-    if (!cost_all && !(P.dev & 1024)) {   // solve path: the compact list of feasible candidates on the f64 matrix cores
+    if (!cost_all && !(P.dev & DEV_EXACT64)) {   // solve path: the compact list of feasible candidates on the f64 matrix cores
         const size_t lds = (size_t)FRAGD_LDS * sizeof(double);
         const int n_units = B * (P.C / 64);
         // prune the list first (value_bound_kernel): scenarios with many feasible candidates -- the tracking and ramp-hold
         // families -- keep a fraction of their entries; short lists (the lattice's 14 per scenario) are left alone
         // value_bound_kernel: scenarios with many feasible candidates -- the tracking and ramp-hold families -- keep a fraction
-        // of their entries; short lists (the lattice's 14 per scenario) are left alone.  IGT_DEV_FLAGS = 131072: no pruning.
-        const int min_entries = (P.dev & 131072) ? 0x7fffffff : 48;
+        // of their entries; short lists (the lattice's 14 per scenario) are left alone.  DEV_NO_PRUNE: no pruning.
+        const int min_entries = (P.dev & DEV_NO_PRUNE) ? 0x7fffffff : 48;
         unsigned* live_count = A.rec_count + 16;          // zeroed with rec_count before the search
         hipLaunchKernelGGL(value_bound_kernel, dim3(B), dim3(64), 0, st, B, P.C / 64, min_entries, net.n_hidden_mats, net, A.unit_seg,
                            A.rec_sN, A.rec_vN, A.rec_J, A.tv_sv, A.enc, A.prune_thr);

@@ -100,7 +100,7 @@ __device__ __forceinline__ int small_div(int x, int d) {
 }
 // whether the steering table of a slice fits LDS with the layout's own G / W columns (then the live-row layouts keep within it)
 __device__ __forceinline__ bool steer_table_fits(const KP& P, int W, int cand) {
-    return (cand == CAND_LATTICE || cand == CAND_RAMP_HOLD) && (P.G / W) * P.N <= STEER_TABLE_MAX_ENTRIES && !(P.dev & 4);
+    return (cand == CAND_LATTICE || cand == CAND_RAMP_HOLD) && (P.G / W) * P.N <= STEER_TABLE_MAX_ENTRIES && !(P.dev & DEV_NO_STEER_TABLE);
 }
 // UNIFORM: the caller's lanes all ask about the same scenario (a search / emit wave): wave-uniform results are moved to scalar
 // registers.  The queue builder asks per lane about DIFFERENT scenarios and must not (round 4: it did, so every lane of a builder
@@ -109,19 +109,19 @@ __device__ __forceinline__ bool steer_table_fits(const KP& P, int W, int cand) {
 template <bool UNIFORM = true>
 __device__ __forceinline__ UnitLayout unit_layout(const KP& P, int W, int cand, unsigned long long mask) {
     UnitLayout L;
-    const bool slices = cand != CAND_TABLE && P.G * P.G == P.C && W * 64 == P.C && P.G % W == 0 && !(P.dev & 1);
+    const bool slices = cand != CAND_TABLE && P.G * P.G == P.C && W * 64 == P.C && P.G % W == 0 && !(P.dev & DEV_NO_SLICES);
     if (!slices) { L.kind = 0; L.per = 64; L.n_units = W; L.R = P.G; L.mask = ~0ull; return L; }
     L.mask = mask & (P.G >= 64 ? ~0ull : ((1ull << P.G) - 1ull));
     L.R = __popcll(L.mask);
     const int nj = 64 / P.G;                                 // = G / W (C = G^2 = 64 W; G is a power of two, igt_api.hip)
-    if (cand == CAND_TRACK && !(P.dev & 262144)) {
+    if (cand == CAND_TRACK && !(P.dev & DEV_STEER_SLICES)) {
         L.kind = 1; L.per = nj;
         L.n_units = (L.R + nj - 1) / nj;                     // nj is a power of two as well
         return L;
     }
     const bool table = steer_table_fits(P, W, cand);
     // 64 live candidates per unit, column by column from the centre outwards: a unit touches at most floor(63 / R) + 2 columns
-    if (L.R > 0 && !(P.dev & 4194304) && (!table || (small_div(63, L.R) + 2) * P.N <= STEER_TABLE_MAX_ENTRIES)) {
+    if (L.R > 0 && !(P.dev & DEV_WHOLE_COLUMNS) && (!table || (small_div(63, L.R) + 2) * P.N <= STEER_TABLE_MAX_ENTRIES)) {
         L.kind = 3; L.per = 0;
         L.n_units = (P.G * L.R + 63) >> 6;
         if (UNIFORM) L.n_units = __builtin_amdgcn_readfirstlane(L.n_units);
@@ -236,10 +236,11 @@ __device__ __forceinline__ void build_queue(const KP& P, int B, int W, int q, co
             frac_out = (arc || P.cand_mode == CAND_TRACK) ? 0.95f : fminf(fmaxf(1.05f - 0.15f * v0, 0.4f), 0.95f);
             weight = arc ? 1.9f : 1.0f;
         }
-        // float64 tracking units (cut along the acceleration axis, highest rows in unit 0): unit-rank-major -- every scenario's
-        // unit 0 before any unit 1 -- so that a later unit of a scenario starts when the earlier ones have left their best cost
-        // as its incumbent (igt_fast64.h BOUND)
-        const bool by_rank = P.cand_mode == CAND_TRACK && (by_rows || (sizeof(T) == 4 && (P.dev & (1 << 30)))) && !(P.dev & 262144);
+        // tracking units (cut along the acceleration axis, highest rows in unit 0): unit-rank-major -- every scenario's unit 0
+        // before any unit 1 -- so that a later unit of a scenario starts when the earlier ones have left their best cost as its
+        // incumbent (igt_fast64.h BOUND; float64: with the live rows, float: with the incumbents, which only its launcher sets)
+        const bool by_rank = P.cand_mode == CAND_TRACK && (by_rows || (sizeof(T) == 4 && (P.dev & DEV_LAUNCH_INCUMBENTS))) &&
+                             !(P.dev & DEV_STEER_SLICES);
         for (int p = 0; p < W; ++p) {
             int c = QC - 1;
             if (p < nu) {
@@ -325,7 +326,7 @@ __device__ __forceinline__ void search_waves(const KP& P, int B, int W, int queu
     // (round 4: 8 items per wave instead of 4 -- at B = 4096 that is every item, i.e. no index is fetched ahead: an item reserved
     // by a wave that is 100 us into an arc unit starts when that unit ends, while waves go idle from 75 % of the span on;
     // profiles/r04_hold_sweep.txt: search 0.228 -> 0.220 ms, one solve at a time 16.1 -> 16.7 M solves/s)
-    const unsigned hold = ((P.dev >> 12) & 15u ? (P.dev >> 12) & 15u : 8u) * (gridDim.x / (unsigned)queues + 1u);
+    const unsigned hold = (dev_late_items(P.dev) ? dev_late_items(P.dev) : 8u) * (gridDim.x / (unsigned)queues + 1u);
     const unsigned late_from = K > hold ? K - hold : 0u;
     // own queue first, then the other XCDs' queues in turn (the XCDs are not equally fast: one of the eight took 10 %
     // longer over the same work in every trace).  Item k of a queue is scenario ordinal j and slice p, through the
@@ -336,7 +337,7 @@ __device__ __forceinline__ void search_waves(const KP& P, int B, int W, int queu
     // four items per wave of the queue, and when stealing, the index is fetched only when the wave is ready for it.
     for (unsigned d = 0; d < (unsigned)queues; ++d) {
         const unsigned qq = (q + d) % (unsigned)queues;
-        if (d > 0 && (P.dev & 512)) break;    // developer switch: no stealing
+        if (d > 0 && (P.dev & DEV_NO_STEAL)) break;    // developer switch: no stealing
         unsigned* counter = work_counter + qq * 64u;
         const unsigned* ord = order ? order + (size_t)qq * order_stride : nullptr;
         unsigned k = 0, item = 0;
@@ -357,12 +358,11 @@ __device__ __forceinline__ void search_waves(const KP& P, int B, int W, int queu
             if (ord) { j = item >> 8; p = item & 255u; }
             else if (p_major) { p = k / n_scen; j = k - p * n_scen; }
             else { j = k / uW; p = k - j * uW; }
-            const unsigned long long t0 = (P.dev & 256) ? wall_clock64() : 0ull;
+            const unsigned long long t0 = (P.dev & DEV_TRACE) ? wall_clock64() : 0ull;
             const int b = queue_scenario((int)qq, (int)j);
             if (b < B) unit(b, (int)p);
-            if ((P.dev & 256) && lane0) {      // developer trace (IGT_DEV_TRACE): when each unit ran, and where
-                unsigned long long* tr =
-                    reinterpret_cast<unsigned long long*>(work_counter + 1024) + ((size_t)qq * order_stride + k) * 4;
+            if ((P.dev & DEV_TRACE) && lane0) {      // developer trace (IGT_DEV_TRACE): when each unit ran, and where
+                unsigned long long* tr = unit_trace(work_counter) + ((size_t)qq * order_stride + k) * 4;
                 tr[0] = t0; tr[1] = wall_clock64(); tr[2] = blockIdx.x; tr[3] = ((unsigned long long)j << 8) | p;
             }
             if (!early && lane0) {

@@ -249,37 +249,33 @@ __global__ __launch_bounds__(ROWS_THREADS) void accel_rows_kernel(KP P, int B, c
     const unsigned long long m = __ballot(live);
     if (b < B && i == 0) {
         row_mask[b] = (m >> (lane & ~(P.G - 1))) & (P.G >= 64 ? ~0ull : ((1ull << P.G) - 1ull));
-        row_mask[B + b] = cost_key((double)INFINITY);      // the scenario's incumbent of this pass: none yet (igt_fast64.h BOUND)
+        row_mask[B + b] = cost_key((double)INFINITY);      // the scenario's incumbent of this pass, behind the masks (PartJTail): none yet
     }
 }
 
-// launch-time bit of KP::dev (never taken from IGT_DEV_FLAGS): the masks of accel_rows_kernel sit behind the partials
-constexpr int DEV_LIVE_ROWS = 1 << 30;
-constexpr int DEV_NO_BOUND = 8388608;      // IGT_DEV_FLAGS: no incumbent bound in the tracking family's search (A/B runs, bitwise test)
-__device__ __forceinline__ const unsigned long long* live_rows_of(const KP& P, int B, int W, const double* part_J) {
-    return (P.dev & DEV_LIVE_ROWS) ? reinterpret_cast<const unsigned long long*>(part_J + (size_t)B * W) : nullptr;
+// The search kernels' view of what part_J holds behind the partials (igt_launch.h PartJTail).  DEV_LAUNCH_LIVE_ROWS: the masks
+// of accel_rows_kernel are in use, and with them the incumbents ([B] keys, set to "none" by accel_rows_kernel) and the rows'
+// travel sums ([B G], tracking family).  DEV_LAUNCH_CKPT: the search pass leaves the unit winners' horizon checkpoints
+// ([B W][CK_RECORD] doubles) for emit_seg_f64_kernel.
+__device__ __forceinline__ const unsigned long long* live_rows_of(const KP& P, int B, int W, double* part_J) {
+    return (P.dev & DEV_LAUNCH_LIVE_ROWS) ? PartJTail<double>(part_J, B, W, P.G).masks() : nullptr;
 }
-// the incumbents sit behind the masks: [B] keys, set to "none" by accel_rows_kernel
 template <int CAND, bool VALUE>
 __device__ __forceinline__ unsigned long long* incumbents_of(const KP& P, int B, int W, double* part_J) {
-    return (CAND == CAND_TRACK && !VALUE && (P.dev & DEV_LIVE_ROWS) && !(P.dev & (DEV_NO_BOUND | 262144)))
-               ? reinterpret_cast<unsigned long long*>(part_J + (size_t)B * W) + B : nullptr;
+    return (CAND == CAND_TRACK && !VALUE && (P.dev & DEV_LAUNCH_LIVE_ROWS) && !(P.dev & (DEV_NO_BOUND | DEV_STEER_SLICES)))
+               ? PartJTail<double>(part_J, B, W, P.G).incumbents() : nullptr;
 }
-// launch-time bit of KP::dev: the search pass leaves the unit winners' horizon checkpoints behind the incumbents
-// ([B W][CK_RECORD] doubles) for emit_seg_f64_kernel
-constexpr int DEV_CKPT = 1 << 29;
-constexpr int DEV_NO_SEG_EMIT = 16777216;   // IGT_DEV_FLAGS: emit re-rolls the winner in one piece (A/B runs, bitwise test)
 constexpr int CK_RECORD = (f64::CK_PARTS - 1) * f64::CK_FIELDS;
-// behind the incumbents: the rows' travel sums [B G] (accel_rows_kernel, tracking family), then the checkpoint records
+static_assert(CK_RECORD == CK_RECORD_DOUBLES, "PartJTail sizes the checkpoint records");
 __device__ __forceinline__ double* row_rems_of(const KP& P, int B, int W, double* part_J) {
-    return part_J + (size_t)B * W + 2 * (size_t)B;
+    return PartJTail<double>(part_J, B, W, P.G).row_rems();
 }
 __device__ __forceinline__ double* checkpoints_of(const KP& P, int B, int W, double* part_J) {
-    return (P.dev & DEV_CKPT) ? part_J + (size_t)B * W + 2 * (size_t)B + (size_t)B * P.G : nullptr;
+    return (P.dev & DEV_LAUNCH_CKPT) ? PartJTail<double>(part_J, B, W, P.G).ck_records() : nullptr;
 }
 // queue items in unit-rank-major order when the tracking family's incumbents are in use and no order table was built
 __device__ __forceinline__ bool rank_major_items(const KP& P, int cand, bool value) {
-    return cand == CAND_TRACK && !value && (P.dev & DEV_LIVE_ROWS) && !(P.dev & (DEV_NO_BOUND | 262144));
+    return cand == CAND_TRACK && !value && (P.dev & DEV_LAUNCH_LIVE_ROWS) && !(P.dev & (DEV_NO_BOUND | DEV_STEER_SLICES));
 }
 
 #define IGT_SEARCH64_ARGS                                                                                            \
@@ -345,7 +341,7 @@ __device__ __forceinline__ void search_unit64(const KP& P, int W, int b, int p, 
     // LDS once per unit instead of being recomputed by each of their 64 W/G lanes at every step (igt_fast64.h)
     // 70 % of the benchmark's scenarios: the other vehicle is out of reach over the whole horizon (or filter_preds moved it
     // away), so the unit rolls without the Cartesian rows -- a sixth of the control step's instructions
-    const bool far = !(P.dev & 65536) && obstacles_out_of_reach<double>(P, S, lane);
+    const bool far = !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
     // horizon checkpoints of every lane in LDS (igt_fast64.h SEGMODE 1); the unit winner's go to HBM below
     constexpr int SM = VALUE ? 0 : 1;
     constexpr int CKF = CAND == CAND_TRACK ? 8 : 5;
@@ -775,26 +771,27 @@ static hipError_t launch_search_exact(const KP& P, int B, const SolveArgs<double
 #endif
 bool search_builds_queues(const KP& P, int B, const SolveArgs<double>& A) {
     const int W = P.C / 64;
-    return A.queue_order && W <= 256 && ((B + 7) / 8) * W <= QB_THREADS * QB_TRIPS && !(P.dev & 16) && !(P.dev & (1024 | 2048));
+    return A.queue_order && W <= 256 && ((B + 7) / 8) * W <= QB_THREADS * QB_TRIPS && !(P.dev & DEV_NO_QUEUE_ORDER) &&
+           !(P.dev & (DEV_EXACT64 | DEV_LITERAL));
 }
 
 // Small batches keep the trajectories of the search pass (CaptureSink) when the kernel built for the reference's
-// discretisation runs; IGT_DEV_FLAGS = 524288 switches it off for A/B runs.
+// discretisation runs; DEV_NO_CAPTURE switches it off for A/B runs.
 static bool captures_trajectories(const KP& P, const SolveArgs<double>& A) {
-    return A.traj && !P.hi_order && P.n_rk4 == 4 && !(P.dev & (32 | 1024 | 2048 | 524288));
+    return A.traj && !P.hi_order && P.n_rk4 == 4 && !(P.dev & (DEV_WAVES3 | DEV_EXACT64 | DEV_LITERAL | DEV_NO_CAPTURE));
 }
 
 // ... and such a batch has no more units than the chip has SIMDs (the kernel that keeps trajectories holds one wave per
 // SIMD), so every unit is given its own wave: the queue builder (6.6 us and a launch) would only order units that all start
 // at once.  Measured, search + emit, tracking family: 67 us against 84 at B = 1, 91 against 101 at B = 32.
-// IGT_DEV_FLAGS = 1048576 keeps the queues for A/B runs; the unit trace (256) needs them.
+// DEV_KEEP_QUEUES keeps the queues for A/B runs; the unit trace (DEV_TRACE) needs them.
 bool search_is_static(const KP& P, int B, const SolveArgs<double>& A) {
-    return captures_trajectories(P, A) && (size_t)B * (P.C / 64) <= (size_t)A.n_cu * 4 && !(P.dev & (256 | 1048576));
+    return captures_trajectories(P, A) && (size_t)B * (P.C / 64) <= (size_t)A.n_cu * 4 && !(P.dev & (DEV_TRACE | DEV_KEEP_QUEUES));
 }
 
 // Whether emit rolls the winner in four pieces from the search pass's checkpoints (emit_seg_f64_kernel): progress cost (with the
 // value network the winner is only known after the network has run), batches that do not keep trajectories, horizons of at
-// least 8 steps, workspace sized for the records (A.ck_ok).  The search launcher and the emit launcher both ask this.
+// least 8 steps, workspace taken for the records (A.ck_records).  The search launcher and the emit launcher both ask this.
 // scenarios per workgroup: a full wave's 64 when their staging fits a compute unit's LDS (116 KB at N = 20; 160 KB per CU,
 // the kernel asks for more than the default 64 KB: seg_lds_opt_in), else the largest power of two that does
 constexpr size_t SEG_LDS_MAX = 150 * 1024;
@@ -812,8 +809,8 @@ static hipError_t seg_lds_opt_in(K kernel) {      // once per instantiation and 
 // 64-thread wave without LDS does, a 320-thread workgroup with 116 KB of LDS waits for a compute unit to drain (measured on one
 // box, three runs each: 20.3 against 20.9 M solves/s with four solves in flight).
 static bool emits_in_pieces(const KP& P, const SolveArgs<double>& A) {
-    return A.ck_ok && P.cost_mode == 0 && P.N >= 8 && !captures_trajectories(P, A) && seg_scenarios_per_block(P) >= 4 &&
-           A.waves_per_simd != 1 && !(P.dev & (32 | 1024 | 2048 | DEV_NO_SEG_EMIT));
+    return A.ck_records && P.cost_mode == 0 && P.N >= 8 && !captures_trajectories(P, A) && seg_scenarios_per_block(P) >= 4 &&
+           A.waves_per_simd != 1 && !(P.dev & (DEV_WAVES3 | DEV_EXACT64 | DEV_LITERAL | DEV_NO_SEG_EMIT));
 }
 
 // Whether the search runs on units made of live acceleration rows only (accel_rows_kernel; unit_layout).  Only for batches of
@@ -822,7 +819,7 @@ static bool emits_in_pieces(const KP& P, const SolveArgs<double>& A) {
 static bool packs_live_rows(const KP& P, int B, const SolveArgs<double>& A) {
     const int W = P.C / 64;
     return A.row_mask && P.cand_mode != CAND_TABLE && P.G <= 64 && P.G * P.G == P.C && W * 64 == P.C && P.G % W == 0 &&
-           !(P.dev & (1 | 1024 | 2048 | 2097152)) && !captures_trajectories(P, A) && (size_t)B * W > (size_t)A.n_cu * 16;
+           !(P.dev & (DEV_NO_SLICES | DEV_EXACT64 | DEV_LITERAL | DEV_ALL_ROWS)) && !captures_trajectories(P, A) && (size_t)B * W > (size_t)A.n_cu * 16;
 }
 
 // float64 search: persistent waves on the per-XCD queues, one 64-candidate unit at a time
@@ -830,7 +827,7 @@ template <int CAND, bool HI, bool VALUE>
 static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A, hipStream_t st) {
     const int W = P.C / 64;
 #if IGT_DEV_KERNELS
-    if ((P.dev & 2048) && !VALUE && P.N <= LIT_MAX_N) {       // measurement variant: the literal wave-per-trajectory mapping
+    if ((P.dev & DEV_LITERAL) && !VALUE && P.N <= LIT_MAX_N) {       // measurement variant: the literal wave-per-trajectory mapping
         hipLaunchKernelGGL((search_literal_f64_kernel<CAND, HI>), dim3(B), dim3(64 * LIT_WAVES), 0, st, P, B, W, A.x0, A.u_prev,
                            A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c);
         return hipGetLastError();
@@ -838,8 +835,8 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
 #endif
     const size_t total = (size_t)B * W;
     // 2 waves per SIMD (232 VGPRs, no spill); the 3-per-SIMD build spills 244 B/lane and is 3-8 % behind at every batch
-    // size (IGT_DEV_FLAGS = 32 selects it for A/B runs)
-    const bool o3 = IGT_DEV_KERNELS && (P.dev & 32) != 0;
+    // size (DEV_WAVES3 selects it for A/B runs)
+    const bool o3 = IGT_DEV_KERNELS && (P.dev & DEV_WAVES3) != 0;
     const size_t slots = (size_t)A.n_cu * 4 * (o3 ? 3 : (A.waves_per_simd == 1 ? 1 : 2));
     const size_t grid = total < slots ? total : slots;
     const unsigned* order = nullptr;
@@ -850,27 +847,27 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
                            A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b, A.unit_seg, A.traj);
         return hipGetLastError();
     }
-    // the live-row masks live behind the partials (part_J[B W ..]): no further kernel argument -- the search kernels spill
-    // scalar registers as it is, and every one more shows up as v_readlane in the control-step loop
+    // the live-row masks and the checkpoint records live behind the partials (PartJTail): no further kernel argument -- the
+    // search kernels spill scalar registers as it is, and every one more shows up as v_readlane in the control-step loop
     KP Pr = P;
-    if (!VALUE && emits_in_pieces(P, A)) Pr.dev |= DEV_CKPT;
+    if (!VALUE && emits_in_pieces(P, A)) Pr.dev |= DEV_LAUNCH_CKPT;
     const unsigned long long* rows = nullptr;
     bool queues_built = false;
     if constexpr (CAND != CAND_TABLE) {
         if (packs_live_rows(P, B, A)) {
-            rows = reinterpret_cast<const unsigned long long*>(A.part_J + (size_t)B * W);
+            rows = A.row_mask;
             const int per_block = (ROWS_THREADS / 64) * (64 / P.G);    // scenarios per workgroup
             const int n_groups = (B + per_block - 1) / per_block;
             // small batches: the same launch sorts the queues (longest units first)
-            queues_built = search_builds_queues(P, B, A) && !(P.dev & 33554432);
+            queues_built = search_builds_queues(P, B, A) && !(P.dev & DEV_SEPARATE_QUEUES);
 #define IGT_LAUNCH_ROWS(QUEUES_)                                                                                              \
             hipLaunchKernelGGL((accel_rows_kernel<CAND, QUEUES_>), dim3(n_groups + (QUEUES_ ? 8 : 0)), dim3(ROWS_THREADS), 0, st, P, \
-                               B, A.x0, A.u_prev, A.flags, A.cinf, A.centre(), const_cast<unsigned long long*>(rows),        \
-                               A.part_J + (size_t)B * W + 2 * (size_t)B, W, A.kparams, A.queue_order, order_stride,           \
+                               B, A.x0, A.u_prev, A.flags, A.cinf, A.centre(), A.row_mask, A.row_rems,        \
+                               W, A.kparams, A.queue_order, order_stride,           \
                                A.work_counter)
             if (queues_built) { IGT_LAUNCH_ROWS(true); order = A.queue_order; } else IGT_LAUNCH_ROWS(false);
 #undef IGT_LAUNCH_ROWS
-            Pr.dev |= DEV_LIVE_ROWS;
+            Pr.dev |= DEV_LAUNCH_LIVE_ROWS;
         }
     }
     if (!queues_built && search_builds_queues(P, B, A)) {    // small batches: longest units first
@@ -911,7 +908,7 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
 template <bool VALUE>
 static hipError_t dispatch_search64(const KP& P, int B, const SolveArgs<double>& A, hipStream_t st) {
 #if IGT_DEV_KERNELS
-    if (P.dev & 1024) return launch_search_exact<VALUE>(P, B, A, st);     // developer switch: oracle-order kernels
+    if (P.dev & DEV_EXACT64) return launch_search_exact<VALUE>(P, B, A, st);     // developer switch: oracle-order kernels
 #endif
     if (P.hi_order) {
         if (P.cand_mode == CAND_LATTICE) return launch_search64<CAND_LATTICE, true, VALUE>(P, B, A, st);
@@ -944,14 +941,13 @@ static hipError_t launch_emit64(const KP& P, int B, int W, const SolveArgs<doubl
     if (emits_in_pieces(P, A)) {
         const int S = seg_scenarios_per_block(P);
         const size_t lds = (size_t)S * seg_doubles_per_scenario(P.N) * 8;
-        double* ck = A.part_J + (size_t)B * W + 2 * (size_t)B + (size_t)B * P.G;
         if (NRK4 == 4 && P.n_rk4 == 4)
             hipLaunchKernelGGL((emit_seg_f64_kernel<CAND, HI, NRK4>), dim3((B + S - 1) / S), dim3(SEG_THREADS), lds, st, P, B, W, S, A.x0, A.u_prev,
-                               A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, ck, A.cost_out, A.argmin_out,
+                               A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.ck_records, A.cost_out, A.argmin_out,
                                A.status_out, A.x_out, A.u_out);
         else
             hipLaunchKernelGGL((emit_seg_f64_kernel<CAND, HI, 0>), dim3((B + S - 1) / S), dim3(SEG_THREADS), lds, st, P, B, W, S, A.x0, A.u_prev,
-                               A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, ck, A.cost_out, A.argmin_out,
+                               A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.ck_records, A.cost_out, A.argmin_out,
                                A.status_out, A.x_out, A.u_out);
         return hipGetLastError();
     }
@@ -985,7 +981,7 @@ hipError_t prepare_emit_kernels() {
 template <>
 hipError_t launch_emit<double>(const KP& P, int B, int W, const SolveArgs<double>& A, hipStream_t st) {
 #if IGT_DEV_KERNELS
-    if (P.dev & 1024) {     // developer switch: oracle-order kernels (argmin_out is already final there)
+    if (P.dev & DEV_EXACT64) {     // developer switch: oracle-order kernels (argmin_out is already final there)
         hipLaunchKernelGGL((emit_kernel<ExactStepper<double>, double>), dim3((B + 63) / 64), dim3(64), 0, st, P, B, A.x0,
                            A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.argmin_out, A.x_out, A.u_out);
         return hipGetLastError();
@@ -1015,7 +1011,7 @@ template <>
 hipError_t launch_rollout_all<double>(const KP& P, int B, const SolveArgs<double>& A, double* X_all, double* U_all,
                                       double* cost_all, uint32_t* viol_all, hipStream_t st) {
 #if IGT_DEV_KERNELS
-    if (P.dev & 1024) {     // developer switch: oracle-order kernels
+    if (P.dev & DEV_EXACT64) {     // developer switch: oracle-order kernels
         hipLaunchKernelGGL((rollout_all_kernel<ExactStepper<double>, double>), dim3((B + 3) / 4), dim3(256), 0, st, P, B,
                            A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), X_all, U_all, cost_all, viol_all,
                            A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol);

@@ -39,7 +39,7 @@ struct SolveArgs {   // all device pointers
     uint32_t* rec_viol;    // [B, C]
     T* p_vec;              // [B, 128] first-layer offsets
     // float path: feasible candidates appended by the search pass (count, scenario, candidate in rec_viol's storage)
-    unsigned* work_counter;         // search_fast_kernel's 8 unit counters, 256 B apart (zeroed before every launch)
+    unsigned* work_counter;         // the search's 8 unit counters, 256 B apart (zeroed before every launch); unit_trace behind them
     int n_cu;                       // compute units (sizes the persistent search grid)
     int waves_per_simd;             // of the persistent search grid: 2, or 1 when solves overlap (igt_set_concurrency); 0 = 2
     double* ckpt;                   // [ck_parts-1][B*Wk] horizon checkpoints of the search pass for emit (null: none)
@@ -51,11 +51,44 @@ struct SolveArgs {   // all device pointers
     int2* unit_seg;                 // double path: [B, C/64] (first entry, count) of each unit's entries in the compact list
     double* prune_thr;              // double path: [B] cost above which an entry cannot win (value_bound_kernel)
     unsigned* live_idx;             // double path: entries left for the network after value_prune_kernel
-    unsigned long long* row_mask;   // double path: [B] live acceleration rows of the generated families (accel_rows_kernel)
     double* traj;                   // double path, small batches: [B C/64][9][N+1][64] kept by the search pass (null: none)
-    bool ck_ok;                     // double path: part_J is followed by [B] masks, [B] incumbents, [B G] row travel sums and [B C/64][24] checkpoint records
+    // in part_J behind the partials (PartJTail)
+    unsigned long long* row_mask;   // double path: [B] live acceleration rows of the generated families (accel_rows_kernel)
+    unsigned long long* incumbents; // [B] the tracking family's best cost keys of the pass (igt_fast64.h BOUND)
+    double* row_rems;               // double path: [B G] the acceleration rows' travel sums (accel_rows_kernel)
+    double* ck_records;             // double path: [B W][CK_RECORD_DOUBLES] unit winners' checkpoints for emit (null: none)
 };
 constexpr int CK_RECORD_DOUBLES = 24;   // igt_fast64.h (CK_PARTS - 1) * CK_FIELDS
+
+// What part_J holds behind its [B, W] partials:
+//   double path: [B] live-row masks, [B] incumbents, [B G] row travel sums, [B W][CK_RECORD_DOUBLES] checkpoint records
+//                (the records only where the host takes them: doubles(true));
+//   float path:  [B] incumbents.
+// The host takes part_J at doubles() and names the pieces in SolveArgs; the search kernels find them from part_J through the
+// same declaration, because their argument lists must not grow (launch_search64) -- launch-time bits of KP::dev say which are
+// in use.
+template <typename T>
+struct PartJTail {
+    double* part_J;
+    size_t B, W, G;
+    __host__ __device__ PartJTail(double* part_J_, int B_, int W_, int G_)
+        : part_J(part_J_), B((size_t)B_), W((size_t)W_), G((size_t)G_) {}
+    __host__ __device__ size_t doubles(bool ck) const {
+        return sizeof(T) == 8 ? B * W + 2 * B + B * G + (ck ? B * W * CK_RECORD_DOUBLES : 0) : B * W + B;
+    }
+    __host__ __device__ unsigned long long* masks() const { return reinterpret_cast<unsigned long long*>(part_J + B * W); }
+    __host__ __device__ unsigned long long* incumbents() const {
+        return reinterpret_cast<unsigned long long*>(part_J + B * W) + (sizeof(T) == 8 ? B : 0);
+    }
+    __host__ __device__ double* row_rems() const { return part_J + B * W + 2 * B; }
+    __host__ __device__ double* ck_records() const { return part_J + B * W + 2 * B + B * G; }
+};
+
+// work_counter is followed by the developer unit trace (DEV_TRACE): u64[queue items][4]
+constexpr size_t WORK_COUNTER_WORDS = 1024;
+__host__ __device__ inline unsigned long long* unit_trace(unsigned* work_counter) {
+    return reinterpret_cast<unsigned long long*>(work_counter + WORK_COUNTER_WORDS);
+}
 
 bool search_builds_queues(const KP& P, int B, const SolveArgs<float>& A);   // then no memset of the counters is needed
 bool search_builds_queues(const KP& P, int B, const SolveArgs<double>& A);

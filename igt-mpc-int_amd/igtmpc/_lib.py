@@ -74,7 +74,28 @@ SYMBOLS = {
 }
 
 _libs = {}
-DEV_KERNEL_FLAGS = 32 | 1024 | 2048      # csrc/igt_device.h IGT_DEV_KERNEL_FLAGS
+# IGT_DEV_FLAGS bits (csrc/igt_device.h DevFlag; the launch-time bits there are the library's own and not listed here)
+DEV_NO_SLICES = 1
+DEV_NO_EARLY_EXIT = 2
+DEV_NO_STEER_TABLE = 4
+DEV_NO_QUEUE_ORDER = 16
+DEV_WAVES3 = 32
+DEV_TRACE = 256
+DEV_NO_STEAL = 512
+DEV_EXACT64 = 1024
+DEV_LITERAL = 2048
+DEV_LATE_ITEMS = 15 << 12
+DEV_NO_FAR = 65536
+DEV_NO_PRUNE = 131072
+DEV_STEER_SLICES = 262144
+DEV_NO_CAPTURE = 524288
+DEV_KEEP_QUEUES = 1048576
+DEV_ALL_ROWS = 2097152
+DEV_WHOLE_COLUMNS = 4194304
+DEV_NO_BOUND = 8388608
+DEV_NO_SEG_EMIT = 16777216
+DEV_SEPARATE_QUEUES = 33554432
+DEV_KERNEL_FLAGS = DEV_WAVES3 | DEV_EXACT64 | DEV_LITERAL      # the kernels only libigtmpc_dev.so carries
 LIB_PATH_DEV = os.path.join(os.path.dirname(LIB_PATH), 'libigtmpc_dev.so')
 
 

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import np_oracle as O
+from igtmpc._lib import DEV_ALL_ROWS, DEV_NO_BOUND, DEV_NO_EARLY_EXIT, DEV_NO_FAR, DEV_NO_PRUNE
 from helpers import F32_EPS, F32_TIE, REL_TOL, ambiguous_mask, oracle_params, rel_err, verdict_margins
 
 LIMITS = {
@@ -27,10 +28,10 @@ LIMITS = {
     'track_vcap': (1.0, 0.0),
     'track_env': (1.0, 0.0, 0.5),
 }
-# every pruning switch the shipped library honours: no early exit (2), no Cartesian row skip (65536), all acceleration rows
-# (2097152), no incumbent bound (8388608); under the value-network cost also no value-bound pruning (131072)
-PRUNE_OFF = 2 | 65536 | 2097152 | 8388608
-PRUNE_OFF_NET = PRUNE_OFF | 131072
+# every pruning switch the shipped library honours: no early exit, no Cartesian row skip, all acceleration rows, no incumbent
+# bound; under the value-network cost also no value-bound pruning
+PRUNE_OFF = DEV_NO_EARLY_EXIT | DEV_NO_FAR | DEV_ALL_ROWS | DEV_NO_BOUND
+PRUNE_OFF_NET = PRUNE_OFF | DEV_NO_PRUNE
 
 N_SEEDS = 32
 F32_SEEDS = range(0, N_SEEDS, 3)

@@ -16,6 +16,9 @@ import numpy as np
 import pytest
 
 import np_oracle as O
+from igtmpc._lib import (DEV_ALL_ROWS, DEV_EXACT64, DEV_KEEP_QUEUES, DEV_NO_BOUND, DEV_NO_CAPTURE, DEV_NO_EARLY_EXIT, DEV_NO_FAR,
+                         DEV_NO_PRUNE, DEV_NO_QUEUE_ORDER, DEV_NO_SEG_EMIT, DEV_NO_SLICES, DEV_NO_STEAL, DEV_NO_STEER_TABLE,
+                         DEV_SEPARATE_QUEUES, DEV_STEER_SLICES, DEV_WAVES3, DEV_WHOLE_COLUMNS)
 from helpers import F32_EPS, F32_TIE, REL_TOL, ambiguous_mask, oracle_params, oracle_solve, rel_err, verdict_margins
 
 pytestmark = pytest.mark.gpu
@@ -149,7 +152,7 @@ def test_search_and_emit_agree_bitwise(igt, B, cand_mode, dtype):
 
 def test_f64_production_kernels_agree_with_oracle_order_kernels(igt, monkeypatch):
     """The float64 entry runs the factorised double arithmetic of igt_fast64.h on persistent waves; the kernels that
-    follow the oracle operation for operation (ExactStepper<double>) stay in the library behind IGT_DEV_FLAGS=1024.
+    follow the oracle operation for operation (ExactStepper<double>) stay in the library behind DEV_EXACT64.
     At BASELINE configs[1] size, where the numpy oracle is too slow to cover every scenario, the two must agree:
     same status everywhere, same arg-min except exact near-ties, trajectories and costs to 1e-11."""
     B = 4096
@@ -158,7 +161,7 @@ def test_f64_production_kernels_agree_with_oracle_order_kernels(igt, monkeypatch
         s.set_cinf(*_cinf())
         fast = s.solve(*_args(b))
         allf = s.rollout_all(*[a[:64] for a in _args(b)])
-    monkeypatch.setenv('IGT_DEV_FLAGS', '1024')
+    monkeypatch.setenv('IGT_DEV_FLAGS', str(DEV_EXACT64))
     with igt.BatchSolver(dtype='f64') as s:
         s.set_cinf(*_cinf())
         ref = s.solve(*_args(b))
@@ -323,7 +326,7 @@ def test_bad_arguments_fail_loudly(igt):
 def test_big_batch_and_other_build_equal_small_pieces(igt, golden_dir, monkeypatch, dtype, value_net):
     """The same scenarios solved in one ragged big batch (queues in index order, no longest-first sort), in small pieces
     (sorted queues, other queue make-up), and by the 3-waves-per-SIMD build of the persistent search kernel
-    (IGT_DEV_FLAGS = 32; a spilling build kept for A/B runs) must come out bit for bit the same -- with the progress
+    (DEV_WAVES3; a spilling build kept for A/B runs) must come out bit for bit the same -- with the progress
     cost and with the value network on the compact list (MFMA kernel, atomicMin winner)."""
     B = 24576 + 5                                  # not a multiple of 8: the last block of 8 has holes
     b = _batch(B, np.float32 if dtype == 'f32' else np.float64)
@@ -340,7 +343,7 @@ def test_big_batch_and_other_build_equal_small_pieces(igt, golden_dir, monkeypat
         big = s.solve(*_args(b), *extra)
         cuts = [0, 4096, 8192, 8192 + 1003, 12288, 20000, B]
         parts = [s.solve(*[np.ascontiguousarray(a[lo:hi]) for a in list(_args(b)) + extra]) for lo, hi in zip(cuts[:-1], cuts[1:])]
-    monkeypatch.setenv('IGT_DEV_FLAGS', '32')
+    monkeypatch.setenv('IGT_DEV_FLAGS', str(DEV_WAVES3))
     with igt.BatchSolver(dtype=dtype, **kw) as s3:
         s3.set_cinf(*_cinf())
         if value_net:
@@ -576,7 +579,10 @@ def test_production_kernel_switches_change_nothing(igt, dtype, cand, monkeypatch
     npdt = np.float64 if dtype == 'f64' else np.float32
     b = _batch(1536, npdt)
     outs = {}
-    for flag in (0, 1, 2, 4, 16, 512, 262144, 2097152, 8388608, 16777216, 33554432, 1 | 2 | 4 | 16 | 512, 4 | 2097152):
+    for flag in (0, DEV_NO_SLICES, DEV_NO_EARLY_EXIT, DEV_NO_STEER_TABLE, DEV_NO_QUEUE_ORDER, DEV_NO_STEAL, DEV_STEER_SLICES,
+                 DEV_ALL_ROWS, DEV_NO_BOUND, DEV_NO_SEG_EMIT, DEV_SEPARATE_QUEUES,
+                 DEV_NO_SLICES | DEV_NO_EARLY_EXIT | DEV_NO_STEER_TABLE | DEV_NO_QUEUE_ORDER | DEV_NO_STEAL,
+                 DEV_NO_STEER_TABLE | DEV_ALL_ROWS):
         monkeypatch.setenv('IGT_DEV_FLAGS', str(flag))
         with igt.BatchSolver(dtype=dtype, cand_mode=cand) as s:
             s.set_cinf(*_cinf())
@@ -605,13 +611,13 @@ def test_production_kernel_switches_change_nothing(igt, dtype, cand, monkeypatch
 def test_units_of_live_acceleration_rows_change_nothing(igt, golden_dir, cand, N, C, B, monkeypatch):
     """The f64 search first rolls the G acceleration recurrences of every scenario (accel_rows_kernel) and builds its units from
     the rows that hold the speed box and the terminal set -- a failing row is infeasible in all of its columns, so it cannot
-    win (igt_kernels_f64.hip "Acceleration rows that cannot win").  With IGT_DEV_FLAGS = 2097152 every row is rolled as
+    win (igt_kernels_f64.hip "Acceleration rows that cannot win").  With DEV_ALL_ROWS every row is rolled as
     before: the solve must be the same bit for bit -- with and without the queue builder (B = 8200 has none), at both horizons,
     with 1, 4, 16 and 64 units per scenario, with warm starts and a refinement pass, and under the value-network cost.  (Batches of
     up to two rounds of units -- 1024 scenarios at 256 candidates -- keep the plain layout: every size here is above that.)
     The tracking family's default solve also prunes against the scenario's incumbent (igt_fast64.h BOUND: units of the highest
     acceleration rows first, a later unit's candidates are lost once a lower bound of their cost exceeds the best cost a finished
-    unit has left): with all rows rolled there is no such pass, with IGT_DEV_FLAGS = 8388608 the bound alone is off -- the same
+    unit has left): with all rows rolled there is no such pass, with DEV_NO_BOUND the bound alone is off -- the same
     bits, with the queue order table (B <= 6144) and with unit-rank-major item decoding (B = 8200, 16 500)."""
     b = _batch(B, np.float64, N=N)
     rng = np.random.default_rng(11)
@@ -628,8 +634,8 @@ def test_units_of_live_acceleration_rows_change_nothing(igt, golden_dir, cand, N
         net = dict(layers=_nets(golden_dir)[1], Wn=np.eye(6) + 0.05 * rng.normal(size=(6, 6)), mu_f=np.zeros(6), sigma_t=2.0, mu_t=0.3)
         # live rows, 64 per unit (tracking: + the incumbent bound); all rows; live rows in whole columns; (tracking:) no incumbent bound
         # ... ; the queue builder as a launch of its own (where the batch has one)
-        for flag in ('0', '2097152', '4194304') + (('8388608',) if cand == 'track' else ()) + (('33554432',) if B <= 4500 else ()):
-            monkeypatch.setenv('IGT_DEV_FLAGS', flag)
+        for flag in (0, DEV_ALL_ROWS, DEV_WHOLE_COLUMNS) + ((DEV_NO_BOUND,) if cand == 'track' else ()) + ((DEV_SEPARATE_QUEUES,) if B <= 4500 else ()):
+            monkeypatch.setenv('IGT_DEV_FLAGS', str(flag))
             with igt.BatchSolver(N=N, C=C, dtype='f64', cand_mode=cand, cost_mode=cost_mode,     # (tracking at N = 40: with a refinement
                                  refine_iters=1 if (cand == 'ramp_hold' or (cand == 'track' and N == 40)) else 0) as s:   # pass -- the incumbents restart)
                 s.set_cinf(*_cinf())
@@ -651,7 +657,7 @@ def test_units_of_live_acceleration_rows_change_nothing(igt, golden_dir, cand, N
 def test_emit_in_pieces_is_the_emit_in_one_piece(igt, cand, N, n_rk4, C, B, monkeypatch):
     """Batches that do not keep trajectories emit the winner in four pieces of the horizon, each resumed from a checkpoint the
     search pass left (igt_fast64.h SEGMODE; emit_seg_f64_kernel), the Cartesian rows rolled on their own from the controls, the
-    outputs written as contiguous lines.  With IGT_DEV_FLAGS = 16777216 emit_f64_kernel rolls the winner in one piece as before:
+    outputs written as contiguous lines.  With DEV_NO_SEG_EMIT emit_f64_kernel rolls the winner in one piece as before:
     the same x, u, cost, arg-min, status bit for bit -- every family, horizons that are and are not multiples of four, both
     sub-step builds, the coarse discretisation's long polynomials, warm starts and a refinement pass, 1 to 16 units per
     scenario; and the winner's trajectory is rollout-all's for the same candidate, bit for bit."""
@@ -668,14 +674,14 @@ def test_emit_in_pieces_is_the_emit_in_one_piece(igt, cand, N, n_rk4, C, B, monk
         u_prev = np.ascontiguousarray(prev[:, :, 0])
         flags = flags | np.where(np.arange(B) % 3 != 0, 2, 0).astype(np.uint32)
     outs, alls = [], None
-    for flag in ('0', '16777216'):
-        monkeypatch.setenv('IGT_DEV_FLAGS', flag)
+    for flag in (0, DEV_NO_SEG_EMIT):
+        monkeypatch.setenv('IGT_DEV_FLAGS', str(flag))
         with igt.BatchSolver(N=N, n_rk4=n_rk4, C=C, dtype='f64', cand_mode=cand, refine_iters=1 if cand == 'ramp_hold' else 0) as s:
             s.set_cinf(*_cinf())
             if table is not None:
                 s.set_candidate_table(table)
             outs.append(s.solve(b['x0'], u_prev, b['kparams'], flags, b['obs_xy'], u_ws=u_ws))
-            if flag == '0' and cand != 'ramp_hold':      # (a refinement pass re-centres the candidates: rollout-all rolls the first pass)
+            if flag == 0 and cand != 'ramp_hold':      # (a refinement pass re-centres the candidates: rollout-all rolls the first pass)
                 alls = s.rollout_all(b['x0'][:48], u_prev[:48], b['kparams'][:48], flags[:48], b['obs_xy'][:48], u_ws=None if u_ws is None else u_ws[:48])
     monkeypatch.delenv('IGT_DEV_FLAGS')
     assert (outs[0]['status'] == 0).any() and (outs[0]['status'] == 1).any()
@@ -692,10 +698,10 @@ def test_emit_in_pieces_is_the_emit_in_one_piece(igt, cand, N, n_rk4, C, B, monk
 def test_kept_trajectories_are_the_rerolled_ones(igt, cand, N, monkeypatch):
     """Double batches with no more 64-candidate units than the chip has SIMDs (256 scenarios at 256 candidates): the search
     pass keeps every candidate's trajectory and emit copies the winner's (igt_kernels_common.h CaptureSink,
-    emit_gather_f64_kernel) instead of rolling it again.  With the capture switched off (IGT_DEV_FLAGS = 524288:
+    emit_gather_f64_kernel) instead of rolling it again.  With the capture switched off (DEV_NO_CAPTURE:
     emit_f64_kernel re-rolls) the solve is the same bit for bit -- at B = 1, 33 (ragged last block of 8) and 256, for every
     candidate family, at both horizons.  Every unit of such a batch gets a wave of its own instead of a place in the XCDs'
-    queues (search_is_static; IGT_DEV_FLAGS = 1048576 keeps the queues): same bits again."""
+    queues (search_is_static; DEV_KEEP_QUEUES keeps the queues): same bits again."""
     rng = np.random.default_rng(5)
     table = None
     if cand == 'table':
@@ -706,8 +712,8 @@ def test_kept_trajectories_are_the_rerolled_ones(igt, cand, N, monkeypatch):
     for B in (1, 33, 256):
         b = {k: np.ascontiguousarray(v[:B]) for k, v in full.items()}
         outs = []
-        for flag in ('0', '524288', '1048576'):      # default; re-rolled by emit; kept, but with the unit queues
-            monkeypatch.setenv('IGT_DEV_FLAGS', flag)
+        for flag in (0, DEV_NO_CAPTURE, DEV_KEEP_QUEUES):      # default; re-rolled by emit; kept, but with the unit queues
+            monkeypatch.setenv('IGT_DEV_FLAGS', str(flag))
             with igt.BatchSolver(N=N, dtype='f64', cand_mode=cand) as s:
                 s.set_cinf(*_cinf())
                 if table is not None:
@@ -728,8 +734,8 @@ def test_kept_trajectories_with_value_net_and_refinement(igt, golden_dir, cost_m
     b = _batch(200, np.float64)
     cand = 'track' if cost_mode == 'value_net' else 'ramp_hold'
     outs = []
-    for flag in ('0', '524288'):
-        monkeypatch.setenv('IGT_DEV_FLAGS', flag)
+    for flag in (0, DEV_NO_CAPTURE):
+        monkeypatch.setenv('IGT_DEV_FLAGS', str(flag))
         with igt.BatchSolver(dtype='f64', cost_mode=cost_mode, cand_mode=cand, refine_iters=refine) as s:
             s.set_cinf(*_cinf())
             if cost_mode == 'value_net':
@@ -746,7 +752,7 @@ def test_kept_trajectories_with_value_net_and_refinement(igt, golden_dir, cost_m
 @pytest.mark.parametrize('dtype,cand', [('f64', 'lattice'), ('f64', 'track'), ('f32', 'lattice'), ('f32', 'ramp_hold')])
 def test_cartesian_row_skip_changes_nothing(igt, dtype, cand, monkeypatch):
     """Search units whose obstacles are out of every speed-feasible candidate's reach roll without x, y (igt_device.h
-    obstacles_out_of_reach; 70 % of the benchmark batch).  The switched-off build path (IGT_DEV_FLAGS = 65536) must give the
+    obstacles_out_of_reach; 70 % of the benchmark batch).  The switched-off build path (DEV_NO_FAR) must give the
     same solve bit for bit -- on the benchmark batch, on a batch whose obstacle sits just inside / just outside the reach
     bound, with two obstacles of which one is near, and with three and four (IGT_MAX_OBS)."""
     npdt = np.float64 if dtype == 'f64' else np.float32
@@ -769,8 +775,8 @@ def test_cartesian_row_skip_changes_nothing(igt, dtype, cand, monkeypatch):
         many[n]['obs_xy'] = np.ascontiguousarray(np.concatenate([b['obs_xy'][:256]] + extra, axis=1))
     for batch, n_obs in ((b, 1), (edge, 1), (two, 2), (many[3], 3), (many[4], 4)):
         outs = []
-        for flag in ('0', '65536'):
-            monkeypatch.setenv('IGT_DEV_FLAGS', flag)
+        for flag in (0, DEV_NO_FAR):
+            monkeypatch.setenv('IGT_DEV_FLAGS', str(flag))
             with igt.BatchSolver(dtype=dtype, cand_mode=cand, n_obs=n_obs) as s:
                 s.set_cinf(*_cinf())
                 outs.append(s.solve(*_args(batch)))
@@ -784,7 +790,7 @@ def test_cartesian_row_skip_changes_nothing(igt, dtype, cand, monkeypatch):
 def test_value_bound_pruning_changes_nothing(igt, golden_dir, sc, monkeypatch):
     """gt_mpc cost, tracking candidates (long lists of feasible candidates): the list is pruned with an interval bound on
     the value network before the matrix-core kernel runs (value_bound_kernel / value_prune_kernel).  Entries that are dropped
-    cannot win, so the solve with pruning == the solve without (IGT_DEV_FLAGS = 131072), bit for bit -- with a non-trivial
+    cannot win, so the solve with pruning == the solve without (DEV_NO_PRUNE), bit for bit -- with a non-trivial
     whitening and a NEGATIVE sigma_t as well (the bound takes the upper end whatever the sign)."""
     layers = _nets(golden_dir)[sc]
     rng = np.random.default_rng(9)
@@ -794,8 +800,8 @@ def test_value_bound_pruning_changes_nothing(igt, golden_dir, sc, monkeypatch):
     b = _batch(768, np.float64)
     for net in nets:
         outs = []
-        for flag in ('0', '131072'):
-            monkeypatch.setenv('IGT_DEV_FLAGS', flag)
+        for flag in (0, DEV_NO_PRUNE):
+            monkeypatch.setenv('IGT_DEV_FLAGS', str(flag))
             with igt.BatchSolver(dtype='f64', cost_mode='value_net', cand_mode='track') as s:
                 s.set_cinf(*_cinf())
                 s.set_value_net(**net)

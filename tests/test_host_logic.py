@@ -159,6 +159,30 @@ def test_c_abi_exports_every_declared_symbol():
     assert flat == [f[0] for f in L.igt_params._fields_]
 
 
+def test_dev_flag_names_mirror_the_header():
+    """igtmpc._lib names the IGT_DEV_FLAGS bits as csrc/igt_device.h's DevFlag does, with the same values; the launch-time
+    bits (DEV_LAUNCH_*) are the library's own, lie above every bit the environment may set and are not mirrored."""
+    from igtmpc import _lib as L
+    hdr = open(os.path.join(ROOT, 'igt-mpc-int_amd', 'csrc', 'igt_device.h')).read()
+    body = re.search(r'enum DevFlag : int \{(.*?)\};', hdr, re.S).group(1)
+    declared = {}
+    for name, expr in re.findall(r'\b(DEV_\w+)\s*=\s*([0-9<| ]+),', body):
+        val = 0
+        for term in expr.split('|'):
+            a, _, b = term.partition('<<')
+            val |= int(a) << int(b or 0)
+        declared[name] = val
+    launch = {n: v for n, v in declared.items() if n.startswith('DEV_LAUNCH_')}
+    user = {n: v for n, v in declared.items() if n not in launch}
+    assert len(user) >= 20 and len(launch) == 3
+    mirrored = {n: getattr(L, n) for n in dir(L) if n.startswith('DEV_') and n != 'DEV_KERNEL_FLAGS'}
+    assert mirrored == user, set(mirrored.items()) ^ set(user.items())
+    assert L.DEV_KERNEL_FLAGS == L.DEV_WAVES3 | L.DEV_EXACT64 | L.DEV_LITERAL
+    assert len(set(declared.values())) == len(declared)                   # no bit means two things
+    env_mask = min(launch.values()) - 1                                   # igt_device.h DEV_ENV_MASK
+    assert all(v & env_mask == v for v in user.values()) and not any(v & env_mask for v in launch.values())
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     """No CPU fallback: without libigtmpc.so the product raises ImportError naming the build command."""
     from igtmpc import _lib as L
@@ -518,12 +542,12 @@ def test_shipped_library_is_built_without_the_developer_kernels(monkeypatch):
     p = L.igt_params()
     shipped.igt_params_default(ct.byref(p))
     h = ct.c_void_p()
-    for flag in ('32', '1024', '2048', str(1024 | 4)):
-        monkeypatch.setenv('IGT_DEV_FLAGS', flag)
+    for flag in (L.DEV_WAVES3, L.DEV_EXACT64, L.DEV_LITERAL, L.DEV_EXACT64 | L.DEV_NO_STEER_TABLE):
+        monkeypatch.setenv('IGT_DEV_FLAGS', str(flag))
         assert shipped.igt_create(ct.byref(p), 0, ct.byref(h)) == -1      # IGT_E_INVALID
         assert b'libigtmpc_dev.so' in shipped.igt_last_error()
         assert L.wants_dev_kernels() and L.load() is dev
-    monkeypatch.setenv('IGT_DEV_FLAGS', '4')                       # switches of the production kernels stay available
+    monkeypatch.setenv('IGT_DEV_FLAGS', str(L.DEV_NO_STEER_TABLE))   # switches of the production kernels stay available
     assert not L.wants_dev_kernels() and L.load() is shipped
 
 
