@@ -379,6 +379,190 @@ __device__ __forceinline__ void fill_steer_table(const KP& P, const Scenario<dou
 constexpr int CK_FIELDS = 8, CK_PARTS = 4;                      // record: s ey epsi s1 c1 [df sb cb]; pieces of the horizon
 __host__ __device__ inline int ckpt_step(int N, int i) { return (i * N) / CK_PARTS; }      // first step of piece i
 
+// What one lane carries from control step to control step (rollout_one, rollout_pool): the state, the candidate's control
+// recurrence, the running cost and verdicts, the carried (sin, cos) pairs, the checkpoint cursor and the incumbent bound.
+template <class FP>
+struct LaneRoll {
+    double x, y, s, ey, ep, v, psi;
+    double a, df, da, ddf, J, gmax;
+    unsigned viol;
+    typename FP::Work w;
+    double cb_prev, sb_prev;        // (sin, cos)(beta_k-1)
+    double sb, cb, sblr;            // of step k: left by step_head for step_tail
+    double trk_sb, trk_cb;
+    bool trk_followed;
+    int ck_q, ck_k;                 // next checkpoint and its step (search; -1: none)
+    double rem, jcut, seg_scale;
+};
+
+// The body of one control step k, in two pieces around the point where a search wave may leave early (rollout_one) and a
+// pooled lane retires a candidate that failed (rollout_pool): step_head -- checkpoint, controls of step k, slip trigonometry,
+// bookkeeping of state k and its verdicts, the incumbent bound -- returns whether the candidate is lost; step_tail -- the
+// collision check of state k, the rotation of the carried pairs, the sub-steps -- takes the lane to state k + 1.  Every
+// roll-out of the float64 path runs these statements, so whatever runs them gives the same bits.
+// LEAN: |ey|, box v and collision folded into the running maximum gmax (search).  stab: the lane's steering column of the
+// table (entry k at stab[k * stab_stride]).
+template <int CAND, bool BOOK, bool LEAN, bool BOUND, bool STAB, int SEGMODE, class FP, class Sink>
+__device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S, const FP& fp, LaneRoll<FP>& L, int k, int cidx,
+                                          const double* __restrict__ table, const double* __restrict__ cinf, Sink& sink,
+                                          const double* __restrict__ stab, int stab_stride, const unsigned long long* inc,
+                                          double* ck, bool rows_judged, bool kv_d) {
+    constexpr int CKF = CAND == CAND_TRACK ? 8 : 5;            // fields this family writes
+    if (SEGMODE == 1 && k == L.ck_k) {          // node k: what a roll-out needs to resume here
+        double* c = ck + (size_t)(L.ck_q - 1) * CKF * 64;
+        c[0] = L.s; c[64] = L.ey; c[128] = L.ep; c[192] = L.w.s1; c[256] = L.w.c1;
+        if (CAND == CAND_TRACK) { c[320] = L.df; c[384] = L.sb_prev; c[448] = L.cb_prev; }
+        ++L.ck_q;
+        L.ck_k = L.ck_q < CK_PARTS ? ckpt_step(P.N, L.ck_q) : -1;
+    }
+    // ---- controls of step k
+    if (CAND == CAND_LATTICE) {
+        L.a = clampd(L.a + L.da, P.a_min, P.a_max);
+        L.df = STAB ? stab[k * stab_stride] : steer_next<CAND>(P, S, k, L.ddf, L.df);
+    } else if (CAND == CAND_RAMP_HOLD) {
+        double ba, bdf;
+        ramp_base<double>(S.ws, P.N, k, S.a_prev, S.df_prev, ba, bdf);
+        const double ta = clampd(ba + L.da, P.a_min, P.a_max);
+        L.a = clampd(L.a + clampd(ta - L.a, -P.rate_a, P.rate_a), P.a_min, P.a_max);
+        L.df = STAB ? stab[k * stab_stride] : steer_next<CAND>(P, S, k, L.ddf, L.df);
+    } else if (CAND == CAND_TRACK) {
+        double ba, bdf;
+        ramp_base<double>(S.ws, P.N, k, S.a_prev, S.df_prev, ba, bdf);
+        L.a = track_accel_next(P, k, ba, L.da, L.v, L.a);
+        L.df = track_steer(P, L.df, L.ey, L.ep, L.ddf, &L.trk_sb, &L.trk_cb, &L.trk_followed);
+    } else {
+        const double an = table[((size_t)cidx * 2 + 0) * P.N + k];
+        const double dn = table[((size_t)cidx * 2 + 1) * P.N + k];
+        if (BOOK) {   // input-rate (mpc.py:301-312, u_{-1} = u_prev) and input box (mpc.py:318-321)
+            if (fmax(fabs(an - L.a) - P.rate_a, fabs(dn - L.df) - P.rate_df) > P.tol) L.viol |= VIOL_RATE;
+            if (fmax(fmax(P.a_min - an, an - P.a_max), fmax(-P.df_max - dn, dn - P.df_max)) > P.tol) L.viol |= VIOL_BOX_U;
+        }
+        L.a = an; L.df = dn;
+    }
+    sink.ctrl(0, k, L.a, L.df);
+    double sb, cb;                               // (sin, cos)(beta), beta = atan(r tan df)
+    if (STAB && (CAND == CAND_LATTICE || CAND == CAND_RAMP_HOLD)) {
+        sb = stab[k * stab_stride + 1];
+        cb = stab[k * stab_stride + 2];
+    } else if (CAND == CAND_TRACK) {
+        // a lane whose steering followed the command has beta = beta_cmd: its (sin, cos) are known already.  The other
+        // lanes (rate- or box-limited) go through sincos(df); the wave skips that when no lane needs it -- which lane
+        // takes which value does not depend on the vote, so search, emit and rollout-all agree bit for bit
+        sb = L.trk_sb; cb = L.trk_cb;
+        if (!__all(L.trk_followed)) {
+            double sb2, cb2;
+            slip_trig<CAND>(P, fp.lr_ratio, L.df, sb2, cb2);
+            sb = L.trk_followed ? sb : sb2;
+            cb = L.trk_followed ? cb : cb2;
+        }
+    } else {
+        slip_trig<CAND>(P, fp.lr_ratio, L.df, sb, cb);
+    }
+    sink.slip(0, k, sb, cb);
+    L.sb = sb; L.cb = cb;
+    L.sblr = sb * fp.inv_lr;
+    // ---- bookkeeping of state k (cost in the oracle's order: control effort, epsi^2, ey^2 -- mpc.py:361-364)
+    if (BOOK) {
+        L.J = L.J + P.w_u * (L.a * L.a + L.df * L.df);
+        L.J = L.J + L.ep * L.ep;
+        L.J = L.J + L.ey * L.ey;
+        if (LEAN) {
+            L.gmax = fmax(L.gmax, fabs(L.ey) - P.ey_lim);                                  // mpc.py:296-299
+            if (!rows_judged) L.gmax = fmax(L.gmax, fmax(P.v_min - L.v, L.v - P.v_max));   // mpc.py:316-317 (k < N)
+        } else {
+            if (fabs(L.ey) - P.ey_lim > P.tol) L.viol |= VIOL_EY;
+            if (fmax(P.v_min - L.v, L.v - P.v_max) > P.tol) L.viol |= VIOL_BOX_V;
+        }
+        if (k == P.N - 1 && !rows_judged) L.viol |= terminal_viol(P, L.v, L.a, cinf);  // mpc.py:177-180
+    }
+    L.w.ey = L.ey; L.w.v1 = L.v;
+    // unused on straight routes; with one scenario per lane the votes of substeps() read them on every lane
+    // (a straight route's break-points are +inf: d = -inf, "clear")
+    if (kv_d) { L.w.d0 = L.s - fp.b0; L.w.d1 = L.s - fp.b1; }
+    if (BOUND && inc) {
+        // the incumbent is re-read every fourth step (a unit that started before its scenario's first unit finished picks it
+        // up on the way); agent scope: the units of a scenario may run on different XCDs, whose L2s are not coherent
+        if ((k & 3) == 0) {
+            const double ji = cost_of_key(__hip_atomic_load(inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            L.jcut = ji + 1e-9 * (1.0 + fabs(ji));
+        }
+        if ((L.J - (L.s - S.x0[2])) - L.rem > L.jcut) L.viol |= VIOL_PRUNED;
+    }
+    return (L.viol != 0) | (LEAN && L.gmax > P.tol);
+}
+template <bool BOOK, bool LEAN, bool BOUND, bool UNIFORM, bool XY, bool KEEP_PSI, class FP, class Sink>
+__device__ __forceinline__ void step_tail(const KP& P, const Scenario<double>& S, const FP& fp, LaneRoll<FP>& L, int k, Sink& sink,
+                                          const unsigned long long* inc) {
+    if (BOOK && XY && k >= 1) {                                                  // collision, mpc.py:223-226
+        for (int o = 0; o < P.n_obs; ++o) {
+            const double dx = L.x - S.obs[(o * 2 + 0) * (P.N + 1) + k], dy = L.y - S.obs[(o * 2 + 1) * (P.N + 1) + k];
+            const double g = P.dmin2 - (dx * dx + dy * dy);
+            if (LEAN) L.gmax = fmax(L.gmax, g);
+            else if (g > P.tol) L.viol |= VIOL_COLLISION;
+        }
+    }
+    // (sin,cos)(psi + beta_k) from (psi + beta_{k-1}), and (sin,cos)(epsi + beta_k) from (epsi + beta_{k-1}): rotate by
+    // beta_k - beta_{k-1}, re-normalise (first order: the pairs are within rounding of unit length)
+    {
+        const double sb = L.sb, cb = L.cb;
+        const double sdb = fma(sb, L.cb_prev, -(cb * L.sb_prev));
+        const double cdb = fma(cb, L.cb_prev, sb * L.sb_prev);
+        rotate(L.w.s1, L.w.c1, sdb, cdb);
+        const double r1 = fma(fma(L.w.s1, L.w.s1, L.w.c1 * L.w.c1), -0.5, 1.5);
+        L.w.s1 *= r1; L.w.c1 *= r1;
+        if (XY) {
+            rotate(L.w.s2, L.w.c2, sdb, cdb);
+            const double r2 = fma(fma(L.w.s2, L.w.s2, L.w.c2 * L.w.c2), -0.5, 1.5);
+            L.w.s2 *= r2; L.w.c2 *= r2;
+        }
+        L.cb_prev = cb; L.sb_prev = sb;
+    }
+    L.w.acc_s = 0.0; L.w.acc_ey = 0.0; L.w.acc_ep = 0.0; L.w.acc_x = 0.0; L.w.acc_y = 0.0; L.w.acc_psi = 0.0;
+    fp.template substeps<UNIFORM, XY>(L.a, L.sblr, L.w);
+    L.s += L.w.acc_s; L.ey += L.w.acc_ey; L.ep += L.w.acc_ep;
+    if (XY) { L.x += L.w.acc_x; L.y += L.w.acc_y; }
+    if (KEEP_PSI) L.psi += L.w.acc_psi;        // psi feeds nothing back (search: dead code)
+    if (BOUND && inc) L.rem -= L.seg_scale * fmax(fabs(L.v), fabs(fma(fp.dt, L.a, L.v)));      // this step's share of the bound is spent
+    L.v = fma(fp.dt, L.a, L.v);
+    const double nxt[7] = {L.x, L.y, L.s, L.ey, L.ep, L.v, L.psi};
+    sink.state(0, k + 1, nxt);
+}
+// the bookkeeping of state N, after the last control step
+template <bool LEAN, bool XY, class FP>
+__device__ __forceinline__ void horizon_end(const KP& P, const Scenario<double>& S, LaneRoll<FP>& L, double& Jout, unsigned& vout,
+                                            double& sN, double& vN) {
+    L.J = L.J + L.ep * L.ep;
+    L.J = L.J + L.ey * L.ey;
+    if (LEAN) L.gmax = fmax(L.gmax, fabs(L.ey) - P.ey_lim);
+    else if (fabs(L.ey) - P.ey_lim > P.tol) L.viol |= VIOL_EY;
+    for (int o = 0; XY && o < P.n_obs; ++o) {
+        const double dx = L.x - S.obs[(o * 2 + 0) * (P.N + 1) + P.N], dy = L.y - S.obs[(o * 2 + 1) * (P.N + 1) + P.N];
+        const double g = P.dmin2 - (dx * dx + dy * dy);
+        if (LEAN) L.gmax = fmax(L.gmax, g);
+        else if (g > P.tol) L.viol |= VIOL_COLLISION;
+    }
+    if (LEAN && L.gmax > P.tol) L.viol |= VIOL_EY;     // lean form: "some state-side verdict failed"
+    if (!(fabs(L.x) < 1e300 && fabs(L.y) < 1e300 && fabs(L.s) < 1e300 && fabs(L.ey) < 1e300 && fabs(L.ep) < 1e300 &&
+          fabs(L.psi) < 1e300))
+        L.viol |= VIOL_NONFINITE;
+    sN = L.s; vN = L.v; Jout = L.J; vout = L.viol;
+}
+// the control increments of a generated candidate: (da, ddf) of the lattice (oracle candidates_lattice), the
+// target OFFSETS from the base sequence of the ramp-hold and tracking families (igt_device.h cand_m, ramp_base; tracking: ddf is
+// the slip-angle offset of the steering feedback, track_steer)
+template <int CAND>
+__device__ __forceinline__ void cand_increments(const KP& P, const Scenario<double>& S, int cidx, double& da, double& ddf) {
+    if (CAND == CAND_LATTICE) {
+        const int i = cidx / P.G, j = cidx - i * P.G;
+        da = -P.rate_a + (2 * P.rate_a) * (double)i / (double)(P.G - 1);
+        ddf = steer_column<CAND>(P, S, j);
+    } else if (CAND == CAND_RAMP_HOLD || CAND == CAND_TRACK) {
+        const int i = cidx / P.G, j = cidx - i * P.G;
+        da = S.cpar[0] + cand_m(i, P.G, P.refine_it == 0) * S.cpar[2];
+        ddf = S.cpar[1] + cand_m(j, P.G, P.refine_it == 0) * S.cpar[3];
+    }
+}
+
 template <int CAND, bool HI_ORDER, bool BOOK, bool UNIFORM, class Sink, bool EARLY_EXIT = false, bool STAB = false, int NRK = 0,
           bool XY = true, int SEGMODE = 0>
 __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>& S, int cidx,
@@ -392,7 +576,6 @@ __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>&
     // box and the terminal set read the row's (a, v) recurrence alone and were judged there, with these statements -- every lane
     // that holds a candidate holds one of a row that passed: not judged again (74 half-planes per lane at the last step)
     const bool rows_judged = BOOK && EARLY_EXIT && UNIFORM && CAND != CAND_TABLE && (P.dev & DEV_LAUNCH_LIVE_ROWS) != 0;
-    constexpr int CKF = CAND == CAND_TRACK ? 8 : 5;            // fields this family writes
     constexpr bool KEEP_PSI = Sink::kKeepsStates;
     // search only needs feasible-or-not: |ey|, box v and collision are folded into one running maximum, compared with
     // the tolerance when it is read (x > tol for some x  <=>  max x > tol; a NaN operand is ignored by both forms)
@@ -400,233 +583,217 @@ __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>&
     typedef Fast64<HI_ORDER, NRK> FP;
     FP fp;
     fp.init(P, S.b0, S.b1, S.kv);
-    double x = S.x0[0], y = S.x0[1], s = S.x0[2], ey = S.x0[3], ep = S.x0[4], v = S.x0[5], psi = S.x0[6];
-    double a = S.a_prev, df = S.df_prev, da = 0.0, ddf = 0.0, J = 0.0, gmax = -1.0e300;
+    LaneRoll<FP> L;
+    L.x = S.x0[0]; L.y = S.x0[1]; L.s = S.x0[2]; L.ey = S.x0[3]; L.ep = S.x0[4]; L.v = S.x0[5]; L.psi = S.x0[6];
+    L.a = S.a_prev; L.df = S.df_prev; L.da = 0.0; L.ddf = 0.0; L.J = 0.0; L.gmax = -1.0e300;
     // cidx < 0 (search): a lane of the unit that holds no candidate (igt_kernels_f64.hip unit_candidate) -- it rolls candidate 0
     // in step with the wave and is "lost" from the start, so it neither wins nor keeps the unit alive
-    unsigned viol = cidx < 0 ? (unsigned)VIOL_EY : 0u;
+    L.viol = cidx < 0 ? (unsigned)VIOL_EY : 0u;
     if (cidx < 0) cidx = 0;
     bool dead = false;
-    if (CAND == CAND_LATTICE) {
-        // da_i = -ra + (2 ra) i/(G-1), ddf_j likewise (oracle candidates_lattice)
-        const int i = cidx / P.G, j = cidx - i * P.G;
-        da = -P.rate_a + (2 * P.rate_a) * (double)i / (double)(P.G - 1);
-        ddf = steer_column<CAND>(P, S, j);
-    } else if (CAND == CAND_RAMP_HOLD || CAND == CAND_TRACK) {
-        // da / ddf hold the OFFSETS of the targets from the base sequence here (igt_device.h cand_m, ramp_base);
-        // CAND_TRACK: ddf is the slip-angle offset of the steering feedback (track_steer)
-        const int i = cidx / P.G, j = cidx - i * P.G;
-        da = S.cpar[0] + cand_m(i, P.G, P.refine_it == 0) * S.cpar[2];
-        ddf = S.cpar[1] + cand_m(j, P.G, P.refine_it == 0) * S.cpar[3];
-    }
+    cand_increments<CAND>(P, S, cidx, L.da, L.ddf);
     if (SEGMODE != 2 || seg_k0 == 0) sink.state(0, 0, S.x0);
-    typename FP::Work w;
-    w.d0 = w.d1 = 0.0;
-    if (XY) sincos_reduced(S.x0[6], w.s2, w.c2);       // carried as (sin,cos)(psi + beta_k); beta_{-1} = 0
-    else { w.s2 = 0.0; w.c2 = 1.0; }
+    L.w.d0 = L.w.d1 = 0.0;
+    if (XY) sincos_reduced(S.x0[6], L.w.s2, L.w.c2);       // carried as (sin,cos)(psi + beta_k); beta_{-1} = 0
+    else { L.w.s2 = 0.0; L.w.c2 = 1.0; }
     // (sin,cos)(epsi + beta_k) is carried the same way: the sub-steps turn the pair by exactly the angle epsi advances by
     // (substep(): h w2 - corr per sub-step), so after control step k-1 it holds (sin,cos)(epsi_k + beta_{k-1}) and step k
     // turns it by beta_k - beta_{k-1} -- no sincos(epsi) per control step (39 of ~460 instructions on a straight route)
-    double cb_prev = 1.0, sb_prev = 0.0;
-    double trk_sb = 0.0, trk_cb = 1.0;
-    bool trk_followed = false;
+    L.cb_prev = 1.0; L.sb_prev = 0.0;
+    L.trk_sb = 0.0; L.trk_cb = 1.0;
+    L.trk_followed = false;
     int k_first = 0, k_last = P.N;
     if (SEGMODE == 2) { k_first = seg_k0; k_last = seg_k1; }
     if (SEGMODE == 2 && seg_k0 > 0) {
-        // resume at node seg_k0: the controls' own recurrences are replayed (the statements of the loop below), the state that
+        // resume at node seg_k0: the controls' own recurrences are replayed (the statements of step_head), the state that
         // depends on the roll-out comes from the checkpoint
         for (int k = 0; k < seg_k0; ++k) {
             if (CAND == CAND_LATTICE) {
-                a = clampd(a + da, P.a_min, P.a_max);
-                df = steer_next<CAND>(P, S, k, ddf, df);
+                L.a = clampd(L.a + L.da, P.a_min, P.a_max);
+                L.df = steer_next<CAND>(P, S, k, L.ddf, L.df);
             } else if (CAND == CAND_RAMP_HOLD || CAND == CAND_TRACK) {
                 double ba, bdf;
                 ramp_base<double>(S.ws, P.N, k, S.a_prev, S.df_prev, ba, bdf);
                 if (CAND == CAND_TRACK) {
-                    a = track_accel_next(P, k, ba, da, v, a);
+                    L.a = track_accel_next(P, k, ba, L.da, L.v, L.a);
                 } else {
-                    const double ta = clampd(ba + da, P.a_min, P.a_max);
-                    a = clampd(a + clampd(ta - a, -P.rate_a, P.rate_a), P.a_min, P.a_max);
+                    const double ta = clampd(ba + L.da, P.a_min, P.a_max);
+                    L.a = clampd(L.a + clampd(ta - L.a, -P.rate_a, P.rate_a), P.a_min, P.a_max);
                 }
-                if (CAND == CAND_RAMP_HOLD) df = steer_next<CAND>(P, S, k, ddf, df);
+                if (CAND == CAND_RAMP_HOLD) L.df = steer_next<CAND>(P, S, k, L.ddf, L.df);
             } else {
-                a = table[((size_t)cidx * 2 + 0) * P.N + k];
-                df = table[((size_t)cidx * 2 + 1) * P.N + k];
+                L.a = table[((size_t)cidx * 2 + 0) * P.N + k];
+                L.df = table[((size_t)cidx * 2 + 1) * P.N + k];
             }
-            v = fma(fp.dt, a, v);
+            L.v = fma(fp.dt, L.a, L.v);
         }
-        s = ck[0]; ey = ck[1]; ep = ck[2]; w.s1 = ck[3]; w.c1 = ck[4];
-        if (CAND == CAND_TRACK) { df = ck[5]; sb_prev = ck[6]; cb_prev = ck[7]; }
-        else slip_trig<CAND>(P, fp.lr_ratio, df, sb_prev, cb_prev);      // of df_{k0-1}: what step k0-1 left in (sb_prev, cb_prev)
+        L.s = ck[0]; L.ey = ck[1]; L.ep = ck[2]; L.w.s1 = ck[3]; L.w.c1 = ck[4];
+        if (CAND == CAND_TRACK) { L.df = ck[5]; L.sb_prev = ck[6]; L.cb_prev = ck[7]; }
+        else slip_trig<CAND>(P, fp.lr_ratio, L.df, L.sb_prev, L.cb_prev);      // of df_{k0-1}: what step k0-1 left in (sb_prev, cb_prev)
     } else {
-        sincos_reduced(S.x0[4], w.s1, w.c1);
+        sincos_reduced(S.x0[4], L.w.s1, L.w.c1);
     }
-    int ck_q = 1, ck_k = (SEGMODE == 1 && ck) ? ckpt_step(P.N, 1) : -1;  // next checkpoint and its step (search; none without slots)
+    L.ck_q = 1; L.ck_k = (SEGMODE == 1 && ck) ? ckpt_step(P.N, 1) : -1;  // next checkpoint and its step (search; none without slots)
     // incumbent bound: rem = bound of the progress still to come (the row's own (a, v) recurrence rolled ahead, the statements of
     // the loop below), jcut = incumbent + a margin far above the rounding of LB_k (1e-9: the comparison is mathematically strict)
-    double rem = 0.0, jcut = (double)INFINITY, seg_scale = 0.0;
+    L.rem = 0.0; L.jcut = (double)INFINITY; L.seg_scale = 0.0;
     if (BOUND && inc) {
-        seg_scale = progress_slack(P, S) * P.dt;
-        if (seg_scale > 0.0) {
+        L.seg_scale = progress_slack(P, S) * P.dt;
+        if (L.seg_scale > 0.0) {
             if (rem_rows) {          // the row's sum as accel_rows_kernel left it (the statements of the loop in the other branch)
-                rem = rem_rows[cidx / P.G];
+                L.rem = rem_rows[cidx / P.G];
             } else {
                 double a2 = S.a_prev, v2 = S.x0[5];
                 for (int k = 0; k < P.N; ++k) {
                     double ba, bdf;
                     ramp_base<double>(S.ws, P.N, k, S.a_prev, S.df_prev, ba, bdf);
-                    a2 = track_accel_next(P, k, ba, da, v2, a2);
+                    a2 = track_accel_next(P, k, ba, L.da, v2, a2);
                     const double vn = fma(fp.dt, a2, v2);
-                    rem += fmax(fabs(v2), fabs(vn));
+                    L.rem += fmax(fabs(v2), fabs(vn));
                     v2 = vn;
                 }
             }
-            rem *= seg_scale * (1.0 + 1e-12);
+            L.rem *= L.seg_scale * (1.0 + 1e-12);
         } else {
             inc = nullptr;
         }
     }
 
+    const bool kv_d = !UNIFORM || fp.kv != 0.0;
     for (int k = k_first; k < k_last; ++k) {
-        if (SEGMODE == 1 && k == ck_k) {          // node k: what a roll-out needs to resume here
-            double* c = ck + (size_t)(ck_q - 1) * CKF * 64;
-            c[0] = s; c[64] = ey; c[128] = ep; c[192] = w.s1; c[256] = w.c1;
-            if (CAND == CAND_TRACK) { c[320] = df; c[384] = sb_prev; c[448] = cb_prev; }
-            ++ck_q;
-            ck_k = ck_q < CK_PARTS ? ckpt_step(P.N, ck_q) : -1;
-        }
-        // ---- controls of step k
-        if (CAND == CAND_LATTICE) {
-            a = clampd(a + da, P.a_min, P.a_max);
-            df = STAB ? stab[k * stab_stride] : steer_next<CAND>(P, S, k, ddf, df);
-        } else if (CAND == CAND_RAMP_HOLD) {
-            double ba, bdf;
-            ramp_base<double>(S.ws, P.N, k, S.a_prev, S.df_prev, ba, bdf);
-            const double ta = clampd(ba + da, P.a_min, P.a_max);
-            a = clampd(a + clampd(ta - a, -P.rate_a, P.rate_a), P.a_min, P.a_max);
-            df = STAB ? stab[k * stab_stride] : steer_next<CAND>(P, S, k, ddf, df);
-        } else if (CAND == CAND_TRACK) {
-            double ba, bdf;
-            ramp_base<double>(S.ws, P.N, k, S.a_prev, S.df_prev, ba, bdf);
-            a = track_accel_next(P, k, ba, da, v, a);
-            df = track_steer(P, df, ey, ep, ddf, &trk_sb, &trk_cb, &trk_followed);
-        } else {
-            const double an = table[((size_t)cidx * 2 + 0) * P.N + k];
-            const double dn = table[((size_t)cidx * 2 + 1) * P.N + k];
-            if (BOOK) {   // input-rate (mpc.py:301-312, u_{-1} = u_prev) and input box (mpc.py:318-321)
-                if (fmax(fabs(an - a) - P.rate_a, fabs(dn - df) - P.rate_df) > P.tol) viol |= VIOL_RATE;
-                if (fmax(fmax(P.a_min - an, an - P.a_max), fmax(-P.df_max - dn, dn - P.df_max)) > P.tol) viol |= VIOL_BOX_U;
-            }
-            a = an; df = dn;
-        }
-        sink.ctrl(0, k, a, df);
-        double sb, cb;                               // (sin, cos)(beta), beta = atan(r tan df)
-        if (STAB && (CAND == CAND_LATTICE || CAND == CAND_RAMP_HOLD)) {
-            sb = stab[k * stab_stride + 1];
-            cb = stab[k * stab_stride + 2];
-        } else if (CAND == CAND_TRACK) {
-            // a lane whose steering followed the command has beta = beta_cmd: its (sin, cos) are known already.  The other
-            // lanes (rate- or box-limited) go through sincos(df); the wave skips that when no lane needs it -- which lane
-            // takes which value does not depend on the vote, so search, emit and rollout-all agree bit for bit
-            sb = trk_sb; cb = trk_cb;
-            if (!__all(trk_followed)) {
-                double sb2, cb2;
-                slip_trig<CAND>(P, fp.lr_ratio, df, sb2, cb2);
-                sb = trk_followed ? sb : sb2;
-                cb = trk_followed ? cb : cb2;
-            }
-        } else {
-            slip_trig<CAND>(P, fp.lr_ratio, df, sb, cb);
-        }
-        sink.slip(0, k, sb, cb);
-        const double sblr = sb * fp.inv_lr;
-        // ---- bookkeeping of state k (cost in the oracle's order: control effort, epsi^2, ey^2 -- mpc.py:361-364)
-        if (BOOK) {
-            J = J + P.w_u * (a * a + df * df);
-            J = J + ep * ep;
-            J = J + ey * ey;
-            if (LEAN) {
-                gmax = fmax(gmax, fabs(ey) - P.ey_lim);                              // mpc.py:296-299
-                if (!rows_judged) gmax = fmax(gmax, fmax(P.v_min - v, v - P.v_max)); // mpc.py:316-317 (k < N)
-            } else {
-                if (fabs(ey) - P.ey_lim > P.tol) viol |= VIOL_EY;
-                if (fmax(P.v_min - v, v - P.v_max) > P.tol) viol |= VIOL_BOX_V;
-            }
-            if (k == P.N - 1 && !rows_judged) viol |= terminal_viol(P, v, a, cinf);  // mpc.py:177-180
-        }
-        w.ey = ey; w.v1 = v;
-        // unused on straight routes; with one scenario per lane the votes of substeps() read them on every lane
-        // (a straight route's break-points are +inf: d = -inf, "clear")
-        if (!UNIFORM || fp.kv != 0.0) { w.d0 = s - fp.b0; w.d1 = s - fp.b1; }
-        if (BOUND && inc) {
-            // the incumbent is re-read every fourth step (a unit that started before its scenario's first unit finished picks it
-            // up on the way); agent scope: the units of a scenario may run on different XCDs, whose L2s are not coherent
-            if ((k & 3) == 0) {
-                const double ji = cost_of_key(__hip_atomic_load(inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                jcut = ji + 1e-9 * (1.0 + fabs(ji));
-            }
-            if ((J - (s - S.x0[2])) - rem > jcut) viol |= VIOL_PRUNED;
-        }
+        const bool lost = step_head<CAND, BOOK, LEAN, BOUND, STAB, SEGMODE>(P, S, fp, L, k, cidx, table, cinf, sink, stab, stab_stride,
+                                                                            inc, ck, rows_judged, kv_d);
         if (BOOK && UNIFORM && EARLY_EXIT) {
             // search only: once every candidate of the slice has failed a verdict, nothing rolled further can win
-            const bool lost = (viol != 0) | (LEAN && gmax > P.tol);
             if (__all(lost) && !(P.dev & DEV_NO_EARLY_EXIT)) { dead = true; break; }
         }
-        if (BOOK && XY && k >= 1) {                                                  // collision, mpc.py:223-226
-            for (int o = 0; o < P.n_obs; ++o) {
-                const double dx = x - S.obs[(o * 2 + 0) * (P.N + 1) + k], dy = y - S.obs[(o * 2 + 1) * (P.N + 1) + k];
-                const double g = P.dmin2 - (dx * dx + dy * dy);
-                if (LEAN) gmax = fmax(gmax, g);
-                else if (g > P.tol) viol |= VIOL_COLLISION;
-            }
-        }
-        // (sin,cos)(psi + beta_k) from (psi + beta_{k-1}), and (sin,cos)(epsi + beta_k) from (epsi + beta_{k-1}): rotate by
-        // beta_k - beta_{k-1}, re-normalise (first order: the pairs are within rounding of unit length)
-        {
-            const double sdb = fma(sb, cb_prev, -(cb * sb_prev));
-            const double cdb = fma(cb, cb_prev, sb * sb_prev);
-            rotate(w.s1, w.c1, sdb, cdb);
-            const double r1 = fma(fma(w.s1, w.s1, w.c1 * w.c1), -0.5, 1.5);
-            w.s1 *= r1; w.c1 *= r1;
-            if (XY) {
-                rotate(w.s2, w.c2, sdb, cdb);
-                const double r2 = fma(fma(w.s2, w.s2, w.c2 * w.c2), -0.5, 1.5);
-                w.s2 *= r2; w.c2 *= r2;
-            }
-            cb_prev = cb; sb_prev = sb;
-        }
-        w.acc_s = 0.0; w.acc_ey = 0.0; w.acc_ep = 0.0; w.acc_x = 0.0; w.acc_y = 0.0; w.acc_psi = 0.0;
-        fp.template substeps<UNIFORM, XY>(a, sblr, w);
-        s += w.acc_s; ey += w.acc_ey; ep += w.acc_ep;
-        if (XY) { x += w.acc_x; y += w.acc_y; }
-        if (KEEP_PSI) psi += w.acc_psi;        // psi feeds nothing back (search: dead code)
-        if (BOUND && inc) rem -= seg_scale * fmax(fabs(v), fabs(fma(fp.dt, a, v)));      // this step's share of the bound is spent
-        v = fma(fp.dt, a, v);
-        const double nxt[7] = {x, y, s, ey, ep, v, psi};
-        sink.state(0, k + 1, nxt);
+        step_tail<BOOK, LEAN, BOUND, UNIFORM, XY, KEEP_PSI>(P, S, fp, L, k, sink, inc);
     }
     if (dead) {            // costs are meaningless; "failed" is what is reported
-        Jout = 0.0; vout = viol | ((LEAN && gmax > P.tol) ? VIOL_EY : 0u); sN = 0.0; vN = 0.0;
+        Jout = 0.0; vout = L.viol | ((LEAN && L.gmax > P.tol) ? VIOL_EY : 0u); sN = 0.0; vN = 0.0;
         return;
     }
     if (BOOK) {
-        J = J + ep * ep;
-        J = J + ey * ey;
-        if (LEAN) gmax = fmax(gmax, fabs(ey) - P.ey_lim);
-        else if (fabs(ey) - P.ey_lim > P.tol) viol |= VIOL_EY;
-        for (int o = 0; XY && o < P.n_obs; ++o) {
-            const double dx = x - S.obs[(o * 2 + 0) * (P.N + 1) + P.N], dy = y - S.obs[(o * 2 + 1) * (P.N + 1) + P.N];
-            const double g = P.dmin2 - (dx * dx + dy * dy);
-            if (LEAN) gmax = fmax(gmax, g);
-            else if (g > P.tol) viol |= VIOL_COLLISION;
-        }
-        if (LEAN && gmax > P.tol) viol |= VIOL_EY;     // lean form: "some state-side verdict failed"
-        if (!(fabs(x) < 1e300 && fabs(y) < 1e300 && fabs(s) < 1e300 && fabs(ey) < 1e300 && fabs(ep) < 1e300 &&
-              fabs(psi) < 1e300))
-            viol |= VIOL_NONFINITE;
-        sN = s; vN = v; Jout = J; vout = viol;
+        horizon_end<LEAN, XY>(P, S, L, Jout, vout, sN, vN);
     } else {
         Jout = 0.0; vout = 0; sN = 0.0; vN = 0.0;
+    }
+}
+
+// ---- the pool roll-out (search, lattice family on live rows with the whole steering table in LDS) ----
+// A unit of 64 candidates leaves through the early exit only when all 64 have failed, and a lattice candidate is feasible
+// rarely (5 %) and dies mostly between steps 4 and 12: a unit's wave spends much of its time issuing for lanes that are dead
+// already.  Here one wave owns all n candidates of its scenario as a pool: every lane holds a candidate number, a step k of
+// its own and its state; one iteration is one control step for every lane that holds a candidate, each at its own k; a lane
+// whose candidate failed a verdict in its last step (step_head) or reached k = N (horizon_end) takes the pool's next number -- numbers are handed
+// out by a ballot and a prefix count from a wave-uniform cursor, no atomics (tools/refill_model.py: 0.52 -> 0.39 of the
+// wave-steps on the benchmark batch).  The statements are rollout_one's (step_head / step_tail / horizon_end), so every
+// candidate's cost and verdicts are the bits the units compute; the sub-step votes run over lanes at different k and may pick
+// another variant than a unit's wave would -- the variants are bit-identical where they apply.
+// The arg-min: the candidates that finish feasible in an iteration are reduced together with the wave's best on (Jq, c), ties
+// to the lowest index -- a total order, so the winner does not depend on the order the pool is worked in.  With checkpoint slots
+// (ck: the lane's column of the LDS records, SEGMODE 1) the new winner's lane copies its records to `rec` (15 doubles).
+// cand_of(g, col): candidate number g of the scenario -> candidate index, and its steering column's rank in the table.
+// start: POOL_START doubles of LDS for what a refill reads of the scenario (read there when a lane refills instead of held in
+// registers over the whole loop: the kernel is at its 256 registers).
+constexpr int POOL_START = 13;
+template <int CAND, bool HI_ORDER, int NRK, bool XY, class CandOf>
+__device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>& S, int n, const CandOf& cand_of,
+                                             const double* __restrict__ cinf, const double* __restrict__ stab, int stab_stride,
+                                             double* ck, double* rec, double* start, double& wJ, int& wC) {
+    static_assert(CAND == CAND_LATTICE, "pool roll-out: the lattice family (its steering is a column of the table)");
+    constexpr int CKF = 5;
+    typedef Fast64<HI_ORDER, NRK> FP;
+    FP fp;
+    fp.init(P, S.b0, S.b1, S.kv);
+    NullSink sink;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // the initial pairs are the scenario's: once per item instead of once per candidate
+    if (lane == 0) {
+        double s1_0, c1_0, s2_0 = 0.0, c2_0 = 1.0;
+        sincos_reduced(S.x0[4], s1_0, c1_0);
+        if (XY) sincos_reduced(S.x0[6], s2_0, c2_0);
+#pragma unroll
+        for (int i = 0; i < 7; ++i) start[i] = S.x0[i];
+        start[7] = S.a_prev; start[8] = S.df_prev;
+        start[9] = s1_0; start[10] = c1_0; start[11] = s2_0; start[12] = c2_0;
+    }
+    __syncthreads();
+    const bool kv_d = fp.kv != 0.0;
+    LaneRoll<FP> L;
+    L.psi = S.x0[6];                                // psi feeds nothing back (search)
+    L.da = 0.0; L.ddf = 0.0; L.trk_sb = 0.0; L.trk_cb = 1.0; L.trk_followed = false;
+    L.rem = 0.0; L.jcut = (double)INFINITY; L.seg_scale = 0.0;
+    int c = 0, k = 0;
+    const double* lstab = stab;
+    bool hold = false;
+    int next = 0;                                   // the pool's cursor (wave-uniform)
+    wJ = 0.0; wC = -1;
+    for (;;) {
+        // ---- idle lanes take the next numbers
+        const unsigned long long want = __ballot(!hold);
+        if (want != 0ull && next < n) {
+            const int g = next + __popcll(want & below);
+            if (!hold && g < n) {
+                int col;
+                c = cand_of(g, col);
+                lstab = stab + col * 3;
+                L.x = start[0]; L.y = start[1]; L.s = start[2]; L.ey = start[3]; L.ep = start[4]; L.v = start[5];
+                L.a = start[7]; L.df = start[8]; L.J = 0.0; L.gmax = -1.0e300; L.viol = 0u;
+                cand_increments<CAND>(P, S, c, L.da, L.ddf);
+                L.w.d0 = L.w.d1 = 0.0;
+                L.w.s1 = start[9]; L.w.c1 = start[10]; L.w.s2 = start[11]; L.w.c2 = start[12];
+                L.cb_prev = 1.0; L.sb_prev = 0.0;
+                L.ck_q = 1; L.ck_k = ck ? ckpt_step(P.N, 1) : -1;
+                k = 0; hold = true;
+            }
+            next += __popcll(want);
+        }
+        if (__ballot(hold) == 0ull) break;
+        // ---- control step k for every lane that holds a candidate; it retires a candidate that failed a verdict of state k,
+        // and one that reached state N after the bookkeeping of the end of the horizon
+        bool fin = false;
+        double Jq = 0.0;
+        if (hold) {
+            const bool lost = step_head<CAND, true, true, false, true, 1>(P, S, fp, L, k, c, nullptr, cinf, sink, lstab, stab_stride,
+                                                                          nullptr, ck, true, kv_d);
+            step_tail<true, true, false, true, XY, false>(P, S, fp, L, k, sink, nullptr);
+            ++k;
+            if (lost) {
+                hold = false;
+            } else if (k == P.N) {
+                double J, sN, vN;
+                unsigned viol;
+                horizon_end<true, XY>(P, S, L, J, viol, sN, vN);
+                Jq = J - (sN - start[2]);                      // mpc.py:372 (start[2] = x0[2])
+                fin = viol == 0 && fabs(Jq) < 1.79e308;        // finite_d
+                hold = false;
+            }
+        }
+        // ---- feasible candidates that finished: reduced with the wave's best (the units' butterfly and tie rule)
+        if (__ballot(fin) != 0ull) {
+            double bJ = Jq;
+            int bC = fin ? c : -1;
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const double oJ = __shfl_xor(bJ, off, 64);
+                const int oC = __shfl_xor(bC, off, 64);
+                const bool take = (oC >= 0) && (bC < 0 || oJ < bJ || (oJ == bJ && oC < bC));
+                if (take) { bJ = oJ; bC = oC; }
+            }
+            bJ = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(bJ)), __builtin_amdgcn_readfirstlane(__double2loint(bJ)));
+            bC = __builtin_amdgcn_readfirstlane(bC);
+            if (wC < 0 || bJ < wJ || (bJ == wJ && bC < wC)) {
+                wJ = bJ; wC = bC;
+                if (ck && fin && c == bC) {                   // the new winner's checkpoints, [q][field]
+#pragma unroll
+                    for (int q = 0; q < CK_PARTS - 1; ++q)
+#pragma unroll
+                        for (int f = 0; f < CKF; ++f) rec[q * CKF + f] = ck[(size_t)(q * CKF + f) * 64];
+                }
+            }
+        }
     }
 }
 

@@ -206,11 +206,13 @@ constexpr int QC = 8, QB_THREADS = 1024, QB_TRIPS = 2;     // up to 2048 units p
 // row_mask: the scenarios' live acceleration rows when they are known at this point (a slice beyond the live rows' units is
 // a hole and sorts last); null: not known -- such slices are sorted as if they held candidates and the search skips them
 // when it gets there.  by_rows: the tracking family's units are cut along the acceleration axis (unit-rank-major order).
+// pool_units > 0 (W = 1): the items are whole scenarios rolled as one pool of candidates (igt_kernels_f64.hip search_pool64);
+// an item costs what its pool_units units would, per unit: the mean of their costs.
 template <typename T, int QB_THREADS_, int QB_TRIPS_>
 __device__ __forceinline__ void build_queue(const KP& P, int B, int W, int q, const T* __restrict__ x0,
                                             const T* __restrict__ kparams, unsigned* __restrict__ order, int stride,
                                             unsigned* __restrict__ work_counter,
-                                            const unsigned long long* __restrict__ row_mask, bool by_rows) {
+                                            const unsigned long long* __restrict__ row_mask, bool by_rows, int pool_units = 0) {
     constexpr int QB_THREADS = QB_THREADS_, QB_TRIPS = QB_TRIPS_;
     __shared__ int cnt[QB_TRIPS][QB_THREADS / 64][QC];   // [trip][wave][class] counts, then exclusive offsets
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -244,7 +246,8 @@ __device__ __forceinline__ void build_queue(const KP& P, int B, int W, int q, co
         for (int p = 0; p < W; ++p) {
             int c = QC - 1;
             if (p < nu) {
-                const float cost = (p == 0 ? 0.95f : frac_out) * weight;                              // 0.4 .. 1.8
+                const float cost = (pool_units > 0 ? (0.95f + (float)(pool_units - 1) * frac_out) / (float)pool_units
+                                                    : (p == 0 ? 0.95f : frac_out)) * weight;          // 0.4 .. 1.8
                 c = (int)((1.85f - cost) * ((float)QC / 1.5f));
                 c = c < 0 ? 0 : (c > QC - 1 ? QC - 1 : c);
                 if (by_rank) c = W <= QC ? p : (p * QC) / W;

@@ -190,11 +190,11 @@ __global__ __launch_bounds__(ROWS_THREADS) void accel_rows_kernel(KP P, int B, c
                                                          const double* __restrict__ cinf, Centre<double> cpar,
                                                          unsigned long long* __restrict__ row_mask, double* __restrict__ row_rem,
                                                          int W, const double* __restrict__ kparams, unsigned* __restrict__ order,
-                                                         int order_stride, unsigned* __restrict__ work_counter) {
+                                                         int order_stride, unsigned* __restrict__ work_counter, int pool_units) {
     if constexpr (QUEUES) {
-        if (blockIdx.x < 8) {
-            build_queue<double, ROWS_THREADS, ROWS_QB_TRIPS>(P, B, W, (int)blockIdx.x, x0, kparams, order, order_stride,
-                                                             work_counter, nullptr, true);
+        if (blockIdx.x < 8) {      // pool_units > 0: one item per scenario (search_pool64)
+            build_queue<double, ROWS_THREADS, ROWS_QB_TRIPS>(P, B, pool_units > 0 ? 1 : W, (int)blockIdx.x, x0, kparams, order,
+                                                             order_stride, work_counter, nullptr, true, pool_units);
             return;
         }
     }
@@ -422,6 +422,73 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                                        rec_vN, rec_J, rec_viol, rec_count, rec_b, unit_seg, live_rows_of(P, B, W, part_J), nullptr,
                                        incumbents_of<CAND, VALUE>(P, B, W, part_J), checkpoints_of(P, B, W, part_J), row_rems_of(P, B, W, part_J));
     }, rank_major_items(P, CAND, VALUE));
+}
+// One work item = one scenario's whole pool of live lattice candidates, rolled by one wave with lanes that refill
+// (igt_fast64.h rollout_pool).  Candidates are numbered as unit_candidate numbers them in the live-row layout: g = r R + q,
+// column rank r from the centre outwards, q the rank among the live rows.  The steering table holds all G columns.  The item
+// leaves the scenario's best (J, c) in slot 0 of its W partials, (0, -1) in the others, and with checkpoint slots the winner's
+// record in slot 0: the emit kernels read the partials as they read the units'.
+template <int CAND, bool HI, int NRK>
+__device__ __forceinline__ void search_pool64(const KP& P, int W, int b, const double* __restrict__ x0,
+                                              const double* __restrict__ u_prev, const double* __restrict__ kparams,
+                                              const uint32_t* __restrict__ flags, const double* __restrict__ obs,
+                                              const double* __restrict__ cinf, Centre<double> cpar, double* __restrict__ part_J,
+                                              int32_t* __restrict__ part_c, const unsigned long long* __restrict__ row_mask,
+                                              double* __restrict__ ck_all) {
+    const int lane = threadIdx.x & 63;
+    const UnitLayout L = unit_layout(P, W, CAND, row_mask[b]);
+    const int R = __builtin_amdgcn_readfirstlane(L.R), n = P.G * R, lg = __ffs(P.G) - 1;
+    constexpr int CKF = 5;
+    __shared__ int rank2row[64];
+    __shared__ double stab[f64::STAB_MAX_ENTRIES * 3];
+    __shared__ double ckl[(f64::CK_PARTS - 1) * CKF * 64];
+    __shared__ double rec[(f64::CK_PARTS - 1) * CKF];
+    __shared__ double start[f64::POOL_START];
+    double wJ = 0.0;
+    int wC = -1;
+    if (n > 0) {
+        Scenario<double> S;
+        load_scenario<double>(S, P, b, x0, u_prev, kparams, flags, obs, cpar);
+        rows_by_rank(L, lane, rank2row);
+        f64::fill_steer_table<CAND>(P, S, P.G, 0, lane, P.lr_ratio, stab);
+        auto cand_of = [&](int g, int& col) {
+            const int r = small_div(g, R), rank = g - r * R;
+            const int j = (r & 1) ? P.G / 2 - 1 - (r >> 1) : P.G / 2 + (r >> 1);      // unit_candidate's column order
+            col = r;
+            return (rank2row[rank] << lg) + j;
+        };
+        const bool far = !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
+        double* ck = ck_all ? ckl + lane : nullptr;
+        if (far) f64::rollout_pool<CAND, HI, NRK, false>(P, S, n, cand_of, cinf, stab, P.G * 3, ck, rec, start, wJ, wC);
+        else f64::rollout_pool<CAND, HI, NRK, true>(P, S, n, cand_of, cinf, stab, P.G * 3, ck, rec, start, wJ, wC);
+        __syncthreads();                                  // rec is complete; the next item of this wave rewrites the tables
+    }
+    if (lane < W) {
+        part_J[b * W + lane] = lane == 0 ? wJ : 0.0;
+        part_c[b * W + lane] = lane == 0 ? wC : -1;
+    }
+    if (ck_all && wC >= 0 && lane < CKF * (f64::CK_PARTS - 1)) {
+        const int q = lane / CKF, f = lane - q * CKF;
+        ck_all[(size_t)(b * W) * CK_RECORD + q * f64::CK_FIELDS + f] = rec[lane];
+    }
+}
+// Whether the search rolls pools of candidates (search_pool64) instead of 64-candidate units: the lattice family, progress cost,
+// units of live rows, the steering table of all G columns fits.  Every developer switch that changes the units' layout keeps
+// the units (the A/B comparisons of the units stay what they were), and so does DEV_NO_REFILL; so do the queues sorted by
+// build_queues_kernel (DEV_SEPARATE_QUEUES), which knows only units.
+__host__ __device__ inline bool search_pools(const KP& P, int cand, bool value, bool live_rows) {
+    return cand == CAND_LATTICE && !value && live_rows && P.G * P.N <= STEER_TABLE_MAX_ENTRIES &&
+           !(P.dev & (DEV_NO_SLICES | DEV_NO_EARLY_EXIT | DEV_NO_STEER_TABLE | DEV_ALL_ROWS | DEV_WHOLE_COLUMNS | DEV_NO_REFILL |
+                      DEV_SEPARATE_QUEUES | DEV_WAVES3));
+}
+template <int CAND, bool HI, bool VALUE, int NRK>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_f64_kernel_pool(IGT_SEARCH64_ARGS) {
+    if constexpr (CAND == CAND_LATTICE && !VALUE) {
+        search_waves(P, B, 1, queues, work_counter, order, order_stride, [&](int b, int) {
+            search_pool64<CAND, HI, NRK>(P, W, b, x0, u_prev, kparams, flags, obs, cinf, cpar, part_J, part_c,
+                                         live_rows_of(P, B, W, part_J), checkpoints_of(P, B, W, part_J));
+        });
+    }
 }
 // small batches (captures_trajectories): the same search, every unit also leaves its 64 trajectories in `traj`
 template <int CAND, bool VALUE>
@@ -840,7 +907,11 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
     const size_t slots = (size_t)A.n_cu * 4 * (o3 ? 3 : (A.waves_per_simd == 1 ? 1 : 2));
     const size_t grid = total < slots ? total : slots;
     const unsigned* order = nullptr;
-    const int order_stride = ((B + 7) / 8) * W;
+    // lattice on live rows: one item per scenario, its candidates rolled as one pool by a wave whose lanes refill (search_pool64).
+    // An item is about four units long, and with fewer than four per wave the longest items make the span (one solve at a time,
+    // B = 4096: 2 per wave, search 0.208 -> 0.230 ms; four solves in flight, one wave per SIMD: 4 per wave, 23.6 -> 27.0 M solves/s)
+    const bool pools = !o3 && search_pools(P, CAND, VALUE, packs_live_rows(P, B, A)) && (size_t)B >= 4 * slots;
+    const int order_stride = ((B + 7) / 8) * (pools ? 1 : W);
     if (!HI && search_is_static(P, B, A)) {
         hipLaunchKernelGGL((search_f64_kernel_cap<CAND, VALUE>), dim3(total), dim3(64), 0, st, P, B, W, 0, A.work_counter, order,
                            order_stride, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c,
@@ -864,7 +935,7 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
             hipLaunchKernelGGL((accel_rows_kernel<CAND, QUEUES_>), dim3(n_groups + (QUEUES_ ? 8 : 0)), dim3(ROWS_THREADS), 0, st, P, \
                                B, A.x0, A.u_prev, A.flags, A.cinf, A.centre(), A.row_mask, A.row_rems,        \
                                W, A.kparams, A.queue_order, order_stride,           \
-                               A.work_counter)
+                               A.work_counter, pools ? W : 0)
             if (queues_built) { IGT_LAUNCH_ROWS(true); order = A.queue_order; } else IGT_LAUNCH_ROWS(false);
 #undef IGT_LAUNCH_ROWS
             Pr.dev |= DEV_LAUNCH_LIVE_ROWS;
@@ -879,6 +950,19 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
         hipLaunchKernelGGL((search_f64_kernel_cap<CAND, VALUE>), dim3(grid), dim3(64), 0, st, P, B, W, 8, A.work_counter, order,
                            order_stride, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c,
                            A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b, A.unit_seg, A.traj);
+        return hipGetLastError();
+    }
+    if constexpr (CAND == CAND_LATTICE && !VALUE) if (pools) {
+        const size_t pgrid = (size_t)B < slots ? (size_t)B : slots;
+        constexpr int NRK4 = HI ? 0 : 4;
+        if (NRK4 == 4 && P.n_rk4 == 4)
+            hipLaunchKernelGGL((search_f64_kernel_pool<CAND, HI, VALUE, NRK4>), dim3(pgrid), dim3(64), 0, st, Pr, B, W, 8, A.work_counter,
+                               order, order_stride, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J,
+                               A.part_c, A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b, A.unit_seg);
+        else
+            hipLaunchKernelGGL((search_f64_kernel_pool<CAND, HI, VALUE, 0>), dim3(pgrid), dim3(64), 0, st, Pr, B, W, 8, A.work_counter,
+                               order, order_stride, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J,
+                               A.part_c, A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b, A.unit_seg);
         return hipGetLastError();
     }
 #if IGT_DEV_KERNELS
