@@ -159,6 +159,8 @@ int validate(const igt_params& p, std::string& why) {
     }
     if (p.refine_iters < 0 || p.refine_iters > 4) { why = "refine_iters must be in [0, 4]"; return -1; }
     if (p.refine_iters > 0 && p.cand_mode != IGT_CAND_RAMP_HOLD && p.cand_mode != IGT_CAND_TRACK) { why = "refine_iters needs IGT_CAND_RAMP_HOLD or IGT_CAND_TRACK"; return -1; }
+    if (p.polish_iters < 0 || p.polish_iters > 4) { why = "polish_iters must be in [0, 4]"; return -1; }
+    if (p.polish_iters > 0 && p.cost_mode != IGT_COST_PROGRESS) { why = "polish_iters needs IGT_COST_PROGRESS (the value-network cost is not polished)"; return -1; }
     if (p.cand_mode == IGT_CAND_TRACK && (!(p.track_ke >= 0) || !(p.track_span >= 0) || !(p.track_beta_lim > 0) || !(p.track_beta_lim < 1.5) || !(p.track_env >= 0) || !(p.track_env < 1e6) || !(p.track_vcap >= 0) || !(p.track_vcap < 1e6))) { why = "track_ke, track_span, track_env, track_vcap must be >= 0 (and finite) and 0 < track_beta_lim < 1.5"; return -1; }
     if (p.cost_mode != IGT_COST_PROGRESS && p.cost_mode != IGT_COST_VALUE_NET) { why = "unknown cost_mode"; return -1; }
     if (!(p.v_min <= p.v_max) || !(p.a_min <= p.a_max) || !(p.df_max >= 0)) { why = "inconsistent limits"; return -1; }
@@ -298,6 +300,10 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     if (empty) return IGT_OK;
     if (!x_out || !u_out || !cost_out || !argmin_out || !status_out) return fail(IGT_E_INVALID, "null buffer");
     const igt_params& p = h->p;
+    if (p.polish_iters > 0 && sizeof(T) == 4)
+        return fail(IGT_E_INVALID, "polish_iters > 0 needs the _f64 entry points (a forward difference of 1e-4 on a float cost is noise)");
+    if (p.polish_iters > 0 && (h->kp.dev & (igt::DEV_EXACT64 | igt::DEV_LITERAL)))
+        return fail(IGT_E_INVALID, "polish_iters > 0 is not available with the developer kernels of IGT_DEV_FLAGS 1024 / 2048");
     const bool value = p.cost_mode == IGT_COST_VALUE_NET;
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
@@ -472,6 +478,9 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     }
     if (h->prof) HIPCHK(hipEventRecord(h->ev[1], st));
     HIPCHK(igt::launch_emit<T>(kp, B, (int)W, A, st));
+    if constexpr (sizeof(T) == 8) {      // the winners, polished in place in the outputs (igt_kernels_f64.hip polish_f64_kernel)
+        if (p.polish_iters > 0) HIPCHK(igt::launch_polish(kp, B, p.polish_iters, A, st));
+    }
     if (h->prof) { HIPCHK(hipEventRecord(h->ev[2], st)); h->ev_recorded = true; }
 
     if (h->kp.dev & igt::DEV_TRACE) {      // developer trace -> $IGT_DEV_TRACE (binary u64[units][4])
@@ -764,6 +773,7 @@ int igt_params_default(igt_params* p) {
     p->w_u = 0.05;                                        /* mpc.py:362 */
     p->feas_tol = 1e-6;
     p->refine_iters = 0;
+    p->polish_iters = 0;
     p->track_ke = 0.3; p->track_span = 0.1; p->track_beta_lim = 0.7; p->track_env = 1.0; p->track_vcap = 1.0;
     return IGT_OK;
 }

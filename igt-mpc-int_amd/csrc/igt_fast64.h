@@ -401,7 +401,7 @@ struct LaneRoll {
 // collision check of state k, the rotation of the carried pairs, the sub-steps -- takes the lane to state k + 1.  Every
 // roll-out of the float64 path runs these statements, so whatever runs them gives the same bits.
 // LEAN: |ey|, box v and collision folded into the running maximum gmax (search).  stab: the lane's steering column of the
-// table (entry k at stab[k * stab_stride]).
+// table (entry k at stab[k * stab_stride]); CAND_TABLE: the lane's control sequence (see the table branch).
 template <int CAND, bool BOOK, bool LEAN, bool BOUND, bool STAB, int SEGMODE, class FP, class Sink>
 __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S, const FP& fp, LaneRoll<FP>& L, int k, int cidx,
                                           const double* __restrict__ table, const double* __restrict__ cinf, Sink& sink,
@@ -431,8 +431,9 @@ __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S
         L.a = track_accel_next(P, k, ba, L.da, L.v, L.a);
         L.df = track_steer(P, L.df, L.ey, L.ep, L.ddf, &L.trk_sb, &L.trk_cb, &L.trk_followed);
     } else {
-        const double an = table[((size_t)cidx * 2 + 0) * P.N + k];
-        const double dn = table[((size_t)cidx * 2 + 1) * P.N + k];
+        // STAB (polish_f64_kernel): the lane's own controls in LDS, a at stab[k * stab_stride], delta_f N entries behind
+        const double an = STAB ? stab[(size_t)k * stab_stride] : table[((size_t)cidx * 2 + 0) * P.N + k];
+        const double dn = STAB ? stab[(size_t)(P.N + k) * stab_stride] : table[((size_t)cidx * 2 + 1) * P.N + k];
         if (BOOK) {   // input-rate (mpc.py:301-312, u_{-1} = u_prev) and input box (mpc.py:318-321)
             if (fmax(fabs(an - L.a) - P.rate_a, fabs(dn - L.df) - P.rate_df) > P.tol) L.viol |= VIOL_RATE;
             if (fmax(fmax(P.a_min - an, an - P.a_max), fmax(-P.df_max - dn, dn - P.df_max)) > P.tol) L.viol |= VIOL_BOX_U;

@@ -690,6 +690,114 @@ __global__ __launch_bounds__(SEG_THREADS) void emit_seg_f64_kernel(KP P, int B, 
     }
 }
 
+// ---- polish of the winner (igt_params.polish_iters; float64, progress cost) ----
+// One wave per solved scenario improves the emitted plan u*[2, N] by projected-gradient steps.  An iteration is two kinds of
+// trips of 64 roll-outs, one per lane: the forward-difference gradient (perturbation c = row c / N, step c % N on lane c; one trip
+// for N <= 32, two up to IGT_MAX_N), then the line search (trial m on lane m: u + 2^(-m/3) d, clamped step by step to the rate
+// window around the clamped step before it and to the input box).  Every lane's control sequence lies in LDS, [2 N][64]: the 64
+// lanes' reads of step k are 64 consecutive doubles, no two on one bank in a pass.  The roll-out is rollout_one itself on the
+// table family with the lane's LDS column as its table (step_head, STAB): the statements of search, emit and rollout-all, so
+// cost and verdicts of a trial are the bits igt_rollout_batch_f64 gives for the same controls, and since all lanes belong to one
+// scenario the sub-step variants are voted as in a search unit.  Scenarios whose obstacles are out of reach roll the trips
+// without the Cartesian rows (obstacles_out_of_reach).  A plan that changed is rolled once more with all rows into LDS and
+// written back as whole rows; one that did not is left alone.  No workspace, no host synchronisation: one launch on the stream.
+constexpr double POLISH_EPS = 1e-4;
+__host__ __device__ inline size_t polish_lds_doubles(int N) { return (size_t)2 * N * 64 + 4 * N + 7 * (N + 1); }
+template <bool HI, int NRK>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void polish_f64_kernel(
+        KP P, int B, int iters, const double* __restrict__ x0, const double* __restrict__ u_prev, const double* __restrict__ kparams,
+        const uint32_t* __restrict__ flags, const double* __restrict__ obs, const double* __restrict__ cinf,
+        const int32_t* __restrict__ status_out, double* __restrict__ cost_out, double* __restrict__ x_out, double* __restrict__ u_out) {
+    extern __shared__ double polish_lds[];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B || status_out[b] != 0) return;             // unsolved: neither read nor written
+    const int N = P.N, n2 = 2 * N;
+    double* slot = polish_lds;                            // [2 N][64] the lanes' control sequences
+    double* u = slot + (size_t)n2 * 64;                   // [2 N] the plan so far
+    double* g = u + n2;                                   // [2 N] gradient, then direction
+    double* xl = g + n2;                                  // [7][N + 1] the final plan's states
+    Scenario<double> S;
+    load_scenario<double>(S, P, b, x0, u_prev, kparams, flags, obs);
+    const bool far = !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
+    for (int i = lane; i < n2; i += 64) u[i] = u_out[(size_t)b * n2 + i];
+    double J0 = cost_out[b];
+    bool changed = false;
+    NullSink none;
+    __syncthreads();
+    const int g_trips = (n2 + 63) >> 6;
+    for (int it = 0; it < iters; ++it) {
+        double bestJ = 0.0;
+        int bestM = -1;
+        for (int trip = 0; trip <= g_trips; ++trip) {
+            const bool search = trip == g_trips;
+            if (!search) {                                // u + eps e_c: no projection
+                const int c = trip * 64 + lane;
+                for (int i = 0; i < n2; ++i) slot[(size_t)i * 64 + lane] = i == c ? u[i] + POLISH_EPS : u[i];
+            } else {
+                // d = -g / scale: the longest trial moves some input by four rate limits
+                double ma = 0.0, md = 0.0;
+                for (int k = lane; k < N; k += 64) { ma = fmax(ma, fabs(g[k])); md = fmax(md, fabs(g[N + k])); }
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) {
+                    ma = fmax(ma, __shfl_xor(ma, off, 64));
+                    md = fmax(md, __shfl_xor(md, off, 64));
+                }
+                const bool steer = P.rate_df > 0.0;
+                const double scale = (steer ? fmax(ma / (4.0 * P.rate_a), md / (4.0 * P.rate_df)) : ma / (4.0 * P.rate_a)) + 1e-30;
+                __syncthreads();                          // every lane has read g
+                for (int i = lane; i < n2; i += 64) g[i] = (i < N || steer) ? -g[i] / scale : 0.0;
+                __syncthreads();
+                const double alpha = exp2(-(double)lane / 3.0);
+                double pa = S.a_prev, pd = S.df_prev;
+                for (int k = 0; k < N; ++k) {
+                    pa = clampd(clampd(u[k] + alpha * g[k], pa - P.rate_a, pa + P.rate_a), P.a_min, P.a_max);
+                    pd = clampd(clampd(u[N + k] + alpha * g[N + k], pd - P.rate_df, pd + P.rate_df), -P.df_max, P.df_max);
+                    slot[(size_t)k * 64 + lane] = pa;
+                    slot[(size_t)(N + k) * 64 + lane] = pd;
+                }
+            }
+            double J, sN, vN;
+            unsigned viol;
+            if (far) f64::rollout_one<CAND_TABLE, HI, true, true, NullSink, false, true, NRK, false>(P, S, 0, nullptr, cinf, none, J, viol, sN, vN, slot + lane, 64);
+            else f64::rollout_one<CAND_TABLE, HI, true, true, NullSink, false, true, NRK, true>(P, S, 0, nullptr, cinf, none, J, viol, sN, vN, slot + lane, 64);
+            const double Jq = J - (sN - S.x0[2]);         // mpc.py:372
+            if (!search) {
+                const int c = trip * 64 + lane;
+                if (c < n2) g[c] = finite_d(Jq) ? (Jq - J0) / POLISH_EPS : 0.0;
+                __syncthreads();
+            } else {
+                bestJ = Jq;
+                bestM = (viol == 0 && finite_d(Jq)) ? lane : -1;
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) {     // the search's butterfly on (J, m), ties to the lowest m
+                    const double oJ = __shfl_xor(bestJ, off, 64);
+                    const int oM = __shfl_xor(bestM, off, 64);
+                    const bool take = (oM >= 0) && (bestM < 0 || oJ < bestJ || (oJ == bestJ && oM < bestM));
+                    if (take) { bestJ = oJ; bestM = oM; }
+                }
+            }
+        }
+        if (bestM < 0 || !(bestJ < J0)) break;            // accepted only when feasible and strictly cheaper
+        __syncthreads();
+        for (int i = lane; i < n2; i += 64) u[i] = slot[(size_t)i * 64 + bestM];
+        J0 = bestJ;
+        changed = true;
+        __syncthreads();
+    }
+    if (!changed) return;
+    // the polished plan with all rows: every lane rolls it (one wave's time either way), lane 0 keeps the states
+    for (int i = 0; i < n2; ++i) slot[(size_t)i * 64 + lane] = u[i];
+    StoreSink<double> keep{lane == 0 ? xl : nullptr, nullptr, N};
+    double J, sN, vN;
+    unsigned viol;
+    f64::rollout_one<CAND_TABLE, HI, true, true, StoreSink<double>, false, true, NRK, true>(P, S, 0, nullptr, cinf, keep, J, viol, sN, vN, slot + lane, 64);
+    __syncthreads();
+    const int nx = 7 * (N + 1);
+    for (int i = lane; i < nx; i += 64) x_out[(size_t)b * nx + i] = xl[i];
+    for (int i = lane; i < n2; i += 64) u_out[(size_t)b * n2 + i] = u[i];
+    if (lane == 0) cost_out[b] = J - (sN - S.x0[2]);
+}
+
 template <int CAND, bool HI>
 __global__ __launch_bounds__(256) void rollout_all_f64_kernel(KP P, int B, const double* __restrict__ x0,
                                                               const double* __restrict__ u_prev,
@@ -1059,6 +1167,9 @@ hipError_t prepare_emit_kernels() {
     if (e == hipSuccess) e = seg_opt_in_family<CAND_TABLE>();
     if (e == hipSuccess) e = seg_opt_in_family<CAND_RAMP_HOLD>();
     if (e == hipSuccess) e = seg_opt_in_family<CAND_TRACK>();
+    if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<false, 4>);
+    if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<false, 0>);
+    if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<true, 0>);
     return e;
 }
 
@@ -1081,6 +1192,21 @@ hipError_t launch_emit<double>(const KP& P, int B, int W, const SolveArgs<double
     if (P.cand_mode == CAND_RAMP_HOLD) return launch_emit64<CAND_RAMP_HOLD, false>(P, B, W, A, st);
     if (P.cand_mode == CAND_TRACK) return launch_emit64<CAND_TRACK, false>(P, B, W, A, st);
     return launch_emit64<CAND_TABLE, false>(P, B, W, A, st);
+}
+
+// polish_iters > 0: after emit, on the same stream (igt_api.hip solve_impl).  The kernel's LDS passes 64 KB from N = 63 on: it is
+// asked for once per handle (prepare_emit_kernels), like the emit in pieces'.
+hipError_t launch_polish(const KP& P, int B, int iters, const SolveArgs<double>& A, hipStream_t st) {
+    if (P.dev & (DEV_EXACT64 | DEV_LITERAL)) return hipErrorNotSupported;      // the oracle-order developer kernels
+    const size_t lds = polish_lds_doubles(P.N) * 8;
+#define IGT_LAUNCH_POLISH(HI_, NRK_)                                                                                          \
+    hipLaunchKernelGGL((polish_f64_kernel<HI_, NRK_>), dim3(B), dim3(64), lds, st, P, B, iters, A.x0, A.u_prev, A.kparams, A.flags, \
+                       A.obs, A.cinf, A.status_out, A.cost_out, A.x_out, A.u_out)
+    if (P.hi_order) IGT_LAUNCH_POLISH(true, 0);
+    else if (P.n_rk4 == 4) IGT_LAUNCH_POLISH(false, 4);
+    else IGT_LAUNCH_POLISH(false, 0);
+#undef IGT_LAUNCH_POLISH
+    return hipGetLastError();
 }
 
 template <int CAND, bool HI>

@@ -23,7 +23,7 @@ class igt_params(C.Structure):
                 ('v_min', C.c_double), ('v_max', C.c_double), ('a_min', C.c_double), ('a_max', C.c_double),
                 ('df_max', C.c_double), ('jerk_limit', C.c_double), ('steer_rate_limit', C.c_double),
                 ('ey_lim', C.c_double), ('d_min', C.c_double), ('w_u', C.c_double), ('feas_tol', C.c_double),
-                ('refine_iters', C.c_int32), ('reserved', C.c_int32),
+                ('refine_iters', C.c_int32), ('polish_iters', C.c_int32),
                 ('track_ke', C.c_double), ('track_span', C.c_double), ('track_beta_lim', C.c_double),
                 ('track_env', C.c_double), ('track_vcap', C.c_double)]
 

@@ -39,6 +39,13 @@ class BatchSolver:
             if not hasattr(p, k):
                 raise TypeError(f'unknown parameter {k!r}')
             setattr(p, k, v)
+        # polish of the winner (igtmpc.h polish_iters): float64 and the progress cost only -- refused here, before any GPU call
+        if not 0 <= p.polish_iters <= 4:
+            raise ValueError('polish_iters must be in [0, 4]')
+        if p.polish_iters > 0 and dtype != 'f64':
+            raise ValueError("polish_iters > 0 needs dtype='f64' (a forward difference of 1e-4 on a float cost is noise)")
+        if p.polish_iters > 0 and cost_mode != 'progress':
+            raise ValueError("polish_iters > 0 needs cost_mode='progress' (the value-network cost is not polished)")
         self.params = p
         self.device = device
         h = ct.c_void_p()

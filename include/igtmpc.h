@@ -113,7 +113,8 @@ typedef struct igt_params {
     double w_u;              /* 0.05, mpc.py:362 */
     double feas_tol;         /* inequality verdicts are g <= feas_tol; >= 0 */
     int32_t refine_iters;    /* IGT_CAND_RAMP_HOLD / IGT_CAND_TRACK: extra search passes around the winner (0..4) */
-    int32_t reserved;
+    int32_t polish_iters;    /* _f64, IGT_COST_PROGRESS: projected-gradient steps on the winner after the search (0..4);
+                                0 = the best candidate as it is.  See igt_solve_batch_*                                   */
     double track_ke;         /* IGT_CAND_TRACK: lateral-error gain of the steering feedback [1/m]          (0.3)  */
     double track_span;       /* IGT_CAND_TRACK: the G slip-angle offsets span +-track_span [rad]            (0.1)  */
     double track_beta_lim;   /* IGT_CAND_TRACK: |beta_cmd| limit [rad]                                      (0.7)  */
@@ -175,6 +176,17 @@ int igt_set_value_net(igt_handle* h, int32_t n_layers, const int32_t* dims, cons
  *   cost_out[B]  argmin_out[B]  status_out[B]
  *        status 0 <-> is_opt True; 1 <-> no feasible candidate (is_opt False,
  *        mpc.py:402-406): then argmin = -1, cost = +inf, x_out/u_out = NaN.
+ *
+ * polish_iters > 0 (_f64 entries, IGT_COST_PROGRESS; igt_create refuses it with IGT_COST_VALUE_NET, the _f32 entries
+ *       answer IGT_E_INVALID): after the search every solved scenario's winner is improved on the device by up to
+ *       polish_iters steps of: forward-difference gradient of the cost over the 2 N inputs (eps = 1e-4), 64 trial steps
+ *       u + 2^(-m/3) d along d = -gradient scaled so that the longest moves some input by four rate limits, every trial
+ *       clamped step by step to the rate window and the input box and judged by all verdicts; the cheapest feasible trial
+ *       is taken when it is strictly cheaper, else the scenario stops.  x_out, u_out, cost_out are then those of the
+ *       polished plan (x_out its roll-out, the bits igt_rollout_batch_f64 gives for u_out as a table candidate; cost_out
+ *       never above the winner's); argmin_out stays the index of the candidate the polish STARTED from -- u_out is no
+ *       longer that candidate's controls; status_out and unsolved scenarios are untouched.  No host synchronisation, no
+ *       extra workspace: such a solve is captured in a stream graph and overlapped like any other.
  *
  * _f64: double everywhere -- the reference's precision.  The RK4 stages are evaluated in factorised form
  *       (csrc/igt_fast64.h); <= 1e-9 of the float64 oracle on every trajectory (measured ~1e-14).
