@@ -684,6 +684,61 @@ int forecast_impl(igt_handle* h, int32_t B, const T* ego_xyh, const T* opp, cons
 }
 
 template <typename T>
+int forecast_scene_impl(igt_handle* h, int32_t E, const T* x, const T* a_prev, const int32_t* route, const T* plan_x,
+                        const T* plan_u, const int32_t* has_plan, T* obs_xy, T* tv_sv, int mem, void* stream) {
+    if (!h) return fail(IGT_E_INVALID, "null handle");
+    if (E < 0) return fail(IGT_E_INVALID, "E < 0");
+    if (!h->d_routes) return fail(IGT_E_INVALID, "route table not set (igt_set_routes)");
+    if (h->p.n_obs < 1) return fail(IGT_E_INVALID, "the forecast entry needs at least one other vehicle (n_obs >= 1)");
+    if (E == 0) return IGT_OK;
+    if (!x || !a_prev || !route || !obs_xy || !tv_sv) return fail(IGT_E_INVALID, "null buffer");
+    const bool plans = plan_x && plan_u && has_plan;
+    if (!plans && (plan_x || plan_u || has_plan)) return fail(IGT_E_INVALID, "plan_x, plan_u, has_plan go together");
+    const int N = h->p.N;
+    const size_t M = (size_t)h->p.n_obs + 1;         // agents per scene; problem e M + i = agent i of scene e as ego
+    if ((size_t)E > (size_t)0x7fffffff / (M * (M - 1))) return fail(IGT_E_INVALID, "E (n_obs + 1) n_obs exceeds int32");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const size_t n_ag = (size_t)E * M, n_x = n_ag * 7, n_px = n_ag * 7 * (N + 1), n_pu = n_ag * 2 * N;
+    const size_t n_pairs = n_ag * (M - 1), n_out = n_pairs * 2 * (N + 1), n_tv = n_pairs * 2;
+    const T *dx = x, *da = a_prev, *dpx = plan_x, *dpu = plan_u;
+    const int32_t *dr = route, *dhp = has_plan;
+    T *dout = obs_xy, *dtv = tv_sv;
+    if (mem == IGT_MEM_HOST) {
+        T *a0, *a1, *a4, *a5;
+        int32_t *a2, *a3;
+        const auto carve = [&](Arena& ar) {
+            a0 = ar.take<T>(n_x); a1 = ar.take<T>(n_ag); a2 = ar.take<int32_t>(n_ag); a3 = ar.take<int32_t>(n_ag);
+            a4 = ar.take<T>(plans ? n_px : 1); a5 = ar.take<T>(plans ? n_pu : 1);
+            dout = ar.take<T>(n_out); dtv = ar.take<T>(n_tv);
+        };
+        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
+        Arena ar{(char*)h->d_stage, 0};
+        carve(ar);
+        HIPCHK(hipMemcpyAsync(a0, x, n_x * sizeof(T), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(a1, a_prev, n_ag * sizeof(T), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(a2, route, n_ag * 4, hipMemcpyHostToDevice, st));
+        dx = a0; da = a1; dr = a2;
+        if (plans) {
+            HIPCHK(hipMemcpyAsync(a3, has_plan, n_ag * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(a4, plan_x, n_px * sizeof(T), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(a5, plan_u, n_pu * sizeof(T), hipMemcpyHostToDevice, st));
+            dhp = a3; dpx = a4; dpu = a5;
+        }
+    } else if (mem != IGT_MEM_DEVICE) {
+        return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
+    }
+    HIPCHK(igt::launch_forecast_scene<T>(h->kp, E, h->d_routes, h->n_routes, dx, da, dr, plans ? dpx : nullptr,
+                                         plans ? dpu : nullptr, plans ? dhp : nullptr, dout, dtv, st));
+    if (mem == IGT_MEM_HOST) {
+        HIPCHK(hipMemcpyAsync(obs_xy, dout, n_out * sizeof(T), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(tv_sv, dtv, n_tv * sizeof(T), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return IGT_OK;
+}
+
+template <typename T>
 int cartesian_impl(igt_handle* h, int32_t n, int32_t steps, const T* z0, const T* u, T* z_out, int mem, void* stream) {
     if (!h) return fail(IGT_E_INVALID, "null handle");
     if (n < 0 || steps < 0) return fail(IGT_E_INVALID, "negative size");
@@ -1093,6 +1148,16 @@ int igt_forecast_batch_f32(igt_handle* h, int32_t B, const float* ego_xyh, const
                            const int32_t* opp_route, const float* plan_x, const float* plan_u, const int32_t* has_plan,
                            float* obs_xy, float* tv_sv, int mem, void* stream) {
     return forecast_impl<float>(h, B, ego_xyh, opp, opp_a, opp_route, plan_x, plan_u, has_plan, obs_xy, tv_sv, mem, stream);
+}
+int igt_forecast_scene_f32(igt_handle* h, int32_t E, const float* x, const float* a_prev, const int32_t* route,
+                           const float* plan_x, const float* plan_u, const int32_t* has_plan, float* obs_xy, float* tv_sv,
+                           int mem, void* stream) {
+    return forecast_scene_impl<float>(h, E, x, a_prev, route, plan_x, plan_u, has_plan, obs_xy, tv_sv, mem, stream);
+}
+int igt_forecast_scene_f64(igt_handle* h, int32_t E, const double* x, const double* a_prev, const int32_t* route,
+                           const double* plan_x, const double* plan_u, const int32_t* has_plan, double* obs_xy, double* tv_sv,
+                           int mem, void* stream) {
+    return forecast_scene_impl<double>(h, E, x, a_prev, route, plan_x, plan_u, has_plan, obs_xy, tv_sv, mem, stream);
 }
 int igt_forecast_batch_f64(igt_handle* h, int32_t B, const double* ego_xyh, const double* opp, const double* opp_a,
                            const int32_t* opp_route, const double* plan_x, const double* plan_u, const int32_t* has_plan,

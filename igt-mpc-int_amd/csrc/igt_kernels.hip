@@ -527,6 +527,87 @@ __global__ __launch_bounds__(256) void forecast_kernel(KP P, int B, const double
         for (int k = 0; k <= N; ++k) { ox[k] = (T)-20; oy[k] = (T)-20; }
 }
 
+// Forecast of a whole scene, scene-major (igt_forecast_scene_*): one lane per (scene e, agent j).  The lane forecasts agent j
+// ONCE -- the arithmetic of forecast_kernel above, statement for statement, through the same frenet2global_dev / sincos_t, so
+// every number equals that kernel's on the gathered inputs bit for bit -- and stores each point into the row of every ego
+// i != j of the scene: problem e M + i, opponent slot j - (j > i) (ascending j, the order filter_preds(preds, i) leaves,
+// utils.py:365-388), or (-20, -20) where agent j is behind that ego.  The filter needs only agent j's first point, which is
+// known before the roll, so there is one pass over k and nothing is read back.  The M egos' (x, y, heading) come from the
+// scene's own rows of x; nothing is gathered.
+template <typename T, int M>
+__global__ __launch_bounds__(256) void forecast_scene_kernel(KP P, int n_agents, const double* __restrict__ routes, int n_routes,
+                                                             const T* __restrict__ x, const T* __restrict__ a_prev,
+                                                             const int32_t* __restrict__ route,
+                                                             const T* __restrict__ plan_x, const T* __restrict__ plan_u,
+                                                             const int32_t* __restrict__ has_plan, T* __restrict__ obs_xy,
+                                                             T* __restrict__ tv_sv) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;      // agent row e M + j
+    if (b >= n_agents) return;
+    const int e = b / M, j = b - e * M;
+    const int N = P.N;
+    const T dt = (T)P.dt;
+    int rid = route[b];
+    rid = rid < 0 ? 0 : (rid >= n_routes ? n_routes - 1 : rid);
+    const double* __restrict__ r = routes + (size_t)rid * 12;
+    const T* xj = x + (size_t)b * 7;
+    const bool shared = plan_x && has_plan && has_plan[b] != 0;
+    const T* px = shared ? plan_x + (size_t)b * 7 * (N + 1) : nullptr;
+    const T x0 = shared ? px[0 * (N + 1) + 1] : xj[0], y0 = shared ? px[1 * (N + 1) + 1] : xj[1];
+    // filter_preds per ego (utils.py:365-388) and the ego's rows: slot q = 0..M-2 is ego i = q + (q >= j)
+    T* ox[M - 1];
+    T* tv[M - 1];
+    bool behind[M - 1];
+#pragma unroll
+    for (int q = 0; q < M - 1; ++q) {
+        const int i = q + (q >= j ? 1 : 0);
+        const T* xi = x + ((size_t)e * M + i) * 7;
+        T sh, ch;
+        sincos_t<T>(xi[6], &sh, &ch);
+        const T dot = (x0 - xi[0]) * ch + (y0 - xi[1]) * sh;
+        behind[q] = dot < 0;
+        const size_t pair = ((size_t)e * M + i) * (M - 1) + (size_t)(j - (j > i ? 1 : 0));
+        ox[q] = obs_xy + pair * 2 * (N + 1);
+        tv[q] = tv_sv + pair * 2;
+    }
+    const auto put = [&](int k, T xk, T yk) {
+#pragma unroll
+        for (int q = 0; q < M - 1; ++q) {
+            ox[q][k] = behind[q] ? (T)-20 : xk;
+            ox[q][N + 1 + k] = behind[q] ? (T)-20 : yk;
+        }
+    };
+    T sl, vl;
+    if (shared) {
+        // utils.py:339-352: plan states k = 1..N, then one predicted step from the plan's last state
+        for (int k = 0; k < N; ++k) put(k, px[0 * (N + 1) + k + 1], px[1 * (N + 1) + k + 1]);
+        T s = px[2 * (N + 1) + N], v = px[5 * (N + 1) + N];
+        T a = plan_u[(size_t)b * 2 * N + (N - 1)];
+        T vn = fmin(fmax(v + a * dt, (T)-2), (T)20);                       // cam:71
+        if (vn > (T)5) { a = 0; vn = fmin(fmax(v, (T)-2), (T)20); }         // utils.py:348-349
+        s = s + (v * dt + (T)0.5 * a * dt * dt);                           // cam:70
+        T xe, ye;
+        frenet2global_dev<T>(r, s, xe, ye);
+        put(N, xe, ye);
+        sl = s; vl = vn;
+    } else {
+        T s = xj[2], v = xj[5];
+        const T a = a_prev[b];
+        put(0, x0, y0);                                                    // cam:40: k = 0 is the true state
+        for (int k = 1; k <= N; ++k) {
+            s = s + (v * dt + (T)0.5 * a * dt * dt);                       // cam:70
+            v = fmin(fmax(v + a * dt, (T)-2), (T)20);                      // cam:71 (fourwayint.yaml:23-24)
+            T xk, yk;
+            frenet2global_dev<T>(r, s, xk, yk);                            // cam:75
+            put(k, xk, yk);
+        }
+        sl = s; vl = v;
+    }
+#pragma unroll
+    for (int q = 0; q < M - 1; ++q) {       // last raw prediction of agent j, in every ego's row (mpc.py:263-276 raw_preds)
+        tv[q][0] = sl; tv[q][1] = vl;
+    }
+}
+
 // float path of igt_frenet_step_f32: one control step through the same pair arithmetic the solver uses
 template <bool HI>
 __global__ __launch_bounds__(256) void frenet_step_fast_kernel(KP P, int n, const float* __restrict__ x,
@@ -851,6 +932,29 @@ hipError_t launch_forecast(const KP& P, int B, const double* routes, int n_route
                        opp_a, opp_route, plan_x, plan_u, has_plan, obs_xy, tv_sv);
     return hipGetLastError();
 }
+template <typename T>
+hipError_t launch_forecast_scene(const KP& P, int E, const double* routes, int n_routes, const T* x, const T* a_prev,
+                                 const int32_t* route, const T* plan_x, const T* plan_u, const int32_t* has_plan, T* obs_xy,
+                                 T* tv_sv, hipStream_t st) {
+    const int M = P.n_obs + 1, n = E * M;       // one lane per agent of every scene
+    const dim3 grid((n + 255) / 256), block(256);
+#define IGT_SCENE(m)                                                                                                       \
+    case m:                                                                                                                \
+        hipLaunchKernelGGL((forecast_scene_kernel<T, m>), grid, block, 0, st, P, n, routes, n_routes, x, a_prev, route,    \
+                           plan_x, plan_u, has_plan, obs_xy, tv_sv);                                                       \
+        break;
+    switch (M) {
+        IGT_SCENE(2) IGT_SCENE(3) IGT_SCENE(4) IGT_SCENE(5)
+        default: return hipErrorInvalidValue;
+    }
+#undef IGT_SCENE
+    return hipGetLastError();
+}
+template hipError_t launch_forecast_scene<float>(const KP&, int, const double*, int, const float*, const float*, const int32_t*,
+                                                 const float*, const float*, const int32_t*, float*, float*, hipStream_t);
+template hipError_t launch_forecast_scene<double>(const KP&, int, const double*, int, const double*, const double*,
+                                                  const int32_t*, const double*, const double*, const int32_t*, double*, double*,
+                                                  hipStream_t);
 template hipError_t launch_forecast<float>(const KP&, int, const double*, int, const float*, const float*, const float*,
                                            const int32_t*, const float*, const float*, const int32_t*, float*, float*,
                                            hipStream_t);

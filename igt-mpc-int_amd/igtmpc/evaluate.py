@@ -1,5 +1,5 @@
 """Closed-loop driver: the time loop of the reference's evaluate.py (mpc branch 451-564, gt_mpc
-branch 193-330) for E episodes in lock-step, every (episode, agent) problem of a timestep solved
+branch 193-330) for E episodes of M = 2..4 agents in lock-step, every (episode, agent) problem of a timestep solved
 in ONE batched call on the GPU (the reference's agents of a timestep all read the same
 predictions -- a Jacobi update, evaluate.py:469-558 -- so batching changes nothing).
 
@@ -34,11 +34,14 @@ A_MIN_POLICY = -4.0        # mpc.yaml:8, used by the brake fallback (evaluate.py
 
 def initial_states(rng, route_pairs, v0=0.0):
     """evaluate.py:91-94 + 404-418: every episode draws one offset per approach lane (order 1,2,3,4);
-    an agent starting at origin o sits `offset_o` metres down its lane with v = 0, ey = epsi = 0."""
+    an agent starting at origin o sits `offset_o` metres down its lane with v = 0, ey = epsi = 0.
+    route_pairs: one tuple of M = 2..4 routes per episode (the same M for all; the draw does not depend on M)."""
     E = len(route_pairs)
     max_start = (R.ROAD_LENGTH - R.ROAD_WIDTH) / 2 - (R.ROAD_WIDTH - R.CA_RADIUS)      # evaluate.py:48-49
     off = rng.random((E, 4)) * max_start
-    M = 2
+    M = len(route_pairs[0]) if E else 2
+    if any(len(p) != M for p in route_pairs):
+        raise ValueError('every episode needs the same number of routes')
     x = np.zeros((E, M, 7))
     rid = np.zeros((E, M), dtype=np.int64)
     for e, pair in enumerate(route_pairs):
@@ -66,7 +69,7 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
                     dtype='f64', rotation=None, cand_mode='track', refine_iters=0, verbose=False,
                     eval_mode='mpc', value_net=None, device_resident=False, warm_start=None, init=None,
                     terminal_set=True, feas_tol=None, limits=None, graph=False, a_min_policy=None, constant_speed=False,
-                    v0=0.0, polish_iters=0):
+                    v0=0.0, polish_iters=0, num_agents=2):
     """eval_mode 'mpc' (evaluate.py:370-639) or 'gt_mpc' (123-369: terminal value network in the cost;
     value_net = dict(layers=[(W,b),...][, Wn, mu_f, sigma_t, mu_t]), default: the network the reference ships for
     scenario sc -- its normalisation statistics are not shipped, identity unless given).  device_resident=True keeps every per-step array in HBM (torch tensors;
@@ -85,7 +88,17 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     a_min_policy: deceleration of the brake fallback (mpc.yaml:8 a_min through evaluate.py:514; default -4);
     constant_speed: the forecast holds the other agent's speed (mpc.yaml:13-14 prediction_type, evaluate.py:76-79);
     v0: initial speed (fourwayint.yaml:11) -- load_reference_configs reads all three from the reference's files.
-    polish_iters (f64, eval_mode 'mpc'): projected-gradient steps on every solved problem's winner (igtmpc.h polish_iters)."""
+    polish_iters (f64, eval_mode 'mpc'): projected-gradient steps on every solved problem's winner (igtmpc.h polish_iters).
+    num_agents = M in 2..4 (evaluate.py:46; four approach lanes): every step solves E M problems with n_obs = M - 1 -- each
+    agent against the forecast / shared plan of every other one (Jacobi, evaluate.py:469-558).  Scenario `sc`'s route tuples for
+    M > 2: routes.scene_routes; init = (x[E,M,7], route tuples of length M).  eval_mode 'mpc' only beyond two (the value
+    network's features are those of a two-vehicle scene, mpc.py:326-338)."""
+    M = int(num_agents)
+    if not 2 <= M <= 4:
+        raise ValueError(f'num_agents = {num_agents}: a scene has 2, 3 or 4 vehicles (one per approach lane)')
+    if eval_mode == 'gt_mpc' and M > 2:
+        raise ValueError("eval_mode='gt_mpc' needs num_agents = 2: the value network's features are those of a two-vehicle "
+                         'scene (mpc.py:326-338)')
     a_min_policy = A_MIN_POLICY if a_min_policy is None else float(a_min_policy)
     gt = eval_mode == 'gt_mpc'
     if gt and value_net is None:
@@ -93,15 +106,21 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
             raise ValueError("eval_mode='gt_mpc' with init= needs value_net (the shipped networks are per scenario)")
         value_net = shipped_value_net(sc)                               # sc{n}_config.yaml:2 model_path
     rng = np.random.default_rng(seed)                                   # evaluate.py:35, 56
-    M = 2
     M_sim = int(round(T_sim / dt))                                      # evaluate.py:83-84
     if init is not None:
         x, pairs = np.array(init[0], dtype=np.float64), [tuple(p) for p in init[1]]
         E = num_samples = len(pairs)
+        if x.shape != (E, M, 7) or any(len(p) != M for p in pairs):
+            raise ValueError(f'init must be (x[E,{M},7], E route tuples of length {M}) for num_agents = {M}; got x{x.shape} and '
+                             f'tuples of length {sorted({len(p) for p in pairs})}')
         rid = np.array([[R.ROUTE_ID[r] for r in p] for p in pairs], dtype=np.int64)
     else:
         E = num_samples
-        pairs = [R.SCENARIO_ROUTES[sc - 1][(e if rotation is None else rotation) % 4] for e in range(E)]
+        pairs = [R.scene_routes(sc, e if rotation is None else rotation, M) for e in range(E)]
+    for p in pairs:
+        if len({r[0] for r in p}) != len(p):                            # evaluate.py:96: lanes are drawn without replacement
+            raise ValueError(f'routes {p}: two agents of a scene start from the same approach lane')
+    if init is None:
         x, rid = initial_states(rng, pairs, v0=v0)                      # x[E,M,7]
     warm = (cand_mode == 'ramp_hold') if warm_start is None else (bool(warm_start) and cand_mode in ('ramp_hold', 'track'))
     limits = dict(limits or {})
@@ -149,21 +168,16 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     sol_u = np.zeros((E, M, 2, N))
 
     for t in range(M_sim):
-        # --- forecast of the other agent for every (episode, ego) problem, on the device:
+        # --- forecast of every other agent for every (episode, ego) problem, on the device, from the scene as it lies:
         #     predict (evaluate.py:455) -> share motion forecasts (458-460) -> filter_preds (474)
-        other = slice(None, None, -1)
-        ego_xyh = x[:, :, [0, 1, 6]].reshape(E * M, 3)
-        opp = x[:, other][:, :, [0, 1, 2, 5]].reshape(E * M, 4)
-        a_fc = u_prev[:, other, 0]
+        a_fc = u_prev[:, :, 0]
         if gt and t == 0:                                               # evaluate.py:207-210: a = 0.09 (k+1) for agent k
-            a_fc = np.tile(0.09 * (np.arange(M)[::-1] + 1.0), (E, 1))
+            a_fc = np.tile(0.09 * (np.arange(M) + 1.0), (E, 1))
         if constant_speed:                                              # constant_acceleration_model.py:26-29
             a_fc = np.zeros((E, M))
-        obs, tv = solver.forecast(ego_xyh.astype(npdt), opp.astype(npdt), a_fc.reshape(-1).astype(npdt),
-                                   rid[:, other].reshape(-1).astype(np.int32),
-                                   sol_x[:, other].reshape(E * M, 7, N + 1).astype(npdt),
-                                   sol_u[:, other].reshape(E * M, 2, N).astype(npdt),
-                                   (have_sol[:, other] & (t > 0)).reshape(-1).astype(np.int32))
+        obs, tv = solver.forecast_scene(x.astype(npdt), a_fc.astype(npdt), rid.astype(np.int32), sol_x.astype(npdt),
+                                         sol_u.astype(npdt), (have_sol & (t > 0)).astype(np.int32))
+        tv = tv.reshape(E * M, -1)                                      # (read by the gt_mpc cost only: M = 2, [E M, 2])
         # --- solve every (episode, agent) problem at once (evaluate.py:470-482); an agent that solved the previous
         #     step passes that solution, shifted by one step, as its warm start (evaluate.py:478-481)
         t0 = time.perf_counter()
@@ -228,7 +242,7 @@ def _loop_device(solver, stepper, x, u_prev, kp, flags, rid, enc, gt, E, M, N, M
     kp_s = kp.reshape(E * M, 3).to(td).contiguous()
     kp_d = kp.reshape(E * M, 3).contiguous()
     flags_t = torch.as_tensor(flags.astype(np.int32), device=dev)
-    rid_o = torch.as_tensor(rid[:, ::-1].reshape(-1).astype(np.int32), device=dev)
+    rid_t = torch.as_tensor(rid.astype(np.int32), device=dev)
     enc_t = T(enc, td) if gt else None
     x_data = torch.zeros((E, 7 * M, M_sim + 1), dtype=torch.float64, device=dev)
     u_data = torch.zeros((E, 2 * M, M_sim), dtype=torch.float64, device=dev)
@@ -237,22 +251,17 @@ def _loop_device(solver, stepper, x, u_prev, kp, flags, rid, enc, gt, E, M, N, M
     have_sol = torch.zeros((E, M), dtype=torch.bool, device=dev)
     sol_x = torch.zeros((E, M, 7, N + 1), dtype=td, device=dev)
     sol_u = torch.zeros((E, M, 2, N), dtype=td, device=dev)
-    ix = torch.tensor([0, 1, 6], device=dev)
-    io = torch.tensor([0, 1, 2, 5], device=dev)
     col = torch.zeros(1, dtype=torch.int64, device=dev)            # the step the next call of step() computes
-    a_fc0 = torch.as_tensor(0.09 * (np.arange(M)[::-1] + 1.0), device=dev).expand(E, M) if gt else None
+    a_fc0 = torch.as_tensor(0.09 * (np.arange(M) + 1.0), device=dev).expand(E, M) if gt else None
 
     def step(first, warm_ok=True):
-        xo, uo = x.flip(1), u_prev.flip(1)
-        a_fc = a_fc0 if (gt and first) else uo[..., 0]
+        # the forecast reads the scene where it lies (igt_forecast_scene_*): no gathered copy of any agent's state or plan
+        a_fc = a_fc0 if (gt and first) else u_prev[..., 0]
         if constant_speed:
-            a_fc = torch.zeros_like(uo[..., 0])
-        hp = (have_sol.flip(1) & (not first)).reshape(-1).to(torch.int32).contiguous()
-        obs, tv = solver.forecast(x.index_select(2, ix).reshape(E * M, 3).to(td).contiguous(),
-                                  xo.index_select(2, io).reshape(E * M, 4).to(td).contiguous(),
-                                  a_fc.reshape(-1).to(td).contiguous(), rid_o,
-                                  sol_x.flip(1).reshape(E * M, 7, N + 1).contiguous(),
-                                  sol_u.flip(1).reshape(E * M, 2, N).contiguous(), hp)
+            a_fc = torch.zeros_like(u_prev[..., 0])
+        hp = (have_sol & (not first)).to(torch.int32)
+        obs, tv = solver.forecast_scene(x.to(td), a_fc.to(td).contiguous(), rid_t, sol_x, sol_u, hp)
+        tv = tv.reshape(E * M, -1)
         fl, u_ws = flags_t, None
         if warm and not first and warm_ok:
             fl = flags_t | (have_sol.reshape(-1).to(torch.int32) * IGT_FLAG_WARM)
@@ -438,6 +447,7 @@ def main():
     ap = argparse.ArgumentParser(description='batched closed-loop evaluation (counterpart of evaluate.py --eval_mode mpc)')
     ap.add_argument('--sc', type=int, default=1)
     ap.add_argument('--num_samples', type=int, default=1)
+    ap.add_argument('--num_agents', type=int, default=2, help='vehicles per scene, 2..4 (fourwayint.yaml:7 num_agents; mpc only beyond 2)')
     ap.add_argument('--N', type=int, default=None, help='horizon; default: the policy file\'s, else 40 (mpc.yaml:6; BASELINE.json benchmarks 20)')
     ap.add_argument('--policy_config', default=None, help="the reference's mpc.yaml (evaluate.py:32)")
     ap.add_argument('--env_config', default=None, help="the reference's common/fourwayint.yaml (evaluate.py:28)")
@@ -471,7 +481,7 @@ def main():
     a.N = kw['N']
     r = run_closed_loop(sc=a.sc, num_samples=a.num_samples, C=a.C, verbose=a.verbose, eval_mode=a.eval_mode,
                         value_net=net, device_resident=a.device_resident, cand_mode=a.cand_mode, dtype=a.dtype, graph=a.graph,
-                        polish_iters=a.polish_iters, **kw)
+                        polish_iters=a.polish_iters, num_agents=a.num_agents, **kw)
     if a.save_dir is not None:
         policy = {'type': 'MPC', 'N': a.N, 'dt': kw.get('dt', 0.1), 'a_min': -4, 'a_max': 3, 'v_min': -1.0, 'v_max': 5,      # mpc.yaml's keys
                   'prediction_type': 'constant_acceleration', 'collision_avoidance_type': 'circle', **policy_file, 'N': a.N,

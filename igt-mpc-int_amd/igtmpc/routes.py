@@ -37,6 +37,25 @@ SCENARIO_ROUTES = [
     [('12', '31'), ('23', '42'), ('13', '34'), ('24', '41')],
 ]
 
+
+def scene_routes(sc, k, num_agents=2):
+    """Route tuple k (mod 4) of scenario `sc` (1..8) for a scene of `num_agents` vehicles.  Two: SCENARIO_ROUTES as it is.
+    More: the reference's rule for any M (evaluate.py:91-101) -- approach lanes drawn WITHOUT replacement out of the four,
+    a goal per lane out of the route table -- made deterministic, as the pairs are: the scenario's pair keeps agents 0 and 1,
+    every further agent takes the lowest-numbered approach lane no agent of the scene starts from and drives straight through
+    (STRAIGHT: '13', '24', '31', '42'), so that it crosses the conflict zone the pair defines."""
+    pair = SCENARIO_ROUTES[sc - 1][k % 4]
+    if not 2 <= num_agents <= 4:
+        raise ValueError('num_agents must be 2, 3 or 4 (four approach lanes)')
+    out = list(pair)
+    for lane in '1234':
+        if len(out) == num_agents:
+            break
+        if all(r[0] != lane for r in out):
+            out.append(next(r for r in STRAIGHT if r[0] == lane))
+    return tuple(out)
+
+
 with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'route_constants.json')) as _f:
     CONSTANTS = json.load(_f)
 

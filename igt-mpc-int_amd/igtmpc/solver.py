@@ -57,6 +57,7 @@ class BatchSolver:
         self._cart = getattr(self.lib, f'igt_cartesian_euler_{dtype}')
         self._fstep = getattr(self.lib, f'igt_frenet_step_{dtype}')
         self._fcast = getattr(self.lib, f'igt_forecast_batch_{dtype}')
+        self._fscene = getattr(self.lib, f'igt_forecast_scene_{dtype}')
         self._routes_set = False
 
     def _check(self, rc):
@@ -271,6 +272,29 @@ class BatchSolver:
         dts = [dt, dt, dt, np.int32, dt, dt, np.int32, dt, dt]
         mode, ptrs, keep = self._prep(arrs, shapes, dts)
         self._check(self._fcast(self._h, B, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        return obs, tv
+
+    def forecast_scene(self, x, a_prev, route, plan_x=None, plan_u=None, has_plan=None, stream=None):
+        """forecast() for E whole scenes of M = n_obs + 1 agents, scene-major, nothing gathered (igt_forecast_scene_*):
+        x[E,M,7] (planner state order), a_prev[E,M], route[E,M], plan_x[E,M,7,N+1], plan_u[E,M,2,N], has_plan[E,M]
+        -> (obs_xy[E M,n_obs,2,N+1], tv_sv[E M,n_obs,2]) -- problem e M + i is agent i of scene e as ego, its opponents the
+        other agents in ascending order.  Each agent is forecast once and filtered per ego; equals forecast() on the gathered
+        inputs bit for bit."""
+        if not self._routes_set:
+            self.set_routes()
+        E, N, M = int(x.shape[0]), self.N, self.n_obs + 1
+        dt = self.np_dtype
+        if _is_torch(x):
+            import torch
+            obs = torch.empty((E * M, M - 1, 2, N + 1), dtype=x.dtype, device=x.device)
+            tv = torch.empty((E * M, M - 1, 2), dtype=x.dtype, device=x.device)
+        else:
+            obs, tv = np.empty((E * M, M - 1, 2, N + 1), dt), np.empty((E * M, M - 1, 2), dt)
+        arrs = [x, a_prev, route, plan_x, plan_u, has_plan, obs, tv]
+        shapes = [(E, M, 7), (E, M), (E, M), (E, M, 7, N + 1), (E, M, 2, N), (E, M), tuple(obs.shape), tuple(tv.shape)]
+        dts = [dt, dt, np.int32, dt, dt, np.int32, dt, dt]
+        mode, ptrs, keep = self._prep(arrs, shapes, dts)
+        self._check(self._fscene(self._h, E, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
         return obs, tv
 
     def frenet_step(self, x, u, kparams, stream=None):

@@ -282,6 +282,24 @@ int igt_forecast_batch_f64(igt_handle* h, int32_t B, const double* ego_xyh, cons
                            const int32_t* opp_route, const double* plan_x, const double* plan_u,
                            const int32_t* has_plan, double* obs_xy, double* tv_sv, int mem, void* stream);
 
+/* The same forecast for E whole scenes, scene-major: one row per AGENT, nothing gathered.  M = n_obs + 1 agents per scene
+ * (2 .. IGT_MAX_OBS + 1); problem e M + i is agent i of scene e as ego, and its opponents are the agents j != i of the scene
+ * in ascending j -- the order filter_preds(preds, i) leaves (utils.py:365-388); with M = 2 "the other one".  Every agent is
+ * forecast (or its shared plan shifted) ONCE per scene and filtered per ego; the outputs are what igt_solve_batch_* reads for
+ * the E M problems and equal igt_forecast_batch_* on the gathered inputs bit for bit (same device arithmetic).
+ *   x [E,M,7] planner state order          a_prev [E,M] last applied a          route [E,M] row of the igt_set_routes table
+ *   plan_x [E,M,7,N+1], plan_u [E,M,2,N], has_plan [E,M] (int32, 0 = no shared plan)  -- all three may be NULL
+ *   obs_xy [E M,n_obs,2,N+1] (out)         tv_sv [E M,n_obs,2] (out)
+ * IGT_MEM_DEVICE: one kernel enqueued on `stream`, no allocation, no host synchronisation (capturable).  IGT_E_INVALID for
+ * E < 0, a handle without routes or with n_obs = 0.  (Added without a change of IGT_VERSION: nothing existing changed; a
+ * caller that must run against an older library probes the symbol.) */
+int igt_forecast_scene_f32(igt_handle* h, int32_t E, const float* x, const float* a_prev, const int32_t* route,
+                           const float* plan_x, const float* plan_u, const int32_t* has_plan, float* obs_xy, float* tv_sv,
+                           int mem, void* stream);
+int igt_forecast_scene_f64(igt_handle* h, int32_t E, const double* x, const double* a_prev, const int32_t* route,
+                           const double* plan_x, const double* plan_u, const int32_t* has_plan, double* obs_xy, double* tv_sv,
+                           int mem, void* stream);
+
 /* 4-state Cartesian forward-Euler bicycle (kinematic_bicycle_model.py:15-50), the
  * model ReferenceGen.py steps to lay out reference paths.
  *   z0 [n,4] = (x, y, psi, v)   u [n,2,T] (a, df)   z_out [n,4,T+1] */
