@@ -694,14 +694,19 @@ __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>&
 // The arg-min: the candidates that finish feasible in an iteration are reduced together with the wave's best on (Jq, c), ties
 // to the lowest index -- a total order, so the winner does not depend on the order the pool is worked in.  With checkpoint slots
 // (ck: the lane's column of the LDS records, SEGMODE 1) the new winner's lane copies its records to `rec` (15 doubles).
-// cand_of(g, col): candidate number g of the scenario -> candidate index, and its steering column's rank in the table.
 // start: POOL_START doubles of LDS for what a refill reads of the scenario (read there when a lane refills instead of held in
 // registers over the whole loop: the kernel is at its 256 registers).
-constexpr int POOL_START = 13;
-template <int CAND, bool HI_ORDER, int NRK, bool XY, class CandOf>
-__device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>& S, int n, const CandOf& cand_of,
+// tabw, tabda: POOL_TAB entries of LDS each -- what a refill needs that depends on the candidate number alone, for a window of
+// POOL_TAB numbers: the candidate index and its column rank in one word (index | rank << 16), and da.  fill(base) has the
+// wave lay out the window that starts at number `base` (igt_kernels_f64.hip search_pool64); it is called when the cursor first
+// reaches past the window (once per item when n <= POOL_TAB, i.e. C <= 256), with the values a refill used to compute on the
+// spot, so the same bits -- and a refill is a wave-uniform branch around a few LDS reads.
+constexpr int POOL_START = 13, POOL_TAB = 256;
+template <int CAND, bool HI_ORDER, int NRK, bool XY, class Fill>
+__device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>& S, int n, const Fill& fill,
                                              const double* __restrict__ cinf, const double* __restrict__ stab, int stab_stride,
-                                             double* ck, double* rec, double* start, double& wJ, int& wC) {
+                                             double* ck, double* rec, double* start, unsigned* tabw, double* tabda,
+                                             double& wJ, int& wC) {
     static_assert(CAND == CAND_LATTICE, "pool roll-out: the lattice family (its steering is a column of the table)");
     constexpr int CKF = 5;
     typedef Fast64<HI_ORDER, NRK> FP;
@@ -730,26 +735,36 @@ __device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>
     const double* lstab = stab;
     bool hold = false;
     int next = 0;                                   // the pool's cursor (wave-uniform)
+    int tab_end = 0;                                // the table holds the numbers [tab_end - POOL_TAB, tab_end): none yet
     wJ = 0.0; wC = -1;
     for (;;) {
-        // ---- idle lanes take the next numbers
+        // ---- idle lanes take the next numbers (a branch the whole wave takes or skips: most iterations refill nothing)
         const unsigned long long want = __ballot(!hold);
         if (want != 0ull && next < n) {
+            // the body stays behind the wave's branch, not if-converted into the iteration.  What holds it there is visible in the
+            // ISA only (profiles/r07_pool_loop_isa.txt): an s_cbranch_vccnz around the refill, no f64 division inside the loop
+            __builtin_amdgcn_sched_barrier(0);
+            const int cnt = __popcll(want);
+            if (next + cnt > tab_end && tab_end < n) {           // the numbers handed out now reach past the window: next one
+                tab_end = next + POOL_TAB;
+                fill(next);
+            }
             const int g = next + __popcll(want & below);
             if (!hold && g < n) {
-                int col;
-                c = cand_of(g, col);
-                lstab = stab + col * 3;
+                const int e = g - (tab_end - POOL_TAB);
+                const unsigned w = tabw[e];
+                L.da = tabda[e];
+                c = (int)(w & 0xffffu);
+                lstab = stab + (w >> 16) * 3;
                 L.x = start[0]; L.y = start[1]; L.s = start[2]; L.ey = start[3]; L.ep = start[4]; L.v = start[5];
                 L.a = start[7]; L.df = start[8]; L.J = 0.0; L.gmax = -1.0e300; L.viol = 0u;
-                cand_increments<CAND>(P, S, c, L.da, L.ddf);
                 L.w.d0 = L.w.d1 = 0.0;
                 L.w.s1 = start[9]; L.w.c1 = start[10]; L.w.s2 = start[11]; L.w.c2 = start[12];
                 L.cb_prev = 1.0; L.sb_prev = 0.0;
                 L.ck_q = 1; L.ck_k = ck ? ckpt_step(P.N, 1) : -1;
                 k = 0; hold = true;
             }
-            next += __popcll(want);
+            next += cnt;
         }
         if (__ballot(hold) == 0ull) break;
         // ---- control step k for every lane that holds a candidate; it retires a candidate that failed a verdict of state k,
@@ -773,7 +788,9 @@ __device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>
             }
         }
         // ---- feasible candidates that finished: reduced with the wave's best (the units' butterfly and tie rule)
-        if (__ballot(fin) != 0ull) {
+        // only when one of them can replace the wave's best: the order on (Jq, c) is total, so the minimum over the finishers
+        // beats (wJ, wC) exactly when some finisher does -- same winner, same lane copying its records
+        if (__ballot(fin && (wC < 0 || Jq < wJ || (Jq == wJ && c < wC))) != 0ull) {
             double bJ = Jq;
             int bC = fin ? c : -1;
 #pragma unroll

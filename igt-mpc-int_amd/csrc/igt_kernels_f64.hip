@@ -437,13 +437,15 @@ __device__ __forceinline__ void search_pool64(const KP& P, int W, int b, const d
                                               double* __restrict__ ck_all) {
     const int lane = threadIdx.x & 63;
     const UnitLayout L = unit_layout(P, W, CAND, row_mask[b]);
-    const int R = __builtin_amdgcn_readfirstlane(L.R), n = P.G * R, lg = __ffs(P.G) - 1;
+    const int R = __builtin_amdgcn_readfirstlane(L.R), n = P.G * R;
     constexpr int CKF = 5;
     __shared__ int rank2row[64];
     __shared__ double stab[f64::STAB_MAX_ENTRIES * 3];
     __shared__ double ckl[(f64::CK_PARTS - 1) * CKF * 64];
     __shared__ double rec[(f64::CK_PARTS - 1) * CKF];
     __shared__ double start[f64::POOL_START];
+    __shared__ unsigned tabw[f64::POOL_TAB];
+    __shared__ double tabda[f64::POOL_TAB];
     double wJ = 0.0;
     int wC = -1;
     if (n > 0) {
@@ -451,16 +453,28 @@ __device__ __forceinline__ void search_pool64(const KP& P, int W, int b, const d
         load_scenario<double>(S, P, b, x0, u_prev, kparams, flags, obs, cpar);
         rows_by_rank(L, lane, rank2row);
         f64::fill_steer_table<CAND>(P, S, P.G, 0, lane, P.lr_ratio, stab);
-        auto cand_of = [&](int g, int& col) {
-            const int r = small_div(g, R), rank = g - r * R;
-            const int j = (r & 1) ? P.G / 2 - 1 - (r >> 1) : P.G / 2 + (r >> 1);      // unit_candidate's column order
-            col = r;
-            return (rank2row[rank] << lg) + j;
+        // the window of the refill table that starts at candidate number `base`: unit_candidate's numbering, cand_increments' da.
+        // What it derives from R and G is derived here, behind the refill's branch, not held in registers over the control steps:
+        // the empty asm makes the two opaque there.  The ISA is the check (profiles/r07_pool_loop_isa.txt): the reciprocal of R and
+        // the division by G - 1 sit in the fill's block, not before the loop.  The word holds the candidate index in its low 16 bits
+        // and the column rank above: C = G G <= 4096 and rank < G <= 64 (igt_api.hip validate: G divides 64).
+        auto fill = [&](int base) {
+            int Rf = R, Gf = P.G;
+            asm volatile("" : "+s"(Rf), "+s"(Gf));
+            const int lgf = __ffs(Gf) - 1;
+            for (int e = lane; e < f64::POOL_TAB && base + e < n; e += 64) {
+                const int g = base + e, r = small_div(g, Rf), rank = g - r * Rf;
+                const int j = (r & 1) ? Gf / 2 - 1 - (r >> 1) : Gf / 2 + (r >> 1);    // unit_candidate's column order
+                const int row = rank2row[rank];
+                tabw[e] = (unsigned)((row << lgf) + j) | ((unsigned)r << 16);
+                tabda[e] = -P.rate_a + (2 * P.rate_a) * (double)row / (double)(Gf - 1);   // cand_increments: i = c / G = row
+            }
+            __syncthreads();
         };
         const bool far = !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
         double* ck = ck_all ? ckl + lane : nullptr;
-        if (far) f64::rollout_pool<CAND, HI, NRK, false>(P, S, n, cand_of, cinf, stab, P.G * 3, ck, rec, start, wJ, wC);
-        else f64::rollout_pool<CAND, HI, NRK, true>(P, S, n, cand_of, cinf, stab, P.G * 3, ck, rec, start, wJ, wC);
+        if (far) f64::rollout_pool<CAND, HI, NRK, false>(P, S, n, fill, cinf, stab, P.G * 3, ck, rec, start, tabw, tabda, wJ, wC);
+        else f64::rollout_pool<CAND, HI, NRK, true>(P, S, n, fill, cinf, stab, P.G * 3, ck, rec, start, tabw, tabda, wJ, wC);
         __syncthreads();                                  // rec is complete; the next item of this wave rewrites the tables
     }
     if (lane < W) {

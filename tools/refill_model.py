@@ -10,6 +10,7 @@ fraction of 4 N per scenario (four 64-candidate units of N steps each).
 A candidate that fails a verdict of state k has rolled k + 1 steps in the pool roll-out (it retires after its step).
 Step counts only: the refill bookkeeping costs instructions on top, and the sub-step votes see lanes at different k.
     python tools/refill_model.py [B] [seed]
+    python tools/refill_model.py --votes [B] [seed]    which sub-step variant each wave-step votes (votes() below)
 """
 import os
 import sys
@@ -70,7 +71,63 @@ def model(B=512, seed=0, N=20, C=256):
                 iterations_with_refill=refill_iters / max(iters, 1))
 
 
+def votes(B=256, seed=0, N=20, C=256):
+    """The sub-step variant a wave votes at every wave-step of the two mappings, with substeps()'s whole-step vote
+    (igt_fast64.h): `clear` -- every busy lane's step stays off the arc, K = 0 throughout; `inside` -- every lane's stays on it,
+    K = k_v; else the per-sub-step fallback.  A unit's lanes vote until the unit leaves (dead lanes roll on); a pool's busy
+    lanes vote each at its own k.  -> shares (clear, inside, fallback) of the wave-steps, for units and pool."""
+    from oracle import np_oracle as O
+    from igtmpc.scenarios import make_batch
+    dead, P = death_steps(B, N, C, seed)
+    G = int(round(C ** 0.5))
+    sc = make_batch(B, N, P.dt, seed=seed, dtype=np.float64)
+    X = O.rollout_frenet(O.apply_flags(sc['x0'], sc['flags'])[:, None, :], O.candidates_lattice(sc['u_prev'], P, C),
+                         sc['kparams'][:, None, :], P)
+    b0, b1, kv = (sc['kparams'][:, i, None, None] for i in range(3))
+    s, v, ey = X[..., O.IS, :N], X[..., O.IV, :N], X[..., O.IEY, :N]
+    a = O.candidates_lattice(sc['u_prev'], P, C)[:, :, 0, :]
+    m = (2 * P.dt) * (np.abs(v) + P.dt * np.abs(a))                      # reach of one control step
+    clear = ((s - b0) + m < 0) | ((s - b1) - m > 0) | (kv == 0)
+    inside = ((s - b0) - m > 0) & ((s - b1) + m < 0) & (np.abs(kv) * (np.abs(ey) + 0.5 * m) < 0.5)
+    cls = np.where(clear, 0, np.where(inside, 1, 2))                     # [B, C, N]
+    vote = lambda c: 0 if (c == 0).all() else 1 if (c == 1).all() else 2
+    live = live_rows(B, P, sc, G)
+    mix = {'units': np.zeros(3), 'pool': np.zeros(3)}
+    for b in range(B):
+        idx = numbering(G, live[b])
+        if idx.size == 0:
+            continue
+        life = np.minimum(dead[b, idx] + 1, N)
+        for u in range(0, idx.size, 64):
+            for k in range(life[u:u + 64].max()):
+                mix['units'][vote(cls[b, idx[u:u + 64], k])] += 1
+        lanes = np.zeros(64, dtype=np.int64)
+        cand = np.zeros(64, dtype=np.int64)
+        kk = np.zeros(64, dtype=np.int64)
+        nxt = 0
+        while True:
+            idle = lanes == 0
+            take = min(int(idle.sum()), idx.size - nxt)
+            if take > 0:
+                w = np.flatnonzero(idle)[:take]
+                lanes[w], cand[w], kk[w] = life[nxt:nxt + take], idx[nxt:nxt + take], 0
+                nxt += take
+            act = lanes > 0
+            if not act.any():
+                break
+            mix['pool'][vote(cls[b, cand[act], kk[act]])] += 1
+            lanes[act] -= 1
+            kk[act] += 1
+    return {k: v / v.sum() for k, v in mix.items()}
+
+
 if __name__ == '__main__':
+    if len(sys.argv) > 1 and sys.argv[1] == '--votes':
+        a = sys.argv[2:]
+        r = votes(int(a[0]) if a else 256, int(a[1]) if len(a) > 1 else 0)
+        for k in ('units', 'pool'):
+            print(f'{k:5s}: K = 0 on {r[k][0]:.1%} of the wave-steps, K = k_v on {r[k][1]:.1%}, per-sub-step fallback on {r[k][2]:.1%}')
+        sys.exit(0)
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 512
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     r = model(B, seed)
