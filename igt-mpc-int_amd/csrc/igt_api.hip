@@ -59,6 +59,7 @@ struct igt_handle {
     int nc;
     int n_cu;              // compute units of the device (sizes the persistent search grid)
     int concurrency;       // solves the caller keeps in flight on the device (igt_set_concurrency)
+    int polish_grad;       // IGT_GRAD_FORWARD_DIFF / IGT_GRAD_ADJOINT (igt_set_polish_gradient)
     void* comm;            // RCCL communicator of igt_comm_init (null: none)
     int comm_world, comm_rank;
     int32_t comm_B_local;  // shard size of the communicator's first all-gather (0 = none yet); later calls must match
@@ -479,7 +480,7 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     if (h->prof) HIPCHK(hipEventRecord(h->ev[1], st));
     HIPCHK(igt::launch_emit<T>(kp, B, (int)W, A, st));
     if constexpr (sizeof(T) == 8) {      // the winners, polished in place in the outputs (igt_kernels_f64.hip polish_f64_kernel)
-        if (p.polish_iters > 0) HIPCHK(igt::launch_polish(kp, B, p.polish_iters, A, st));
+        if (p.polish_iters > 0) HIPCHK(igt::launch_polish(kp, B, p.polish_iters, h->polish_grad == IGT_GRAD_ADJOINT, A, st));
     }
     if (h->prof) { HIPCHK(hipEventRecord(h->ev[2], st)); h->ev_recorded = true; }
 
@@ -621,6 +622,46 @@ int frenet_step_impl(igt_handle* h, int32_t n, const T* x, const T* u, const T* 
     HIPCHK(igt::launch_frenet_step<T>(h->kp, n, dx, du, dk, dout, st));
     if (mem == IGT_MEM_HOST) {
         HIPCHK(hipMemcpyAsync(x_next, dout, n_x * sizeof(T), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return IGT_OK;
+}
+
+int cost_gradient_impl(igt_handle* h, int32_t B, const double* x0, const double* kparams, const uint32_t* flags, const double* U,
+                       double* cost_out, double* grad_out, int mem, void* stream) {
+    if (!h) return fail(IGT_E_INVALID, "null handle");
+    if (h->p.cost_mode != IGT_COST_PROGRESS)
+        return fail(IGT_E_INVALID, "the cost gradient is that of IGT_COST_PROGRESS (the value-network cost is not differentiated)");
+    if (B < 0) return fail(IGT_E_INVALID, "B < 0");
+    if (B == 0) return IGT_OK;
+    if (!cost_out || !grad_out) return fail(IGT_E_INVALID, "null output buffer (cost_out, grad_out)");
+    if (!x0 || !kparams || !flags || !U) return fail(IGT_E_INVALID, "null buffer");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const size_t n_x = (size_t)B * 7, n_k = (size_t)B * 3, n_u = (size_t)B * 2 * h->p.N;
+    const double *dx = x0, *dk = kparams, *du = U;
+    double *dc = cost_out, *dg = grad_out;
+    if (mem == IGT_MEM_HOST) {
+        double *a, *b, *c;
+        const auto carve = [&](Arena& ar) {
+            a = ar.take<double>(n_x); b = ar.take<double>(n_k); c = ar.take<double>(n_u);
+            dc = ar.take<double>((size_t)B); dg = ar.take<double>(n_u);
+        };
+        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
+        Arena ar{(char*)h->d_stage, 0};
+        carve(ar);
+        HIPCHK(hipMemcpyAsync(a, x0, n_x * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b, kparams, n_k * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(c, U, n_u * 8, hipMemcpyHostToDevice, st));
+        dx = a; dk = b; du = c;
+    } else if (mem != IGT_MEM_DEVICE) {
+        return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
+    }
+    // the flags only act on psi_0, which the progress cost never reads (igt_kernels_f64.hip cost_gradient_f64_kernel)
+    HIPCHK(igt::launch_cost_gradient(h->kp, B, dx, dk, du, dc, dg, st));
+    if (mem == IGT_MEM_HOST) {
+        HIPCHK(hipMemcpyAsync(cost_out, dc, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(grad_out, dg, n_u * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
     return IGT_OK;
@@ -867,6 +908,7 @@ int igt_create(const igt_params* p, int device, igt_handle** out) {
     while ((p->C / 64) % h->nc) h->nc /= 2;
     h->n_cu = 256;
     h->concurrency = 1;
+    h->polish_grad = IGT_GRAD_FORWARD_DIFF;
     h->dev_ckpt = -1; h->dev_traj_max = -1;      // developer sweeps: the environment is read here, not on every solve
     if (const char* e = std::getenv("IGT_DEV_CKPT")) h->dev_ckpt = std::max(std::atoi(e), 0);
     if (const char* e = std::getenv("IGT_DEV_TRAJ_MAX")) h->dev_traj_max = std::max(std::atoi(e), 0);
@@ -1228,6 +1270,19 @@ int igt_set_concurrency(igt_handle* h, int32_t solves_in_flight) {
     if (solves_in_flight < 1 || solves_in_flight > 64) return fail(IGT_E_INVALID, "solves_in_flight must lie in [1, 64]");
     h->concurrency = solves_in_flight;
     return IGT_OK;
+}
+
+int igt_set_polish_gradient(igt_handle* h, int mode) {
+    if (!h) return fail(IGT_E_INVALID, "null handle");
+    if (mode != IGT_GRAD_FORWARD_DIFF && mode != IGT_GRAD_ADJOINT)
+        return fail(IGT_E_INVALID, "mode must be IGT_GRAD_FORWARD_DIFF or IGT_GRAD_ADJOINT");
+    h->polish_grad = mode;
+    return IGT_OK;
+}
+
+int igt_cost_gradient_f64(igt_handle* h, int32_t B, const double* x0, const double* kparams, const uint32_t* flags,
+                          const double* U, double* cost_out, double* grad_out, int mem, void* stream) {
+    return cost_gradient_impl(h, B, x0, kparams, flags, U, cost_out, grad_out, mem, stream);
 }
 
 int igt_set_profiling(igt_handle* h, int enable) {

@@ -5,11 +5,14 @@
 //   emit_f64_kernel       one lane per scenario: the winner re-rolled with the same arithmetic -> x*[7,N+1], u*[2,N]
 //   emit_gather_f64_kernel   small batches: the winner's trajectory copied out of the unit that rolled it
 //   rollout_all_f64_kernel   debug / parity: every candidate's trajectory, cost and verdict bits
+//   polish_f64_kernel     projected-gradient steps on the winner (forward-difference or adjoint gradient)
+//   cost_gradient_f64_kernel   dJ/du of the progress cost for one control sequence per scenario (igt_adjoint64.h)
 //   search_kernel / emit_kernel / rollout_all_kernel<ExactStepper<double>>   the oracle's operation order (IGT_DEV_FLAGS=1024)
 //   search_literal_f64_kernel   the literal north_star mapping, a measurement variant (IGT_DEV_FLAGS=2048)
 // Compiled on its own so that the two heavy translation units build in parallel.
 #include "igt_device.h"
 #include "igt_fast64.h"
+#include "igt_adjoint64.h"
 #include "igt_launch.h"
 #include "igt_kernels_common.h"
 
@@ -715,9 +718,19 @@ __global__ __launch_bounds__(SEG_THREADS) void emit_seg_f64_kernel(KP P, int B, 
 // scenario the sub-step variants are voted as in a search unit.  Scenarios whose obstacles are out of reach roll the trips
 // without the Cartesian rows (obstacles_out_of_reach).  A plan that changed is rolled once more with all rows into LDS and
 // written back as whole rows; one that did not is left alone.  No workspace, no host synchronisation: one launch on the stream.
+// ADJ (igt_set_polish_gradient IGT_GRAD_ADJOINT): the gradient trips are replaced by the analytic gradient at the plan.  The
+// plan's node states lie in xl (iteration 1: the emitted x_out); lane k forms (A_k, B_k) of control step k from them
+// (igt_adjoint64.h step_jacobian -- N Jacobians side by side, a few control steps' time) into the slot region, which is idle
+// until the trials are laid out; the costate recursion over the N steps is then run by every lane on the same LDS words
+// (broadcast reads, ~25 fused multiply-adds a step), lane 0 keeps g.  Direction, trials, verdicts and acceptance are the
+// statements of the forward-difference mode.  An accepted trial is rolled once more with all rows, every lane its own trial as
+// it lies in its column, and the accepted lane keeps the states in xl: the next iteration's node states and the final
+// write-back -- the roll the forward-difference mode does once at the end, moved into the loop (the sub-step variants the
+// wave votes for are bit-identical where they apply, so the states are those of the plan rolled alone).  An iteration is a
+// Jacobian pass, a trial trip and an accepted-plan roll against g_trips + 1 trips; the LDS is polish_lds_doubles(N) either way.
 constexpr double POLISH_EPS = 1e-4;
 __host__ __device__ inline size_t polish_lds_doubles(int N) { return (size_t)2 * N * 64 + 4 * N + 7 * (N + 1); }
-template <bool HI, int NRK>
+template <bool HI, int NRK, bool ADJ = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void polish_f64_kernel(
         KP P, int B, int iters, const double* __restrict__ x0, const double* __restrict__ u_prev, const double* __restrict__ kparams,
         const uint32_t* __restrict__ flags, const double* __restrict__ obs, const double* __restrict__ cinf,
@@ -734,6 +747,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     load_scenario<double>(S, P, b, x0, u_prev, kparams, flags, obs);
     const bool far = !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
     for (int i = lane; i < n2; i += 64) u[i] = u_out[(size_t)b * n2 + i];
+    if (ADJ) {
+        for (int i = lane; i < 7 * (N + 1); i += 64) xl[i] = x_out[(size_t)b * 7 * (N + 1) + i];
+    }
     double J0 = cost_out[b];
     bool changed = false;
     NullSink none;
@@ -742,7 +758,35 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     for (int it = 0; it < iters; ++it) {
         double bestJ = 0.0;
         int bestM = -1;
-        for (int trip = 0; trip <= g_trips; ++trip) {
+        if (ADJ) {
+            const int N1 = N + 1;
+            adj::StepModel M;
+            M.init(P, S.b0, S.b1, S.kv);
+            if (lane < N) {                               // (A_k, B_k) of step k = lane, [15][N] in the slot region
+                double T[3][5];
+                adj::step_jacobian(M, xl[2 * N1 + lane], xl[3 * N1 + lane], xl[4 * N1 + lane], xl[5 * N1 + lane], u[lane], u[N + lane], T);
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int d = 0; d < 5; ++d) slot[(size_t)(r * 5 + d) * N + lane] = T[r][d];
+            }
+            __syncthreads();
+            double lam[4] = {-1.0, 2.0 * xl[3 * N1 + N], 2.0 * xl[4 * N1 + N], 0.0};      // d J / d (s, ey, epsi, v) at node N
+            for (int k = N - 1; k >= 0; --k) {
+                double T[3][5], ga, gd;
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int d = 0; d < 5; ++d) T[r][d] = slot[(size_t)(r * 5 + d) * N + k];
+                adj::costate_step(T, P.dt, P.w_u, xl[3 * N1 + k], xl[4 * N1 + k], u[k], u[N + k], lam, ga, gd);
+                if (lane == 0) {
+                    g[k] = finite_d(ga) ? ga : 0.0;
+                    g[N + k] = finite_d(gd) ? gd : 0.0;
+                }
+            }
+            __syncthreads();
+        }
+        for (int trip = ADJ ? g_trips : 0; trip <= g_trips; ++trip) {
             const bool search = trip == g_trips;
             if (!search) {                                // u + eps e_c: no projection
                 const int c = trip * 64 + lane;
@@ -797,8 +841,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         J0 = bestJ;
         changed = true;
         __syncthreads();
+        if (ADJ) {                                        // the accepted trial with all rows: its lane keeps the states
+            StoreSink<double> keep{lane == bestM ? xl : nullptr, nullptr, N};
+            double J, sN, vN;
+            unsigned viol;
+            f64::rollout_one<CAND_TABLE, HI, true, true, StoreSink<double>, false, true, NRK, true>(P, S, 0, nullptr, cinf, keep, J, viol, sN, vN, slot + lane, 64);
+            J0 = __shfl(J - (sN - S.x0[2]), bestM, 64);
+            __syncthreads();
+        }
     }
     if (!changed) return;
+    if (ADJ) {
+        const int nx = 7 * (N + 1);
+        for (int i = lane; i < nx; i += 64) x_out[(size_t)b * nx + i] = xl[i];
+        for (int i = lane; i < n2; i += 64) u_out[(size_t)b * n2 + i] = u[i];
+        if (lane == 0) cost_out[b] = J0;
+        return;
+    }
     // the polished plan with all rows: every lane rolls it (one wave's time either way), lane 0 keeps the states
     for (int i = 0; i < n2; ++i) slot[(size_t)i * 64 + lane] = u[i];
     StoreSink<double> keep{lane == 0 ? xl : nullptr, nullptr, N};
@@ -810,6 +869,71 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     for (int i = lane; i < nx; i += 64) x_out[(size_t)b * nx + i] = xl[i];
     for (int i = lane; i < n2; i += 64) u_out[(size_t)b * n2 + i] = u[i];
     if (lane == 0) cost_out[b] = J - (sN - S.x0[2]);
+}
+
+// ---- dJ/du of the progress cost for one control sequence per scenario (igt_cost_gradient_f64) ----
+// 64 sequences per wave, one per lane.  Forward sweep: the roll-out of (s, ey, epsi) with the node states kept in LDS,
+// [3 (N + 1)][GRAD_STRIDE]; backward sweep: per step the Jacobian at the kept node (igt_adjoint64.h) and the costate update, v
+// walked back by v_k = v_k+1 - dt a_k.  The two gradient entries of step k take the slots of node k + 1, which the sweep has just
+// left, so at the end the wave's gradients lie in LDS and leave as whole lines: [2 N] doubles per scenario, the 64 scenarios'
+// rows contiguous in HBM.  The lane stride is 65 doubles, not 64: the sweeps read a slot across lanes (consecutive words either
+// way), the write-out reads one lane's slots (stride 3 x 65 words: spread over the banks; 3 x 64 would put them all on one).
+// x, y, psi feed nothing back and are not rolled, so IGT_FLAG_ABS_HEADING (|psi_0|) changes nothing here.  A non-finite cost
+// gives a NaN row.  No workspace, no wave votes: lanes past B idle.
+constexpr int GRAD_STRIDE = 65;
+__host__ __device__ inline size_t grad_lds_doubles(int N) { return (size_t)3 * (N + 1) * GRAD_STRIDE; }
+__global__ __launch_bounds__(64) void cost_gradient_f64_kernel(KP P, int B, const double* __restrict__ x0,
+                                                               const double* __restrict__ kparams, const double* __restrict__ U,
+                                                               double* __restrict__ cost_out, double* __restrict__ grad_out) {
+    extern __shared__ double grad_lds[];
+    const int lane = threadIdx.x, N = P.N, n2 = 2 * N;
+    const int b0 = blockIdx.x * 64, b = b0 + lane;
+    if (b < B) {
+        adj::StepModel M;
+        M.init(P, kparams[(size_t)b * 3 + 0], kparams[(size_t)b * 3 + 1], kparams[(size_t)b * 3 + 2]);
+        const double* ua = U + (size_t)b * n2;
+        double* node = grad_lds + lane;
+        double s = x0[(size_t)b * 7 + 2], ey = x0[(size_t)b * 7 + 3], ep = x0[(size_t)b * 7 + 4], v = x0[(size_t)b * 7 + 5];
+        const double s0 = s;
+        double J = 0.0, T[3][5];
+        node[0] = s; node[GRAD_STRIDE] = ey; node[2 * GRAD_STRIDE] = ep;
+        for (int k = 0; k < N; ++k) {
+            const double a = ua[k], df = ua[N + k];
+            J = J + P.w_u * (a * a + df * df);                                       // mpc.py:362-364
+            J = J + ep * ep;
+            J = J + ey * ey;
+            const adj::Slip sl = adj::slip(M.lr_ratio, df);
+            M.step<false>(s, ey, ep, v, a, sl, T);
+            v = fma(M.dt, a, v);
+            double* nk = node + (size_t)3 * (k + 1) * GRAD_STRIDE;
+            nk[0] = s; nk[GRAD_STRIDE] = ey; nk[2 * GRAD_STRIDE] = ep;
+        }
+        J = J + ep * ep;
+        J = J + ey * ey;
+        J = J - (s - s0);                                                            // mpc.py:372
+        cost_out[b] = J;
+        double lam[4] = {-1.0, 2.0 * ey, 2.0 * ep, 0.0};
+        for (int k = N - 1; k >= 0; --k) {
+            const double a = ua[k], df = ua[N + k];
+            v = fma(-M.dt, a, v);
+            double* nk = node + (size_t)3 * k * GRAD_STRIDE;
+            const double sk = nk[0], eyk = nk[GRAD_STRIDE], epk = nk[2 * GRAD_STRIDE];
+            adj::step_jacobian(M, sk, eyk, epk, v, a, df, T);
+            double ga, gd;
+            adj::costate_step(T, M.dt, P.w_u, eyk, epk, a, df, lam, ga, gd);
+            nk[3 * GRAD_STRIDE] = ga;                                                // node k + 1's s and ey slots
+            nk[4 * GRAD_STRIDE] = gd;
+        }
+        node[0] = finite_d(J) ? 1.0 : 0.0;                                           // node 0's s slot: the row's verdict
+    }
+    __syncthreads();
+    const int nS = B - b0 < 64 ? B - b0 : 64;
+    double* go = grad_out + (size_t)b0 * n2;
+    for (int i = lane; i < nS * n2; i += 64) {
+        const int sc = i / n2, r = i - sc * n2, row = r >= N ? 1 : 0, k = r - row * N;
+        const double gv = grad_lds[(size_t)(3 * (k + 1) + row) * GRAD_STRIDE + sc];
+        go[i] = grad_lds[sc] != 0.0 ? gv : (double)NAN;
+    }
 }
 
 template <int CAND, bool HI>
@@ -1184,6 +1308,10 @@ hipError_t prepare_emit_kernels() {
     if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<false, 4>);
     if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<false, 0>);
     if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<true, 0>);
+    if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<false, 4, true>);
+    if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<false, 0, true>);
+    if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<true, 0, true>);
+    if (e == hipSuccess) e = seg_lds_opt_in(cost_gradient_f64_kernel);
     return e;
 }
 
@@ -1210,16 +1338,29 @@ hipError_t launch_emit<double>(const KP& P, int B, int W, const SolveArgs<double
 
 // polish_iters > 0: after emit, on the same stream (igt_api.hip solve_impl).  The kernel's LDS passes 64 KB from N = 63 on: it is
 // asked for once per handle (prepare_emit_kernels), like the emit in pieces'.
-hipError_t launch_polish(const KP& P, int B, int iters, const SolveArgs<double>& A, hipStream_t st) {
+// adjoint: the gradient of every iteration is the analytic one (igt_set_polish_gradient); the same grid, block and LDS.
+hipError_t launch_polish(const KP& P, int B, int iters, bool adjoint, const SolveArgs<double>& A, hipStream_t st) {
     if (P.dev & (DEV_EXACT64 | DEV_LITERAL)) return hipErrorNotSupported;      // the oracle-order developer kernels
     const size_t lds = polish_lds_doubles(P.N) * 8;
-#define IGT_LAUNCH_POLISH(HI_, NRK_)                                                                                          \
-    hipLaunchKernelGGL((polish_f64_kernel<HI_, NRK_>), dim3(B), dim3(64), lds, st, P, B, iters, A.x0, A.u_prev, A.kparams, A.flags, \
+#define IGT_LAUNCH_POLISH(HI_, NRK_, ADJ_)                                                                                    \
+    hipLaunchKernelGGL((polish_f64_kernel<HI_, NRK_, ADJ_>), dim3(B), dim3(64), lds, st, P, B, iters, A.x0, A.u_prev, A.kparams, A.flags, \
                        A.obs, A.cinf, A.status_out, A.cost_out, A.x_out, A.u_out)
-    if (P.hi_order) IGT_LAUNCH_POLISH(true, 0);
-    else if (P.n_rk4 == 4) IGT_LAUNCH_POLISH(false, 4);
-    else IGT_LAUNCH_POLISH(false, 0);
+    if (adjoint) {
+        if (P.hi_order) IGT_LAUNCH_POLISH(true, 0, true);
+        else if (P.n_rk4 == 4) IGT_LAUNCH_POLISH(false, 4, true);
+        else IGT_LAUNCH_POLISH(false, 0, true);
+    } else if (P.hi_order) IGT_LAUNCH_POLISH(true, 0, false);
+    else if (P.n_rk4 == 4) IGT_LAUNCH_POLISH(false, 4, false);
+    else IGT_LAUNCH_POLISH(false, 0, false);
 #undef IGT_LAUNCH_POLISH
+    return hipGetLastError();
+}
+
+// igt_cost_gradient_f64: one wave per 64 scenarios; the LDS passes 64 KB from N = 41 on (asked for in prepare_emit_kernels)
+hipError_t launch_cost_gradient(const KP& P, int B, const double* x0, const double* kparams, const double* U, double* cost_out,
+                                double* grad_out, hipStream_t st) {
+    hipLaunchKernelGGL(cost_gradient_f64_kernel, dim3((B + 63) / 64), dim3(64), grad_lds_doubles(P.N) * 8, st, P, B, x0, kparams, U,
+                       cost_out, grad_out);
     return hipGetLastError();
 }
 

@@ -104,7 +104,9 @@ hipError_t launch_value(const KP& P, int B, const DevNet<T>& net, const SolveArg
 hipError_t prepare_value_kernels(int n_hidden_mats);   // once per igt_set_value_net: dynamic-LDS function attributes
 hipError_t prepare_emit_kernels();                     // once per igt_create: the same for the float64 emit in pieces
 // polish_iters > 0 (float64, progress cost): projected-gradient steps on the emitted winners, in place in A's outputs
-hipError_t launch_polish(const KP& P, int B, int iters, const SolveArgs<double>& A, hipStream_t st);
+hipError_t launch_polish(const KP& P, int B, int iters, bool adjoint, const SolveArgs<double>& A, hipStream_t st);
+hipError_t launch_cost_gradient(const KP& P, int B, const double* x0, const double* kparams, const double* U, double* cost_out,
+                                double* grad_out, hipStream_t st);
 template <typename T> hipError_t launch_reduce(int B, int W, const SolveArgs<T>& A, hipStream_t st);
 // ramp-hold refinement: winner of the pass just finished -> centre/span of the next pass (cpar[B,4])
 template <typename T>

@@ -13,6 +13,7 @@ IGT_CAND_LATTICE, IGT_CAND_TABLE, IGT_CAND_RAMP_HOLD, IGT_CAND_TRACK = 0, 1, 2, 
 IGT_COST_PROGRESS, IGT_COST_VALUE_NET = 0, 1
 IGT_FLAG_ABS_HEADING = 1
 IGT_FLAG_WARM = 2
+IGT_GRAD_FORWARD_DIFF, IGT_GRAD_ADJOINT = 0, 1
 VIOL_BITS = dict(box_v=1, box_u=2, rate=4, ey=8, terminal=16, collision=32, nonfinite=64)
 
 
@@ -71,10 +72,15 @@ SYMBOLS = {
     'igt_allgather_controls_f32': (_i, [_vp, _i32, _vp, _vp, _vp]),
     'igt_allgather_controls_f64': (_i, [_vp, _i32, _vp, _vp, _vp]),
     'igt_set_concurrency': (_i, [_vp, _i32]),
+    'igt_set_polish_gradient': (_i, [_vp, _i]),
+    'igt_cost_gradient_f64': (_i, [_vp, _i32] + [_vp] * 6 + [_i, _vp]),
     'igt_set_profiling': (_i, [_vp, _i]),
     'igt_get_kernel_ms': (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     'igt_algorithmic_bytes_per_solve': (_i, [_vp, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
+
+# added without a change of IGT_VERSION: a library of the same ABI from before them (IGT_LIB_PATH, tools/ab_lib.sh) lacks them
+OPTIONAL_SYMBOLS = ('igt_set_polish_gradient', 'igt_cost_gradient_f64')
 
 _libs = {}
 # IGT_DEV_FLAGS bits (csrc/igt_device.h DevFlag; the launch-time bits there are the library's own and not listed here)
@@ -137,6 +143,8 @@ def load(dev=None):
     except OSError as e:
         raise ImportError(f'cannot load {path}: {e}') from e
     for name, (res, args) in SYMBOLS.items():
+        if name in OPTIONAL_SYMBOLS and path != (LIB_PATH_DEV if dev else LIB_PATH) and not hasattr(lib, name):
+            continue                # an older build given by IGT_LIB_PATH: whoever needs the symbol gets the AttributeError
         fn = getattr(lib, name)     # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

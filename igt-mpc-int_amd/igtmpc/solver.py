@@ -22,7 +22,7 @@ def _is_torch(x):
 
 class BatchSolver:
     def __init__(self, N=20, dt=0.1, n_rk4=4, C=256, n_obs=1, device=0, dtype='f32',
-                 cand_mode='lattice', cost_mode='progress', **limits):
+                 cand_mode='lattice', cost_mode='progress', polish_grad='fd', **limits):
         self._h = None
         self.lib = L.load()          # the shipped library -- or libigtmpc_dev.so when IGT_DEV_FLAGS asks for developer kernels
         if dtype not in _DT:
@@ -46,6 +46,10 @@ class BatchSolver:
             raise ValueError("polish_iters > 0 needs dtype='f64' (a forward difference of 1e-4 on a float cost is noise)")
         if p.polish_iters > 0 and cost_mode != 'progress':
             raise ValueError("polish_iters > 0 needs cost_mode='progress' (the value-network cost is not polished)")
+        # gradient of the polish (igtmpc.h igt_set_polish_gradient): 'fd' forward differences (the default), 'adjoint' analytic
+        if polish_grad not in ('fd', 'adjoint'):
+            raise ValueError("polish_grad must be 'fd' or 'adjoint'")
+        self.polish_grad = polish_grad
         self.params = p
         self.device = device
         h = ct.c_void_p()
@@ -59,6 +63,8 @@ class BatchSolver:
         self._fcast = getattr(self.lib, f'igt_forecast_batch_{dtype}')
         self._fscene = getattr(self.lib, f'igt_forecast_scene_{dtype}')
         self._routes_set = False
+        if polish_grad != 'fd':      # the default needs no call: a library from before the setter still serves it
+            self._check(self.lib.igt_set_polish_gradient(self._h, L.IGT_GRAD_ADJOINT))
 
     def _check(self, rc):
         L.check(rc, self.lib)
@@ -235,6 +241,31 @@ class BatchSolver:
         mode, ptrs, keep = self._prep(arrs, shapes, dts)
         self._check(self._rollout(self._h, B, *ptrs, mode, self._stream_ptr(stream, False)))
         return dict(X=X, U=U, cost=cost, viol=viol)
+
+    def cost_gradient(self, x0, kparams, flags, U, out=None, stream=None):
+        """dJ/du of the progress cost (mpc.py:356-373) for one control sequence per scenario, no projection and no verdicts
+        (igtmpc.h igt_cost_gradient_f64): x0[B,7] kparams[B,3] flags[B] U[B,2,N] -> dict(cost[B], grad[B,2,N]); a non-finite
+        cost gives a NaN row.  float64 solvers with the progress cost; numpy arrays or tensors on the solver's GPU, as solve."""
+        if self.dtype != 'f64':
+            raise ValueError("cost_gradient needs dtype='f64'")
+        B, N = int(x0.shape[0]), self.N
+        torch_mode = _is_torch(x0)
+        if out is None:
+            if torch_mode:
+                import torch
+                out = dict(cost=torch.empty((B,), dtype=torch.float64, device=x0.device),
+                           grad=torch.empty((B, 2, N), dtype=torch.float64, device=x0.device))
+            else:
+                out = dict(cost=np.empty((B,), np.float64), grad=np.empty((B, 2, N), np.float64))
+        f8 = np.float64
+        mode, ptrs, keep = self._prep([x0, kparams, flags, U, out['cost'], out['grad']],
+                                      [(B, 7), (B, 3), (B,), (B, 2, N), (B,), (B, 2, N)], [f8, f8, np.uint32, f8, f8, f8])
+        if mode == L.IGT_MEM_HOST:
+            for k, i in (('cost', 4), ('grad', 5)):
+                if keep_is_copy(out[k], ptrs[i]):
+                    raise ValueError(f'out[{k!r}] must be a contiguous float64 array')
+        self._check(self.lib.igt_cost_gradient_f64(self._h, B, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        return out
 
     def set_routes(self, table=None):
         """Route geometry for forecast(); default: the four-way intersection of igtmpc.routes."""

@@ -344,6 +344,31 @@ int igt_allgather_controls_f64(igt_handle* h, int32_t B_local, const double* u_o
  * Results do not depend on it.  IGT_E_INVALID unless 1 <= solves_in_flight <= 64. */
 int igt_set_concurrency(igt_handle* h, int32_t solves_in_flight);
 
+/* Which gradient the polish of the winner takes its direction from (polish_iters > 0; default IGT_GRAD_FORWARD_DIFF: the 2 N
+ * forward differences described at igt_solve_batch_*, today's launch sequence and bits).  IGT_GRAD_ADJOINT: the analytic
+ * gradient of the cost at the current plan -- the derivative igt_cost_gradient_f64 returns -- from the plan's node states and one
+ * costate sweep; direction scaling, the 64 projected trials judged by every verdict and acceptance only when strictly cheaper
+ * are unchanged, and so is everything the polish promises about x_out, u_out, cost_out, argmin_out, status_out, workspace and
+ * stream capture.  The two gradients differ by the forward difference's truncation (order 1e-4 J''), so the polished plans are
+ * close, not equal.  A setter and not a member of igt_params: that struct is not versioned.  IGT_E_INVALID for any other mode.
+ * (Added without a change of IGT_VERSION; a caller that must run against an older library probes the symbol.) */
+enum { IGT_GRAD_FORWARD_DIFF = 0, IGT_GRAD_ADJOINT = 1 };
+int igt_set_polish_gradient(igt_handle* h, int mode);
+
+/* dJ/du of the progress cost for one control sequence per scenario:
+ *   J(u) = sum_{k<=N} (epsi_k^2 + ey_k^2) + w_u sum_{k<N} (a_k^2 + df_k^2) - (s_N - s_0)            (mpc.py:356-373)
+ * over the RK4 Frenet roll-out from x0 with the handle's dt, n_rk4, l_r, l_f, differentiated by every a_k and df_k.  No
+ * projection, no verdicts: limits, obstacles and the terminal set play no part.  K(s) is taken as locally constant, which is
+ * the derivative wherever no RK stage argument sits on a curvature break-point.
+ *   x0 [B,7]  kparams [B,3]  flags [B]  U [B,2,N]  ->  cost_out [B]  grad_out [B,2,N]
+ * flags are accepted as a solve's are (IGT_FLAG_ABS_HEADING acts on psi_0, which the cost does not read).  A non-finite cost
+ * gives that scenario a NaN gradient row.  cost_out agrees with igt_rollout_batch_f64's cost of the same controls to rounding
+ * (~1e-12), not bit for bit.  IGT_MEM_DEVICE: one kernel enqueued on `stream`, no workspace, no allocation, no host
+ * synchronisation (capturable).  IGT_E_INVALID on a handle with IGT_COST_VALUE_NET, for B < 0 and for null buffers; B = 0 is a
+ * no-op.  (Added without a change of IGT_VERSION; callers probe the symbol.) */
+int igt_cost_gradient_f64(igt_handle* h, int32_t B, const double* x0, const double* kparams, const uint32_t* flags,
+                          const double* U, double* cost_out, double* grad_out, int mem, void* stream);
+
 /* Workspace (owned by the handle, grown on the first solve of a batch size, never shrunk; growth synchronises the stream and is
  * refused under stream capture with IGT_E_STATE).  Per scenario, C = 256: 48 B of slice partials, 16 B of live-row masks and
  * incumbent keys (float64; float32: 8 B), 128 B of the acceleration rows' travel sums (float64), 768 B of horizon checkpoints of
