@@ -14,8 +14,8 @@ The oracle's full [B, C, 7, N+1] tensor would be ~20 GB at these sizes, so each 
 import numpy as np
 import pytest
 
-import np_oracle as O
-from helpers import F32_EPS, F32_TIE, REL_TOL, ambiguous_mask, oracle_params, rel_err
+import parity_cases as PC
+from helpers import F32_EPS, REL_TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -29,53 +29,6 @@ def igt():
     return igtmpc
 
 
-def _cinf():
-    from igtmpc.cinf import cinf_halfplanes
-    return cinf_halfplanes()
-
-
-def _net(golden_dir, sc):
-    v = np.load(f'{golden_dir}/value_net_golden.npz')
-    layers, i = [], 0
-    while f'sc{sc}_W{i}' in v:
-        layers.append((v[f'sc{sc}_W{i}'], v[f'sc{sc}_b{i}']))
-        i += 1
-    return layers
-
-
-def _check_subsample(b, got, idx, P, tol, eps, net=None, cand='lattice'):
-    """got[idx] against the float64 oracle on the same 512 scenarios."""
-    f = lambda k: np.asarray(b[k][idx], dtype=np.float64)
-    kw = {}
-    if net is not None:
-        kw = dict(net=net, tv_sv=f('tv_sv'), enc=f('enc'))
-    if cand == 'lattice':
-        ref = O.solve_batch(f('x0'), f('u_prev'), f('kparams'), b['flags'][idx], f('obs_xy'), *_cinf(), P,
-                            return_all=True, **kw)
-    else:
-        ref = O.solve_batch_refined(f('x0'), f('u_prev'), f('kparams'), b['flags'][idx], f('obs_xy'), *_cinf(), P,
-                                    cand=cand, **kw)[0]
-    kp = f('kparams')[:, None, :]
-    x0 = O.apply_flags(f('x0'), b['flags'][idx])[:, None, :]
-    bp = O.breakpoint_distance(x0, ref['U'], kp, P)
-    # cost near-ties: 1e-6 for the f32 rollout arithmetic; the f32 value network (MFMA, hardware exp/rcp tanh) adds
-    # ~1e-6 relative error to V, so with the terminal value in the cost ties are set aside at 2e-5
-    tie = eps if eps != F32_EPS else (2e-5 if net is not None else F32_TIE)
-    amb = ambiguous_mask(ref, P, eps, tie, eps, bp)
-    ok = ~amb
-    # the steering feedback carries rounding differences forward: more of the tracking family's decisions sit inside noise
-    assert ok.mean() > (0.99 if cand == 'lattice' else 0.85), f'only {ok.mean():.3f} of the subsample is decided outside float noise'
-    g = {k: got[k][idx] for k in ('x', 'u', 'cost', 'argmin', 'status')}
-    assert (g['status'][ok] == ref['status'][ok]).all()
-    assert (g['argmin'][ok] == ref['argmin'][ok]).all()
-    sol = ok & (ref['status'] == 0)
-    assert sol.sum() > 100, 'subsample has too few solvable scenarios to mean anything'
-    assert rel_err(g['x'][sol], ref['x'][sol]).max() <= tol
-    assert rel_err(g['u'][sol], ref['u'][sol]).max() <= max(tol, 1e-7)
-    assert rel_err(g['cost'][sol], ref['cost'][sol]).max() <= tol
-    return float(amb.mean())
-
-
 def _check_pieces(solver, b, big, cuts, extra=()):
     """big batch == the same scenarios solved in pieces (different queue make-up, other search build), bitwise."""
     keys = list(ARGS) + list(extra)
@@ -84,42 +37,35 @@ def _check_pieces(solver, b, big, cuts, extra=()):
         assert np.array_equal(np.concatenate([q[k] for q in parts]), big[k], equal_nan=True), k
 
 
-def _run(igt, B, offset, dtype, tol, eps, golden_dir=None, gt_sc=0, cand='lattice'):
-    from igtmpc.scenarios import make_batch
-    npdt = np.float64 if dtype == 'f64' else np.float32
-    b = make_batch(B, dtype=npdt, offset=offset)
+def _run(igt, name, B, offset, dtype, tol, eps, gt_sc=0, cand='lattice'):
+    """The subsample, its set-aside widths and its recorded floors are parity_cases.fullsize_case's."""
+    case, idx, b = PC.fullsize_case(name, B, offset, dtype, gt_sc, cand)
+    assert (tol, eps) == (case['tol'], case['eps'])
     assert set(np.unique(b['sc'])) == set(range(1, 9)), 'all 8 scenario variants must be tiled into the batch'
-    idx = np.sort(np.random.default_rng(7).choice(B, 512, replace=False))
-    kw, extra, net = dict(cand_mode=cand), (), None
-    if gt_sc:
-        layers = _net(golden_dir, gt_sc)
-        net = dict(layers=layers, Wn=np.eye(6), mu_f=np.zeros(6), sigma_t=1.0, mu_t=0.0)   # bench.py's normalisation
-        kw['cost_mode'] = 'value_net'
-        extra = ('tv_sv', 'enc')
-    with igt.BatchSolver(dtype=dtype, **kw) as s:
-        P = oracle_params(s)
-        s.set_cinf(*_cinf())
-        if gt_sc:
-            s.set_value_net(**net)
+    extra = ('tv_sv', 'enc') if gt_sc else ()
+    with PC.open_solver(igt, case) as s:
         big = s.solve(*[b[k] for k in list(ARGS) + list(extra)])
         assert 0.5 < (big['status'] == 0).mean() < 1.0
         q = B // 4
         _check_pieces(s, b, big, [0, 4096, 4096 + 1003, q + 17, 2 * q, 3 * q + 5, B], extra)
-    amb = _check_subsample(b, big, idx, P, tol, eps, net, cand)
-    print(f'B={B} dtype={dtype} gt={gt_sc} cand={cand}: ambiguous share of the subsample {amb:.4f}')
+    got = {k: big[k][idx] for k in ('x', 'u', 'cost', 'argmin', 'status')}
+    m = PC.check_case(case, got, PC.oracle_passes(case))
+    # the bounds this file has always asserted, next to the recorded ones
+    assert m['compared'] / m['B'] > (0.99 if cand == 'lattice' else 0.85), 'too little of the subsample is decided outside float noise'
+    assert m['solved'] > 100, 'subsample has too few solvable scenarios to mean anything'
 
 
 @pytest.mark.parametrize('dtype,tol,eps', [('f64', 1e-9, 1e-9), ('f32', REL_TOL, F32_EPS)])
 def test_config2_batch_65536(igt, dtype, tol, eps):
     """BASELINE configs[2]: batch = 65 536, all 8 sc variants tiled, horizon 20, Frenet-frame model."""
-    _run(igt, 65536, 0, dtype, tol, eps)
+    _run(igt, 'config2', 65536, 0, dtype, tol, eps)
 
 
 @pytest.mark.parametrize('dtype,tol,eps', [('f64', 1e-9, 1e-9), ('f32', REL_TOL, F32_EPS)])
 def test_config3_shard_32768(igt, dtype, tol, eps):
     """BASELINE configs[3]: 262 144 scenarios sharded 8 ways = 32 768 per GPU; rank 3's shard (offset 3 x 32 768,
     the generator's per-rank offset path).  The all-gather across ranks is covered by tests/test_sharding_gloo.py."""
-    _run(igt, 32768, 3 * 32768, dtype, tol, eps)
+    _run(igt, 'config3', 32768, 3 * 32768, dtype, tol, eps)
 
 
 @pytest.mark.parametrize('dtype,tol,eps,sc', [('f64', 1e-9, 1e-9, 1), ('f64', 1e-9, 1e-9, 3), ('f32', REL_TOL, F32_EPS, 1),
@@ -127,7 +73,7 @@ def test_config3_shard_32768(igt, dtype, tol, eps):
 def test_config4_gt_mpc_65536(igt, golden_dir, dtype, tol, eps, sc):
     """BASELINE configs[4]: gt_mpc, terminal value network (shipped V_GT_sc1: 2 hidden layers, V_GT_sc3: 3) evaluated
     on the GPU inside the cost, batch = 65 536 (per GPU; the 8-GPU run itself is the driver's)."""
-    _run(igt, 65536, 0, dtype, tol, eps, golden_dir, sc)
+    _run(igt, 'config4', 65536, 0, dtype, tol, eps, sc)
 
 
 @pytest.mark.parametrize('dtype,tol,eps', [('f64', 1e-9, 1e-9), ('f32', REL_TOL, 2e-5)])
@@ -135,4 +81,4 @@ def test_config2_batch_65536_tracking_family(igt, dtype, tol, eps):
     """The same full-size batch through the family the planner and the closed-loop driver use by default
     (IGT_CAND_TRACK: steering feedback inside the roll-out, acceleration envelope): oracle on the 512-scenario subsample
     + the big batch equals the same scenarios solved in pieces, bitwise."""
-    _run(igt, 65536, 0, dtype, tol, eps, cand='track')
+    _run(igt, 'config2_track', 65536, 0, dtype, tol, eps, cand='track')

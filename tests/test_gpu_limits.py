@@ -13,148 +13,24 @@ import pytest
 
 import np_oracle as O
 from igtmpc._lib import DEV_ALL_ROWS, DEV_NO_BOUND, DEV_NO_EARLY_EXIT, DEV_NO_FAR, DEV_NO_PRUNE
-from helpers import F32_EPS, F32_TIE, REL_TOL, ambiguous_mask, oracle_params, rel_err, verdict_margins
+from parity_cases import LIMITS, LIMITS_F32_SEEDS as F32_SEEDS, LIMITS_N_SEEDS as N_SEEDS, limits_case, limits_cinf as _cinf, \
+    limits_draw as _draw, limits_inputs as _inputs, limits_net as _net
+from helpers import F32_EPS, F32_TIE, REL_TOL, compare_solve, floors, oracle_params, params_equal, rel_err, solver_track, verdict_margins
 
-LIMITS = {
-    'v_min': (0.0, -1.0, -2.0),            # mpc.yaml ships -1.0; mpc.py:57 hard-codes 0
-    'v_max': (5.0, 8.0, 15.0),
-    'a_min': (-4.0, -1.5, -8.0),
-    'a_max': (3.0, 6.0, 20.0),
-    'df_max': (1.0, 0.6, 0.35),            # either side of the df_small switch (0.78)
-    'jerk_limit': (0.9, 0.2, 0.02, 4.0),
-    'steer_rate_limit': (0.7, 0.1, 2.0),
-    'l_r_l_f': ((2.235, 2.235), (1.2, 3.0)),
-    'feas_tol': (1e-6, 0.0, 1e-3),
-    'track_vcap': (1.0, 0.0),
-    'track_env': (1.0, 0.0, 0.5),
-}
 # every pruning switch the shipped library honours: no early exit, no Cartesian row skip, all acceleration rows, no incumbent
 # bound; under the value-network cost also no value-bound pruning
 PRUNE_OFF = DEV_NO_EARLY_EXIT | DEV_NO_FAR | DEV_ALL_ROWS | DEV_NO_BOUND
 PRUNE_OFF_NET = PRUNE_OFF | DEV_NO_PRUNE
 
-N_SEEDS = 32
-F32_SEEDS = range(0, N_SEEDS, 3)
 # Compared share of the draws (scenarios outside the set-asides; 1.0 where not listed), as measured, asserted less one scenario
-# (or 0.02).  Every f64 share below 0.95 is the near-tie rule alone, and every such draw is ramp-hold with a refinement pass:
+# (or 0.02: helpers.share_floor).  Every f64 share below 0.95 is the near-tie rule alone, and every such draw is ramp-hold with a refinement pass:
 # the re-centred pass spans a narrow interval around a winner pinned at a limit (steering rate 0.1 or 0.7, a clipped target),
-# and neighbouring candidates with different controls land within 1e-9 of each other's cost.  No f64 scenario is set aside by
-# a threshold or a break-point.  f32: seeds 6 and 21 are near-ties too; seed 12 is one near-tie and five stage arguments within
+# and neighbouring candidates with different controls land within 1e-9 of each other's cost.  Seed 20 (tracking family,
+# feas_tol = 0) is the one f64 draw with threshold set-asides: two winners ride a limit exactly, g = 0.0 = feas_tol.  No f64
+# scenario is set aside by a break-point.  f32: seeds 6 and 21 are near-ties too; seed 12 is one near-tie and five stage arguments within
 # F32_EPS of a break-point (lattice, a_max = 20: the fast candidates cross the arc's ends).
 SHARE = {('f64', 5): 0.875, ('f64', 6): 0.825, ('f64', 20): 0.95, ('f64', 21): 0.875, ('f64', 25): 0.875,
          ('f32', 6): 0.8, ('f32', 12): 0.914, ('f32', 15): 69 / 70, ('f32', 21): 0.85}
-
-
-def _floor(share, B):
-    return share - max(0.02, 1.0 / B)
-
-
-def _choice(rng, seq):
-    return seq[int(rng.integers(len(seq)))]
-
-
-def _draw(seed):
-    rng = np.random.default_rng([1923, seed])
-    cfg = dict(
-        N=_choice(rng, (7, 12, 20, 33)),
-        n_rk4=_choice(rng, (2, 4, 4)),
-        dt=_choice(rng, (0.05, 0.1, 0.1, 0.2)),
-        C=_choice(rng, (64, 256, 256)),
-        cand=_choice(rng, ('lattice', 'ramp_hold', 'track', 'track')),
-        n_obs=_choice(rng, (0, 1, 1, 2)),
-        B=_choice(rng, (8, 24, 40, 70)),
-        terminal=bool(rng.random() < 0.6),
-    )
-    lim = {k: _choice(rng, v) for k, v in LIMITS.items() if k not in ('l_r_l_f', 'track_vcap', 'track_env')}
-    lim['l_r'], lim['l_f'] = _choice(rng, LIMITS['l_r_l_f'])
-    vcap, env = _choice(rng, LIMITS['track_vcap']), _choice(rng, LIMITS['track_env'])
-    # the first seeds are pinned to the corners that must be reached whatever the generator draws: the tracking family with
-    # the speed cap off and accelerations above the device's old clipped cap (a_max = 20; jerk_limit = 0.02), and with v_min < 0
-    if seed in (0, 1, 2):
-        cfg['cand'] = 'track'
-    if seed == 0:
-        lim['a_max'], lim['jerk_limit'], vcap, cfg['dt'] = 20.0, 0.9, 0.0, 0.1
-    if seed == 1:
-        lim['jerk_limit'], vcap = 0.02, 0.0
-    if seed == 2:
-        lim['v_min'] = -2.0
-    if seed == 3:
-        lim['feas_tol'] = 0.0
-    if cfg['cand'] == 'track':
-        lim['track_vcap'], lim['track_env'] = vcap, env
-    cfg['refine'] = _choice(rng, (0, 0, 1)) if cfg['cand'] != 'lattice' else 0
-    if seed in (0, 1):          # rollout_all compares every candidate's controls (first pass only)
-        cfg['refine'] = 0
-    cfg['net'] = _choice(rng, (0, 0, 0, 1, 3)) if cfg['n_obs'] == 1 else 0
-    while cfg['B'] * cfg['C'] * cfg['N'] * cfg['n_rk4'] * (1 + cfg['refine']) > 2.5e7:     # the numpy oracle: about a second
-        cfg['B'] //= 2
-    cfg['limits'] = lim
-    return cfg
-
-
-# (dt, jerk_limit) pairs whose terminal set has more facets than IGT_MAX_CINF = 256: the fixed point converges at every drawn
-# pair, but at a slow jerk ramp the polygon keeps one edge per step (dt = 0.05: 982 facets at jerk 0.02, 312 at 0.2;
-# dt = 0.1, jerk 0.02: 492) -- and takes minutes to compute.  Those draws run without the terminal set.
-CINF_TOO_LARGE = {(0.05, 0.02), (0.1, 0.02), (0.05, 0.2)}
-
-
-def _cinf(cfg):
-    """The terminal set at the drawn (dt, jerk), or (None, None)."""
-    from igtmpc.cinf import cinf_halfplanes
-    jerk = cfg['limits'].get('jerk_limit', 0.9)
-    if not cfg['terminal'] or (cfg['dt'], jerk) in CINF_TOO_LARGE:
-        return None, None
-    A, b = cinf_halfplanes(dt=cfg['dt'], jerk=jerk, **cfg.get('cinf_kw', {}))
-    assert len(b) <= 256
-    return A, b
-
-
-def _inputs(cfg, seed):
-    """make_batch's scenes (routes, curvature, opponents) with the ego's state and previous controls stretched to the limits:
-    u_prev across [a_min, a_max] x [-df_max, df_max], speeds across [v_min, v_max] with a fifth of them within 0.1 of either end,
-    and a sixth of the heading errors beyond pi/4.  float64 arrays."""
-    from igtmpc.scenarios import make_batch
-    N, dt, B, lim = cfg['N'], cfg['dt'], cfg['B'], cfg['limits']
-    b = make_batch(max(B, 8), N=N, dt=dt, seed=300 + seed, dtype=np.float64)
-    b = {k: np.ascontiguousarray(v[:B]) for k, v in b.items() if isinstance(v, np.ndarray) and len(v) >= B}
-    rng = np.random.default_rng([11, seed])
-    v_min, v_max = lim.get('v_min', 0.0), lim.get('v_max', 5.0)
-    a_min, a_max, df_max = lim.get('a_min', -4.0), lim.get('a_max', 3.0), lim.get('df_max', 1.0)
-    u_prev = np.stack([rng.uniform(a_min, a_max, B), rng.uniform(-df_max, df_max, B)], axis=-1)
-    u_prev[0:2, 0] = a_max - 0.02 * (a_max - a_min), a_min + 0.02 * (a_max - a_min)     # the box's ends in rollout_all's scenarios
-    x0 = b['x0'].copy()
-    v0 = rng.uniform(v_min, v_max, B)
-    v0[0::5] = v_min + rng.uniform(0.0, 0.1, len(v0[0::5]))
-    v0[1::5] = v_max - rng.uniform(0.0, 0.1, len(v0[1::5]))
-    x0[:, 5] = v0
-    i = np.arange(2, B, 6)
-    dep = np.where(rng.random(len(i)) < 0.5, -1.0, 1.0) * rng.uniform(0.8, 1.3, len(i)) - x0[i, 4]
-    x0[i, 4] += dep
-    x0[i, 6] += dep
-    obs = b['obs_xy']
-    if cfg['n_obs'] == 0:
-        obs = np.zeros((B, 0, 2, N + 1))
-    elif cfg['n_obs'] == 2:                                    # a second vehicle 9 m behind the first along its path
-        lag = obs.copy()
-        lag[:, 0, 0, :] -= 9.0 * np.cos(0.3 * np.arange(B))[:, None]
-        lag[:, 0, 1, :] -= 9.0 * np.sin(0.3 * np.arange(B))[:, None]
-        obs = np.concatenate([obs, lag], axis=1)
-    return dict(x0=x0, u_prev=u_prev, kparams=b['kparams'], flags=b['flags'], obs=np.ascontiguousarray(obs), u_ws=None,
-                tv_sv=b['tv_sv'], enc=b['enc'])
-
-
-def _net(cfg, golden_dir, seed):
-    if not cfg['net']:
-        return None
-    v = np.load(f'{golden_dir}/value_net_golden.npz')
-    layers, i = [], 0
-    while f"sc{cfg['net']}_W{i}" in v:
-        layers.append((v[f"sc{cfg['net']}_W{i}"], v[f"sc{cfg['net']}_b{i}"]))
-        i += 1
-    rng = np.random.default_rng([13, seed])
-    return dict(layers=layers, Wn=np.eye(6) + 0.05 * rng.normal(size=(6, 6)),
-                mu_f=np.array([20.0, 2.5, 0.0, 0.0, 0.0, 0.0]) + 0.1 * rng.normal(size=6), sigma_t=float(_choice(rng, (1.0, -2.0))),
-                mu_t=float(rng.normal()))
 
 
 def _device(cfg, inp, dtype, net, flags_env, monkeypatch, with_all):
@@ -186,9 +62,11 @@ def _device(cfg, inp, dtype, net, flags_env, monkeypatch, with_all):
     return got, allc, P, tk, cinf
 
 
-def _check(cfg, inp, dtype, golden_dir, monkeypatch, seed=0, floor=None, tag='', xtol=None):
-    """Solve on the device (pruning on and off: the same bits) and compare with the oracle.  -> the compared share.
-    xtol: the trajectories' tolerance where a caller has measured that it must differ from the default (see its comment)."""
+def _check(cfg, inp, dtype, golden_dir, monkeypatch, seed=0, share=1.0, tag='', xtol=None, min_solved=0, host=None):
+    """Solve on the device (pruning on and off: the same bits) and compare with the oracle (helpers.compare_solve; share: the
+    measured compared share, asserted less one scenario or 0.02).  -> the compared share.
+    xtol: the trajectories' tolerance where a caller has measured that it must differ from the default (see its comment).
+    host: the same draw as limits_case built it without a solver -- its oracle parameters must be the handle's."""
     f32 = dtype == 'f32'
     net = _net(cfg, golden_dir, seed)
     B, C = cfg['B'], cfg['C']
@@ -198,6 +76,8 @@ def _check(cfg, inp, dtype, golden_dir, monkeypatch, seed=0, floor=None, tag='',
     tol_x = tol if xtol is None else xtol
     with_all = cfg['refine'] == 0
     got, allc, P, tk, cinf = _device(cfg, inp, dtype, net, 0, monkeypatch, with_all)
+    if host is not None:
+        assert params_equal(P, host['P']) and (cfg['cand'] != 'track' or tk == host['tk']), (vars(P), vars(host['P']), tk, host['tk'])
     off, _, _, _, _ = _device(cfg, inp, dtype, net, PRUNE_OFF_NET if net else PRUNE_OFF, monkeypatch, False)
     for k in ('x', 'u', 'cost', 'argmin', 'status'):
         assert np.array_equal(got[k], off[k], equal_nan=True), (tag, 'pruning off changes', k, cfg)
@@ -237,42 +117,30 @@ def _check(cfg, inp, dtype, golden_dir, monkeypatch, seed=0, floor=None, tag='',
         thr = fin & (np.abs(first['g'][:n] - P.feas_tol) > vmargin)
         assert ((allc['viol'] == 0) == first['feas'][:n])[thr].all(), (tag, cfg)
     # the solve: set aside a scenario that ANY pass decided inside eps of a threshold, a near-tie or a break-point
-    amb = np.zeros(B, dtype=bool)
-    for r in passes:
-        amb |= ambiguous_mask(r, P, eps, tie, eps, O.breakpoint_distance(x0, r['U'], kp, P))
-    ok = ~amb
-    assert (got['status'][ok] == ref['status'][ok]).all(), (tag, cfg)
-    assert (got['argmin'][ok] == ref['argmin'][ok]).all(), (tag, cfg)
-    sol = ok & (ref['status'] == 0)
-    if sol.any():
-        assert rel_err(got['x'][sol], ref['x'][sol]).max() <= tol_x, (tag, cfg)
-        assert rel_err(got['u'][sol], ref['u'][sol]).max() <= max(tol, utol), (tag, cfg)
-        assert rel_err(got['cost'][sol], ref['cost'][sol]).max() <= (2e-5 if f32 and net else tol), (tag, cfg)
-    bad = got['status'] == 1
-    assert np.isnan(got['x'][bad]).all() and np.isinf(got['cost'][bad]).all() and (got['argmin'][bad] == -1).all()
-    share = ok.mean()
-    print(f'{tag} {dtype}: compared share {share:.3f} ({ok.sum()}/{B}), solved {(got["status"] == 0).mean():.2f}  '
-          f'{cfg["cand"]} N={cfg["N"]} C={C} dt={cfg["dt"]} {cfg["limits"]}')
-    if floor is not None:
-        assert share >= floor, (tag, share, cfg)
-    return share
+    m = compare_solve(got, passes, P, x0, kp, eps=eps, tie=tie, tol=tol, utol=utol, xtol=tol_x, ctol=2e-5 if f32 and net else tol,
+                      share=share, tie_share=0.0, min_solved=min_solved, label=f'{tag} {dtype} {cfg["cand"]} N={cfg["N"]} C={C} '
+                      f'dt={cfg["dt"]} {cfg["limits"]}')
+    return m['compared'] / B
+
+
+def _draw_check(seed, dtype, golden_dir, monkeypatch):
+    cfg = _draw(seed)
+    case = limits_case(seed, dtype)
+    _check(cfg, _inputs(cfg, seed), dtype, golden_dir, monkeypatch, seed, SHARE.get((dtype, seed), 1.0), f'seed {seed}',
+           min_solved=floors(case['key'])['min_solved'], host=case)
 
 
 # ----------------------------------------------------------------------------- part 1: the seeded draws
 @pytest.mark.gpu
 @pytest.mark.parametrize('seed', range(N_SEEDS))
 def test_limits_draw_matches_oracle(seed, golden_dir, monkeypatch):
-    cfg = _draw(seed)
-    _check(cfg, _inputs(cfg, seed), 'f64', golden_dir, monkeypatch, seed, _floor(SHARE.get(('f64', seed), 1.0), cfg['B']),
-           f'seed {seed}')
+    _draw_check(seed, 'f64', golden_dir, monkeypatch)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('seed', F32_SEEDS)
 def test_limits_draw_matches_oracle_f32(seed, golden_dir, monkeypatch):
-    cfg = _draw(seed)
-    _check(cfg, _inputs(cfg, seed), 'f32', golden_dir, monkeypatch, seed, _floor(SHARE.get(('f32', seed), 1.0), cfg['B']),
-           f'seed {seed}')
+    _draw_check(seed, 'f32', golden_dir, monkeypatch)
 
 
 def _old_device_cap(cfg):
@@ -344,7 +212,7 @@ def test_obstacles_at_the_reach_bound(lim, cand, dtype, golden_dir, monkeypatch)
     # roll-outs' difference grows with speed times horizon -- measured 2.8e-5 (relative, |ref| floored at 1) on this batch,
     # against the 1e-5 that holds at the reference's limits and in every draw above.  The bar here is 5e-5.
     xtol = 5e-5 if (dtype, cand, lim.get('a_max')) == ('f32', 'track', 20.0) else None
-    _check(cfg, inp, dtype, golden_dir, monkeypatch, floor=_floor(share, cfg['B']), tag=f'reach {lim}', xtol=xtol)
+    _check(cfg, inp, dtype, golden_dir, monkeypatch, share=share, tag=f'reach {lim}', xtol=xtol)
 
 
 def _slack(lim, N, dt, kv):
@@ -386,7 +254,7 @@ def test_progress_slack_at_its_edges(lim, dtype, golden_dir, monkeypatch):
     inp['kparams'] = kp
     inp['x0'][:, 3] *= 0.2          # a lane error this curvature's feasible roll-outs can hold
     # four scenarios set aside by the break-point rule: side 5 of the q cases puts b0 on s_0 itself
-    _check(cfg, inp, dtype, golden_dir, monkeypatch, floor=_floor(92 / 96, cfg['B']), tag=f'slack {lim}')
+    _check(cfg, inp, dtype, golden_dir, monkeypatch, share=92 / 96, tag=f'slack {lim}')
 
 
 @pytest.mark.gpu
@@ -411,4 +279,4 @@ def test_f32_incumbent_bound_with_braking_to_a_negative_terminal_speed(jerk, gol
     inp['u_ws'] = ws
     inp['flags'] = inp['flags'] | np.where(np.arange(B) % 4 != 0, 2, 0).astype(np.uint32)
     for dtype in ('f32', 'f64'):
-        _check(cfg, inp, dtype, golden_dir, monkeypatch, floor=_floor(1.0, cfg['B']), tag=f'braking jerk={jerk}')
+        _check(cfg, inp, dtype, golden_dir, monkeypatch, share=1.0, tag=f'braking jerk={jerk}')

@@ -13,23 +13,21 @@ its own batches (two per lane, alternating between rounds), B = 4096 per solve a
 import numpy as np
 import pytest
 
-from helpers import F32_EPS, REL_TOL, oracle_params
-from test_gpu_fullsize import _check_subsample, _cinf, _net
+import parity_cases as PC
+from helpers import oracle_params, params_equal
 
 pytestmark = pytest.mark.gpu
 
-B = 4096
-ROUNDS = 4                       # >= 3 rounds of solves in flight per lane, none of them waited for
+B = PC.OVERLAP_B
+ROUNDS = PC.OVERLAP_ROUNDS
 KEYS = ('x', 'u', 'cost', 'argmin', 'status')
-# (dtype, candidate family, value net of scenario sc or 0); lane q takes LANES[q % 5]
-LANES = [('f64', 'lattice', 0), ('f64', 'track', 0), ('f32', 'lattice', 0), ('f64', 'lattice', 1), ('f32', 'track', 0)]
 
 
 def _solver(igt, golden_dir, dtype, cand, gt, concurrency):
     s = igt.BatchSolver(dtype=dtype, cand_mode=cand, cost_mode='value_net' if gt else 'progress')
-    s.set_cinf(*_cinf())
+    s.set_cinf(*PC.cinf_default())
     if gt:
-        s.set_value_net(layers=_net(golden_dir, gt), Wn=np.eye(6), mu_f=np.zeros(6), sigma_t=1.0, mu_t=0.0)
+        s.set_value_net(layers=PC.nets(gt), Wn=np.eye(6), mu_f=np.zeros(6), sigma_t=1.0, mu_t=0.0)
     s.set_concurrency(concurrency)
     return s
 
@@ -50,12 +48,10 @@ def _empty_out(torch, dtype):
 def test_overlapped_solves_equal_the_same_batches_solved_alone(golden_dir, F):
     import torch
     import igtmpc as igt
-    from igtmpc.scenarios import make_batch
     igt.load_library()
-    cfg = [LANES[q % len(LANES)] for q in range(F)]
-    # two batches per lane, no two lanes share one (make_batch(offset=...) is the generator's per-shard path)
-    host = [[make_batch(B, dtype=np.float64 if d == 'f64' else np.float32, offset=(2 * q + v + 1) * B) for v in range(2)]
-            for q, (d, _, _) in enumerate(cfg)]
+    assert F <= PC.OVERLAP_MAX_F
+    cfg = [PC.overlap_lane(q) for q in range(F)]
+    host = [[PC.overlap_batch(q, v) for v in range(2)] for q in range(F)]       # two batches per lane, no two lanes share one
     dargs = [[_device_args(torch, host[q][v], cfg[q][2]) for v in range(2)] for q in range(F)]
     solvers = [_solver(igt, golden_dir, *cfg[q], concurrency=F) for q in range(F)]
     streams = [torch.cuda.Stream() for _ in range(F)]
@@ -102,9 +98,10 @@ def test_overlapped_solves_equal_the_same_batches_solved_alone(golden_dir, F):
             assert 0.5 < (got[q][r]['status'] == 0).mean() < 1.0
             for k in KEYS:
                 assert np.array_equal(got[q][r][k], alone[r % 2][k], equal_nan=True), (F, q, cfg[q], r, k)
-        # ... and the overlapped answers are the oracle's (round ROUNDS-1 of batch (ROUNDS-1) % 2)
-        v = (ROUNDS - 1) % 2
-        idx = np.sort(np.random.default_rng(5 + q).choice(B, 256, replace=False))
-        tol, eps = (1e-9, 1e-9) if dtype == 'f64' else (REL_TOL, F32_EPS if cand == 'lattice' else 2e-5)
-        net = dict(layers=_net(golden_dir, gt), Wn=np.eye(6), mu_f=np.zeros(6), sigma_t=1.0, mu_t=0.0) if gt else None
-        _check_subsample(host[q][v], got[q][ROUNDS - 1], idx, P, tol, eps, net, cand)
+        # ... and the overlapped answers are the oracle's (round ROUNDS-1 of batch (ROUNDS-1) % 2) on the lane's 256-scenario
+        # subsample, with the floors recorded for it (parity_cases.overlap_case)
+        case, idx = PC.overlap_case(q, host[q][(ROUNDS - 1) % 2])
+        assert params_equal(P, case['P'])
+        m = PC.check_case(case, {k: got[q][ROUNDS - 1][k][idx] for k in KEYS}, PC.oracle_passes(case))
+        # the bounds this comparison has always asserted, next to the recorded ones
+        assert m['compared'] / m['B'] > (0.99 if cand == 'lattice' else 0.85) and m['solved'] > 100, m

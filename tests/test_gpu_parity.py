@@ -19,7 +19,8 @@ import np_oracle as O
 from igtmpc._lib import (DEV_ALL_ROWS, DEV_EXACT64, DEV_KEEP_QUEUES, DEV_NO_BOUND, DEV_NO_CAPTURE, DEV_NO_EARLY_EXIT, DEV_NO_FAR,
                          DEV_NO_PRUNE, DEV_NO_QUEUE_ORDER, DEV_NO_SEG_EMIT, DEV_NO_SLICES, DEV_NO_STEAL, DEV_NO_STEER_TABLE,
                          DEV_SEPARATE_QUEUES, DEV_STEER_SLICES, DEV_WAVES3, DEV_WHOLE_COLUMNS)
-from helpers import F32_EPS, F32_TIE, REL_TOL, ambiguous_mask, oracle_params, oracle_solve, rel_err, verdict_margins
+import parity_cases as PC
+from helpers import F32_EPS, F32_TIE, REL_TOL, oracle_params, oracle_solve, rel_err, verdict_margins
 
 pytestmark = pytest.mark.gpu
 
@@ -91,39 +92,13 @@ def test_rollout_all_f32_within_1e5(igt):
 # ----------------------------------------------------------------------------- solves
 @pytest.mark.parametrize('dtype,tol,eps,eps_tie', [('f64', 1e-9, 1e-9, 1e-9), ('f32', REL_TOL, F32_EPS, F32_TIE)])
 def test_solve_matches_oracle(igt, dtype, tol, eps, eps_tie):
-    npdt = np.float64 if dtype == 'f64' else np.float32
-    b = _batch(512, npdt)
-    with igt.BatchSolver(dtype=dtype) as s:
-        P = oracle_params(s)
-        s.set_cinf(*_cinf())
-        got = s.solve(*_args(b))
-    ref = oracle_solve(b, P, cinf=_cinf())
-    kp = b['kparams'].astype(np.float64)[:, None, :]
-    x0 = O.apply_flags(b['x0'].astype(np.float64), b['flags'])[:, None, :]
-    bp = O.breakpoint_distance(x0, ref['U'], kp, P)
-    amb = ambiguous_mask(ref, P, eps, eps_tie, eps, bp)
-    print(f'{dtype}: scenarios set aside (threshold / break-point within {eps:g}, tie within {eps_tie:g}): {amb.sum()} of {len(amb)}')
-    assert amb.mean() < 0.005
-    ok = ~amb
-    assert (got['status'][ok] == ref['status'][ok]).all()
-    assert (got['argmin'][ok] == ref['argmin'][ok]).all()
-    sol = ok & (ref['status'] == 0)
-    assert sol.sum() > 50, 'sample has too few solvable scenarios to mean anything'
-    assert rel_err(got['x'][sol], ref['x'][sol]).max() <= tol
-    assert rel_err(got['u'][sol], ref['u'][sol]).max() <= max(tol, 1e-7)
-    assert rel_err(got['cost'][sol], ref['cost'][sol]).max() <= tol
-    # ambiguous scenarios: whatever was picked must still be a near-optimal, near-feasible candidate
-    for i in np.nonzero(amb)[0]:
-        c = got['argmin'][i]
-        if c >= 0:
-            best = np.where(ref['feas'][i], ref['J'][i], np.inf).min()
-            assert ref['g'][i, c] <= P.feas_tol + 10 * eps_tie
-            assert ref['J'][i, c] <= best + 10 * eps_tie or not np.isfinite(best)
-    # status-1 rows carry NaN / inf / -1
-    bad = got['status'] == 1
-    if bad.any():
-        assert np.isnan(got['x'][bad]).all() and np.isnan(got['u'][bad]).all()
-        assert np.isinf(got['cost'][bad]).all() and (got['argmin'][bad] == -1).all()
+    case = PC.solve_case(dtype)
+    assert (tol, eps, eps_tie) == (case['tol'], case['eps'], case['tie'])
+    with PC.open_solver(igt, case) as s:
+        got = PC.device_solve(s, case)
+    m = PC.check_case(case, got, PC.oracle_passes(case))
+    assert 1.0 - m['compared'] / m['B'] < 0.005
+    assert m['solved'] > 50, 'sample has too few solvable scenarios to mean anything'
 
 
 @pytest.mark.parametrize('B,cand_mode,dtype', [(64, 'lattice', 'f32'), (64, 'ramp_hold', 'f32'), (2304, 'lattice', 'f32'),
@@ -273,28 +248,16 @@ def test_all_infeasible_reports_status_1(igt):
     assert np.isnan(out['x']).all() and np.isinf(out['cost']).all()
 
 
-@pytest.mark.parametrize('N,n_rk4,C,n_obs', [(10, 4, 256, 1), (40, 4, 64, 1), (20, 7, 64, 1), (20, 4, 1024, 1),
-                                             (20, 4, 256, 0), (20, 2, 256, 2), (64, 4, 256, 1), (64, 4, 64, 3), (64, 3, 1024, 1),
-                                             (20, 4, 256, 4), (20, 4, 256, 3)])
+@pytest.mark.parametrize('N,n_rk4,C,n_obs', PC.SHAPES_F64)
 def test_other_shapes_f64(igt, N, n_rk4, C, n_obs):
     """... up to what include/igtmpc.h advertises: IGT_MAX_N = 64 (with the slice's steering table in LDS, C = 256 / 1024, and
-    without, C = 64) and IGT_MAX_OBS = 4 obstacles."""
-    b = _batch(24, np.float64, N=N)
-    obs = np.concatenate([b['obs_xy']] * max(n_obs, 1), axis=1)[:, :n_obs]
-    for m in range(1, n_obs):            # further vehicles: the first one's forecast, displaced
-        obs[:, m, 0] += 3.0 * m
-        obs[:, m, 1] -= 2.0 * (m - 1)
-    with igt.BatchSolver(dtype='f64', N=N, n_rk4=n_rk4, C=C, n_obs=n_obs) as s:
-        P = oracle_params(s)
-        got = s.solve(b['x0'], b['u_prev'], b['kparams'], b['flags'], np.ascontiguousarray(obs))
-    bb = dict(b, obs_xy=obs)
-    ref = oracle_solve(bb, P, C=C)
-    amb = ambiguous_mask(ref, P, 1e-9, 1e-9)
-    ok = ~amb
-    assert (got['argmin'][ok] == ref['argmin'][ok]).all()
-    sol = ok & (ref['status'] == 0)
-    if sol.any():
-        assert rel_err(got['x'][sol], ref['x'][sol]).max() < 1e-9
+    without, C = 64) and IGT_MAX_OBS = 4 obstacles.  From N = 40 on at limits under which the lattice has feasible members
+    (parity_cases.LONG_LIMITS: at the reference's, no candidate of 64 steps stays in the lane and nothing would be compared);
+    N = 33 is solved at the reference's own."""
+    case = PC.shape_case('f64', N, n_rk4, C, n_obs)
+    with PC.open_solver(igt, case) as s:
+        got = PC.device_solve(s, case)
+    PC.check_case(case, got, PC.oracle_passes(case))
 
 
 def test_bad_arguments_fail_loudly(igt):
@@ -411,43 +374,31 @@ def _nets(golden_dir):
 
 @pytest.mark.parametrize('sc,dtype,tol,eps', [(1, 'f64', 1e-9, 1e-9), (3, 'f64', 1e-9, 1e-9),
                                               (1, 'f32', REL_TOL, 2e-5), (3, 'f32', REL_TOL, 2e-5)])
-def test_value_net_cost_matches_oracle(igt, golden_dir, sc, dtype, tol, eps):
+def test_value_net_cost_matches_oracle(igt, sc, dtype, tol, eps):
     """gt_mpc cost (mpc.py:367-369) with the shipped checkpoints V_GT_sc1 (2 hidden layers) and V_GT_sc3 (3),
     a non-trivial whitening / de-normalisation (synthetic: the reference's statistics are not shipped)."""
-    layers = _nets(golden_dir)[sc]
-    rng = np.random.default_rng(5)
-    Wn = np.eye(6) + 0.05 * rng.normal(size=(6, 6))
-    mu_f = np.array([20.0, 2.5, 0.0, 0.0, 0.0, 0.0]) + 0.1 * rng.normal(size=6)
-    net = dict(layers=layers, Wn=Wn, mu_f=mu_f, sigma_t=3.0, mu_t=-1.5)
-    npdt = np.float64 if dtype == 'f64' else np.float32
-    b = _batch(160, npdt)
+    case = PC.value_net_case(sc, dtype)
+    assert (tol, eps, eps) == (case['tol'], case['eps'], case['tie'])
+    a, net = case['args'], case['net']
     with igt.BatchSolver(dtype=dtype, cost_mode='value_net') as s:
-        P = oracle_params(s)
-        s.set_cinf(*_cinf())
+        assert PC.params_equal(oracle_params(s), case['P'])
+        s.set_cinf(*case['cinf'])
         with pytest.raises(igt.IgtError):
-            s.solve(*_args(b), b['tv_sv'], b['enc'])          # net not loaded yet
+            PC.device_solve(s, case)          # net not loaded yet
         s.set_value_net(**net)
-        got = s.solve(*_args(b), b['tv_sv'], b['enc'])
-        allc = s.rollout_all(*[a[:32] for a in _args(b)], b['tv_sv'][:32], b['enc'][:32], want_X=False, want_U=False)
-    f = lambda k: np.asarray(b[k], dtype=np.float64)
-    ref = O.solve_batch(f('x0'), f('u_prev'), f('kparams'), b['flags'], f('obs_xy'), *_cinf(), P, net=net,
-                        tv_sv=f('tv_sv'), enc=f('enc'), return_all=True)
+        got = PC.device_solve(s, case)
+        pos, _ = PC.solve_args(case, 32)
+        allc = s.rollout_all(*pos, want_X=False, want_U=False)
+    oracle = PC.oracle_passes(case)
+    ref = oracle[0][0]
     fin = np.isfinite(ref['J'][:32])
     assert rel_err(allc['cost'][fin], ref['J'][:32][fin]).max() <= tol
-    kp = f('kparams')[:, None, :]
-    x0 = O.apply_flags(f('x0'), b['flags'])[:, None, :]
-    bp = O.breakpoint_distance(x0, ref['U'], kp, P)
-    amb = ambiguous_mask(ref, P, eps, eps, eps, bp)
-    ok = ~amb
-    assert ok.mean() > 0.85
-    assert (got['status'][ok] == ref['status'][ok]).all()
-    assert (got['argmin'][ok] == ref['argmin'][ok]).all()
-    sol = ok & (ref['status'] == 0)
-    assert sol.sum() > 20
-    assert rel_err(got['cost'][sol], ref['cost'][sol]).max() <= tol
-    assert rel_err(got['x'][sol], ref['x'][sol]).max() <= tol
+    m = PC.check_case(case, got, oracle)
+    assert m['solved'] > 20
     # the terminal value really matters: it changes the winner w.r.t. the progress cost on this sample
-    prog = O.solve_batch(f('x0'), f('u_prev'), f('kparams'), b['flags'], f('obs_xy'), *_cinf(), P)
+    f = lambda k: np.asarray(a[k], dtype=np.float64)
+    prog = O.solve_batch(f('x0'), f('u_prev'), f('kparams'), a['flags'], f('obs'), *case['cinf'], case['P'])
+    sol = ref['status'] == 0
     assert (prog['argmin'][sol] != ref['argmin'][sol]).any()
 
 
@@ -456,116 +407,48 @@ def test_value_net_cost_matches_oracle(igt, golden_dir, sc, dtype, tol, eps):
 def test_ramp_hold_with_refinement_matches_oracle(igt, dtype, tol, eps):
     """IGT_CAND_RAMP_HOLD with 2 refinement passes: every pass re-centres on the previous winner, so a scenario
     counts only if NO pass decided it inside float noise."""
-    npdt = np.float64 if dtype == 'f64' else np.float32
-    b = _batch(384, npdt)
-    f = lambda k: np.asarray(b[k], dtype=np.float64)
-    with igt.BatchSolver(dtype=dtype, cand_mode='ramp_hold') as s0:
-        P = oracle_params(s0)
-        s0.set_cinf(*_cinf())
-        first = s0.solve(*_args(b))
-        all0 = s0.rollout_all(*[a[:24] for a in _args(b)], want_X=False)
-    with igt.BatchSolver(dtype=dtype, cand_mode='ramp_hold', refine_iters=2) as s2:
-        s2.set_cinf(*_cinf())
-        got = s2.solve(*_args(b))
-    passes = O.solve_batch_refined(f('x0'), f('u_prev'), f('kparams'), b['flags'], f('obs_xy'), *_cinf(), P,
-                                   refine_iters=2)
-    kp = f('kparams')[:, None, :]
-    x0 = O.apply_flags(f('x0'), b['flags'])[:, None, :]
-    amb = np.zeros(384, bool)        # decided inside float noise in some pass (thresholds, break-points, ties)
-    edge = np.zeros(384, bool)       # ... thresholds / break-points only (near-ties are all acceptable answers)
-    amb_first = None
-    for r in passes:
-        bp = O.breakpoint_distance(x0, r['U'], kp, P)
-        amb |= ambiguous_mask(r, P, eps, eps, eps, bp)
-        edge |= ambiguous_mask(r, P, eps, eps, eps, bp, ties=False)
-        if amb_first is None:
-            amb_first = amb.copy()
+    case = PC.ramp_hold_refined_case(dtype)
+    assert (tol, eps, eps) == (case['tol'], case['eps'], case['tie'])
+    with PC.open_solver(igt, case, refine=0) as s0:
+        first = PC.device_solve(s0, case)
+        pos, _ = PC.solve_args(case, 24)
+        all0 = s0.rollout_all(*pos, want_X=False)
+    with PC.open_solver(igt, case) as s2:
+        got = PC.device_solve(s2, case)
+    oracle = PC.oracle_passes(case)
+    passes = oracle[0]
     # pass 0 alone
     assert rel_err(all0['U'], passes[0]['U'][:24]).max() < 1e-7
-    ok0 = ~amb_first
-    assert ok0.mean() > 0.85
-    assert (first['argmin'][ok0] == passes[0]['argmin'][ok0]).all()
+    PC.check_case(case, first, oracle, first=True)
     # after two refinements: the refined grids are so fine that near-ties are the rule; where every pass was
     # clear-cut the winner must be identical, elsewhere (ties only) the COST must agree
-    ref = passes[-1]
-    ok = ~amb
-    assert ok.sum() > 20
-    assert (got['status'][ok] == ref['status'][ok]).all()
-    assert (got['argmin'][ok] == ref['argmin'][ok]).all()
-    sol = ok & (ref['status'] == 0)
-    assert rel_err(got['x'][sol], ref['x'][sol]).max() <= tol
-    assert rel_err(got['u'][sol], ref['u'][sol]).max() <= max(tol, 1e-7)
-    assert rel_err(got['cost'][sol], ref['cost'][sol]).max() <= tol
-    tie = ~edge
-    assert tie.mean() > 0.80
-    assert (got['status'][tie] == ref['status'][tie]).all()
-    st = tie & (ref['status'] == 0)
-    assert rel_err(got['cost'][st], ref['cost'][st]).max() <= max(10 * tol, 1e-7)
-    # the returned trajectory is the rollout of the returned controls
-    X = O.rollout_frenet(x0[st, 0], got['u'][st].astype(np.float64), kp[st, 0], P)
-    bpu = O.breakpoint_distance(x0[st, 0], got['u'][st].astype(np.float64), kp[st, 0], P)
-    e = rel_err(got['x'][st], X).max(axis=(-1, -2))
-    assert e[bpu > F32_EPS].max() <= tol
+    m = PC.check_case(case, got, oracle)
+    assert m['compared'] > 20
     # refinement never makes the answer worse, and improves it somewhere
+    ref = passes[-1]
     both = (passes[0]['status'] == 0) & (ref['status'] == 0)
     assert (ref['cost'][both] <= passes[0]['cost'][both] + 1e-12).all()
     assert (ref['cost'][both] < passes[0]['cost'][both] - 1e-6).any()
 
 
-@pytest.mark.parametrize('N,n_rk4,C,n_obs', [(10, 4, 256, 1), (40, 4, 64, 1), (20, 7, 64, 1), (20, 4, 1024, 1),
-                                             (20, 4, 256, 0), (20, 2, 256, 2), (20, 1, 256, 1), (64, 4, 256, 1), (64, 4, 64, 3),
-                                             (20, 4, 256, 4)])
+@pytest.mark.parametrize('N,n_rk4,C,n_obs', PC.SHAPES_F32)
 def test_other_shapes_f32(igt, N, n_rk4, C, n_obs):
     """float path at other discretisations (n_rk4 <= 2 switches to the longer offset polynomials), odd chunk
-    counts (C = 64) and many slices (C = 1024)."""
-    b = _batch(48, np.float32, N=N)
-    obs = np.concatenate([b['obs_xy']] * max(n_obs, 1), axis=1)[:, :n_obs]
-    for m in range(1, n_obs):
-        obs[:, m, 0] += 3.0 * m
-        obs[:, m, 1] -= 2.0 * (m - 1)
-    obs = np.ascontiguousarray(obs)
-    with igt.BatchSolver(dtype='f32', N=N, n_rk4=n_rk4, C=C, n_obs=n_obs) as s:
-        P = oracle_params(s)
-        got = s.solve(b['x0'], b['u_prev'], b['kparams'], b['flags'], obs)
-    bb = dict(b, obs_xy=obs)
-    ref = oracle_solve(bb, P, C=C)
-    kp = b['kparams'].astype(np.float64)[:, None, :]
-    x0 = O.apply_flags(b['x0'].astype(np.float64), b['flags'])[:, None, :]
-    bp = O.breakpoint_distance(x0, ref['U'], kp, P)
-    amb = ambiguous_mask(ref, P, 2e-5, 2e-5, 2e-5, bp)
-    ok = ~amb
-    assert ok.mean() > 0.7
-    assert (got['argmin'][ok] == ref['argmin'][ok]).all() and (got['status'][ok] == ref['status'][ok]).all()
-    sol = ok & (ref['status'] == 0)
-    if sol.any():
-        assert rel_err(got['x'][sol], ref['x'][sol]).max() <= REL_TOL
-        assert rel_err(got['cost'][sol], ref['cost'][sol]).max() <= REL_TOL
+    counts (C = 64) and many slices (C = 1024).  From N = 40 on at limits under which the lattice has feasible members
+    (parity_cases.LONG_LIMITS); N = 33 is solved at the reference's own."""
+    case = PC.shape_case('f32', N, n_rk4, C, n_obs)
+    with PC.open_solver(igt, case) as s:
+        got = PC.device_solve(s, case)
+    PC.check_case(case, got, PC.oracle_passes(case))
 
 
-def test_value_net_with_ramp_hold_refinement_f64(igt, golden_dir):
+def test_value_net_with_ramp_hold_refinement_f64(igt):
     """gt_mpc cost + ramp-hold candidates + one refinement pass (per-chunk partials feed the refinement)."""
-    layers = _nets(golden_dir)[1]
-    net = dict(layers=layers, Wn=np.eye(6), mu_f=np.zeros(6), sigma_t=1.0, mu_t=0.0)
-    b = _batch(96, np.float64)
-    f = lambda k: np.asarray(b[k], dtype=np.float64)
-    with igt.BatchSolver(dtype='f64', cost_mode='value_net', cand_mode='ramp_hold', refine_iters=1) as s:
-        P = oracle_params(s)
-        s.set_cinf(*_cinf())
-        s.set_value_net(**net)
-        got = s.solve(*_args(b), b['tv_sv'], b['enc'])
-    passes = O.solve_batch_refined(f('x0'), f('u_prev'), f('kparams'), b['flags'], f('obs_xy'), *_cinf(), P,
-                                   refine_iters=1, net=net, tv_sv=f('tv_sv'), enc=f('enc'))
-    amb = np.zeros(96, bool)
-    for r in passes:
-        amb |= ambiguous_mask(r, P, 1e-9, 1e-9)
-    ok = ~amb
-    ref = passes[-1]
-    assert ok.mean() > 0.9
-    assert (got['argmin'][ok] == ref['argmin'][ok]).all() and (got['status'][ok] == ref['status'][ok]).all()
-    sol = ok & (ref['status'] == 0)
-    assert sol.sum() > 10
-    assert rel_err(got['x'][sol], ref['x'][sol]).max() < 1e-9
-    assert rel_err(got['cost'][sol], ref['cost'][sol]).max() < 1e-9
+    case = PC.value_net_ramp_hold_case()
+    with PC.open_solver(igt, case) as s:
+        got = PC.device_solve(s, case)
+    m = PC.check_case(case, got, PC.oracle_passes(case))
+    assert m['solved'] > 10
 
 
 @pytest.mark.parametrize('dtype,cand', [('f64', 'lattice'), ('f64', 'track'), ('f32', 'lattice'), ('f32', 'track')])
@@ -792,11 +675,7 @@ def test_value_bound_pruning_changes_nothing(igt, golden_dir, sc, monkeypatch):
     the value network before the matrix-core kernel runs (value_bound_kernel / value_prune_kernel).  Entries that are dropped
     cannot win, so the solve with pruning == the solve without (DEV_NO_PRUNE), bit for bit -- with a non-trivial
     whitening and a NEGATIVE sigma_t as well (the bound takes the upper end whatever the sign)."""
-    layers = _nets(golden_dir)[sc]
-    rng = np.random.default_rng(9)
-    nets = [dict(layers=layers, Wn=np.eye(6), mu_f=np.zeros(6), sigma_t=1.0, mu_t=0.0),
-            dict(layers=layers, Wn=np.eye(6) + 0.05 * rng.normal(size=(6, 6)),
-                 mu_f=np.array([20.0, 2.5, 0.0, 0.0, 0.0, 0.0]), sigma_t=-2.0, mu_t=0.7)]
+    nets = PC.value_bound_nets(sc)
     b = _batch(768, np.float64)
     for net in nets:
         outs = []
@@ -811,19 +690,10 @@ def test_value_bound_pruning_changes_nothing(igt, golden_dir, sc, monkeypatch):
         for k in ('x', 'u', 'cost', 'argmin', 'status'):
             assert np.array_equal(outs[0][k], outs[1][k], equal_nan=True), k
     # ... and the pruned solve is the oracle's answer (one scenario subset, sigma_t = 1)
-    P = O.Params(N=20)
-    f = lambda k: np.asarray(b[k][:64], dtype=np.float64)
-    ref = O.solve_batch_refined(f('x0'), f('u_prev'), f('kparams'), b['flags'][:64], f('obs_xy'), *_cinf(), P, cand='track',
-                                net=nets[0], tv_sv=f('tv_sv'), enc=f('enc'))[0]
-    with igt.BatchSolver(dtype='f64', cost_mode='value_net', cand_mode='track') as s:
-        s.set_cinf(*_cinf())
-        s.set_value_net(**nets[0])
-        got = s.solve(*[a[:64] for a in _args(b)], b['tv_sv'][:64], b['enc'][:64])
-    amb = ambiguous_mask(ref, P, 1e-9, 1e-9)
-    ok = ~amb
-    assert ok.mean() > 0.8 and (got['argmin'][ok] == ref['argmin'][ok]).all()
-    sol = ok & (ref['status'] == 0)
-    assert rel_err(got['cost'][sol], ref['cost'][sol]).max() < 1e-9
+    case = PC.value_bound_case(sc)
+    with PC.open_solver(igt, case) as s:
+        got = PC.device_solve(s, case)
+    PC.check_case(case, got, PC.oracle_passes(case))
 
 
 # ----------------------------------------------------------------------------- warm start (augment_prev_sol)
@@ -832,62 +702,37 @@ def test_warm_started_ramp_hold_matches_oracle(igt, dtype, tol, eps):
     """igt_solve_batch_ws_* / igt_rollout_batch_ws_*: ramp-hold targets centred on a warm start (the previous solution
     shifted by one step, utils.py:354-363) where flags carry IGT_FLAG_WARM, on u_prev held elsewhere; one refinement
     pass on top.  Every candidate's controls and trajectory, then the solve."""
-    npdt = np.float64 if dtype == 'f64' else np.float32
-    B = 192
-    b = _batch(B, npdt)
-    f = lambda k: np.asarray(b[k], dtype=np.float64)
-    P0 = O.Params()
-    # a plausible previous solution per scenario: some lattice candidate rolled from u_prev, then shifted
-    prev = O.candidates_lattice(f('u_prev'), P0)[np.arange(B), (np.arange(B) * 37) % 256]       # [B,2,N]
-    u_ws = np.ascontiguousarray(O.shift_controls(prev).astype(npdt))
-    u_prev = np.ascontiguousarray(prev[:, :, 0].astype(npdt))                                     # the applied input
-    flags = b['flags'] | np.where(np.arange(B) % 3 != 0, 2, 0).astype(np.uint32)
-    args = (b['x0'], u_prev, b['kparams'], flags, b['obs_xy'])
-    with igt.BatchSolver(dtype=dtype, cand_mode='ramp_hold') as s0:
-        P = oracle_params(s0)
-        s0.set_cinf(*_cinf())
-        all0 = s0.rollout_all(*[a[:48] for a in args], u_ws=u_ws[:48])
-        first = s0.solve(*args, u_ws=u_ws)
-    with igt.BatchSolver(dtype=dtype, cand_mode='ramp_hold', refine_iters=1) as s1:
-        s1.set_cinf(*_cinf())
-        got = s1.solve(*args, u_ws=u_ws)
-    up = u_prev.astype(np.float64)
-    passes = O.solve_batch_refined(f('x0'), up, f('kparams'), flags, f('obs_xy'), *_cinf(), P, refine_iters=1,
-                                   u_ws=u_ws.astype(np.float64))
+    case = PC.warm_case(dtype, 'ramp_hold')
+    assert (tol, eps, eps) == (case['tol'], case['eps'], case['tie'])
+    a, P = case['args'], case['P']
+    u_ws, flags = a['u_ws'], a['flags']
+    with PC.open_solver(igt, case, refine=0) as s0:
+        pos, kw = PC.solve_args(case, 48)
+        all0 = s0.rollout_all(*pos, **kw)
+        first = PC.device_solve(s0, case)
+    with PC.open_solver(igt, case) as s1:
+        got = PC.device_solve(s1, case)
+    oracle = PC.oracle_passes(case)
+    passes, x0, kp = oracle
     r0 = passes[0]
     # the warm start itself is candidate (G/2, G/2) wherever the scenario carries one
     w = (flags & 2) != 0
     assert rel_err(r0['U'][w, 8 * 16 + 8], u_ws[w]).max() < 1e-7
     assert not np.allclose(r0['U'][~w, 8 * 16 + 8], u_ws[~w])
     assert rel_err(all0['U'], r0['U'][:48]).max() <= (1e-14 if dtype == 'f64' else 1e-7)
-    kp = f('kparams')[:, None, :]
-    x0 = O.apply_flags(f('x0'), flags)[:, None, :]
-    bp = O.breakpoint_distance(x0, r0['U'], kp, P)
-    clear = bp[:48] > eps
+    bp = O.breakpoint_distance(x0[:48], r0['U'][:48], kp[:48], P)
+    clear = bp > eps
     err = rel_err(all0['X'], r0['X'][:48]).max(axis=(-1, -2))
     assert err[clear].max() <= tol
-    amb0 = ambiguous_mask(r0, P, eps, eps, eps, bp)
-    ok0 = ~amb0
-    assert ok0.mean() > 0.85
-    assert (first['argmin'][ok0] == r0['argmin'][ok0]).all() and (first['status'][ok0] == r0['status'][ok0]).all()
-    sol = ok0 & (r0['status'] == 0)
-    assert sol.sum() > 30
-    assert rel_err(first['x'][sol], r0['x'][sol]).max() <= tol
-    assert rel_err(first['cost'][sol], r0['cost'][sol]).max() <= tol
+    m0 = PC.check_case(case, first, oracle, first=True)
+    assert m0['solved'] > 30
     # refined pass: costs agree wherever no threshold / break-point decided a pass inside float noise
-    edge = np.zeros(B, bool)
-    for r in passes:
-        edge |= ambiguous_mask(r, P, eps, eps, eps, O.breakpoint_distance(x0, r['U'], kp, P), ties=False)
-    ref = passes[-1]
-    tie = ~edge
-    assert tie.mean() > 0.8
-    assert (got['status'][tie] == ref['status'][tie]).all()
-    st = tie & (ref['status'] == 0)
-    assert rel_err(got['cost'][st], ref['cost'][st]).max() <= max(10 * tol, 1e-7)
+    PC.check_case(case, got, oracle)
     # a warm start needs the ramp-hold family
     with igt.BatchSolver(dtype=dtype) as s2:
         with pytest.raises(igt.IgtError):
-            s2.solve(*args, u_ws=u_ws)
+            pos, kw = PC.solve_args(case)
+            s2.solve(*pos, **kw)
 
 
 # ----------------------------------------------------------------------------- tracking candidates (state-feedback steering)
@@ -897,59 +742,31 @@ def test_tracking_candidates_match_oracle(igt, dtype, tol, eps):
     (beta_cmd = -epsi - k_e ey + offset_j, rate-limited).  The controls come out of the roll-out, so every candidate's
     controls AND trajectory are compared with the oracle's interleaved generation; then the solve, with a warm start on
     two thirds of the scenarios and one refinement pass; and the family must beat ramp-hold on its own cost."""
-    npdt = np.float64 if dtype == 'f64' else np.float32
-    B = 192
-    b = _batch(B, npdt)
-    f = lambda k: np.asarray(b[k], dtype=np.float64)
-    P0 = O.Params()
-    prev = O.candidates_lattice(f('u_prev'), P0)[np.arange(B), (np.arange(B) * 37) % 256]
-    u_ws = np.ascontiguousarray(O.shift_controls(prev).astype(npdt))
-    u_prev = np.ascontiguousarray(prev[:, :, 0].astype(npdt))
-    flags = b['flags'] | np.where(np.arange(B) % 3 != 0, 2, 0).astype(np.uint32)
-    args = (b['x0'], u_prev, b['kparams'], flags, b['obs_xy'])
-    with igt.BatchSolver(dtype=dtype, cand_mode='track') as s0:
-        P = oracle_params(s0)
+    case = PC.warm_case(dtype, 'track')
+    assert (tol, eps, eps) == (case['tol'], case['eps'], case['tie'])
+    P = case['P']
+    with PC.open_solver(igt, case, refine=0) as s0:
         assert (s0.params.track_ke, s0.params.track_span, s0.params.track_beta_lim, s0.params.track_env) == (0.3, 0.1, 0.7, 1.0)
-        s0.set_cinf(*_cinf())
-        all0 = s0.rollout_all(*[a[:48] for a in args], u_ws=u_ws[:48])
-        first = s0.solve(*args, u_ws=u_ws)
-    with igt.BatchSolver(dtype=dtype, cand_mode='track', refine_iters=1) as s1:
-        s1.set_cinf(*_cinf())
-        got = s1.solve(*args, u_ws=u_ws)
-    with igt.BatchSolver(dtype=dtype, cand_mode='ramp_hold') as s2:
-        s2.set_cinf(*_cinf())
-        rh = s2.solve(*args, u_ws=u_ws)
-    up = u_prev.astype(np.float64)
-    passes = O.solve_batch_refined(f('x0'), up, f('kparams'), flags, f('obs_xy'), *_cinf(), P, refine_iters=1,
-                                   u_ws=u_ws.astype(np.float64), cand='track')
+        pos, kw = PC.solve_args(case, 48)
+        all0 = s0.rollout_all(*pos, **kw)
+        first = PC.device_solve(s0, case)
+    with PC.open_solver(igt, case) as s1:
+        got = PC.device_solve(s1, case)
+    with PC.open_solver(igt, dict(case, cand='ramp_hold'), refine=0) as s2:
+        rh = PC.device_solve(s2, case)
+    oracle = PC.oracle_passes(case)
+    passes, x0, kp = oracle
     r0 = passes[0]
-    kp = f('kparams')[:, None, :]
-    x0 = O.apply_flags(f('x0'), flags)[:, None, :]
-    bp = O.breakpoint_distance(x0, r0['U'], kp, P)
-    clear = bp[:48] > eps
+    bp = O.breakpoint_distance(x0[:48], r0['U'][:48], kp[:48], P)
+    clear = bp > eps
     # the steering depends on the rolled state: f64 agrees to rounding, f32 to the trajectory tolerance
     assert rel_err(all0['U'][clear], r0['U'][:48][clear]).max() <= (1e-12 if dtype == 'f64' else REL_TOL)
     assert rel_err(all0['X'], r0['X'][:48]).max(axis=(-1, -2))[clear].max() <= tol
     # steering differs between the accelerations of one offset column (it is placed, not timed)
     assert np.abs(r0['U'][:, 0 * 16 + 8, 1] - r0['U'][:, 15 * 16 + 8, 1]).max() > 1e-3
-    amb0 = ambiguous_mask(r0, P, eps, eps, eps, bp)
-    ok0 = ~amb0
-    assert ok0.mean() > 0.85
-    assert (first['argmin'][ok0] == r0['argmin'][ok0]).all() and (first['status'][ok0] == r0['status'][ok0]).all()
-    sol = ok0 & (r0['status'] == 0)
-    assert sol.sum() > 60
-    assert rel_err(first['x'][sol], r0['x'][sol]).max() <= tol
-    assert rel_err(first['u'][sol], r0['u'][sol]).max() <= max(tol, 1e-12)
-    assert rel_err(first['cost'][sol], r0['cost'][sol]).max() <= tol
-    edge = np.zeros(B, bool)
-    for r in passes:
-        edge |= ambiguous_mask(r, P, eps, eps, eps, O.breakpoint_distance(x0, r['U'], kp, P), ties=False)
-    ref = passes[-1]
-    tie = ~edge
-    assert tie.mean() > 0.8
-    assert (got['status'][tie] == ref['status'][tie]).all()
-    st = tie & (ref['status'] == 0)
-    assert rel_err(got['cost'][st], ref['cost'][st]).max() <= max(10 * tol, 1e-7)
+    m0 = PC.check_case(case, first, oracle, first=True)
+    assert m0['solved'] > 60
+    PC.check_case(case, got, oracle)
     # quality: solves more scenarios than ramp-hold and costs less where both solve
     assert (first['status'] == 0).sum() >= (rh['status'] == 0).sum()
     both = (first['status'] == 0) & (rh['status'] == 0)
@@ -986,37 +803,22 @@ def test_tracking_speed_cap_matches_oracle(igt, dtype):
     still keeps v <= v_max (igt_device.h track_speed_cap; oracle np_oracle.track_speed_cap).  Scenarios that start near the
     speed limit (v0 = 3.6 .. 4.9 m/s) so that the top rows meet the cap: every candidate's controls and the solve agree with the
     oracle with the cap on and off, capped candidates stay inside the speed box, and the cap never makes an answer worse."""
-    B = 128
-    npdt = np.float64 if dtype == 'f64' else np.float32
-    b = _batch(B, npdt)
-    rng = np.random.default_rng(77)
-    x0 = np.array(b['x0'], dtype=npdt)
-    x0[:, 5] = rng.uniform(3.6, 4.9, B).astype(npdt)
-    u_prev = np.array(b['u_prev'], dtype=npdt)
-    u_prev[:, 0] = rng.uniform(-0.2, 1.2, B).astype(npdt)
     f = lambda a: np.asarray(a, dtype=np.float64)
-    args = (x0, u_prev, b['kparams'], b['flags'], b['obs_xy'])
     res = {}
     for vcap in (1.0, 0.0):
-        with igt.BatchSolver(dtype=dtype, cand_mode='track', track_vcap=vcap) as s:
-            P = oracle_params(s)
+        case = PC.speed_cap_case(dtype, vcap)
+        x0, u_prev, P, eps = case['args']['x0'], case['args']['u_prev'], case['P'], case['eps']
+        with PC.open_solver(igt, case) as s:
             assert s.params.track_vcap == vcap
-            s.set_cinf(*_cinf())
-            all_ = s.rollout_all(*[a[:32] for a in args])
-            got = s.solve(*args)
-        ref = O.solve_batch_refined(f(x0), f(u_prev), f(b['kparams']), b['flags'], f(b['obs_xy']), *_cinf(), P, cand='track',
-                                    track=dict(vcap=vcap))[0]
-        kp = f(b['kparams'])[:, None, :]
-        bp = O.breakpoint_distance(O.apply_flags(f(x0), b['flags'])[:, None, :], ref['U'], kp, P)
-        clear = bp[:32] > (1e-9 if dtype == 'f64' else 2e-5)
-        tolU, tolx = (1e-12, 1e-9) if dtype == 'f64' else (2e-5, 1e-4)
-        assert rel_err(all_['U'][clear], ref['U'][:32][clear]).max() <= tolU
-        eps = 1e-9 if dtype == 'f64' else 2e-5
-        ok = ~ambiguous_mask(ref, P, eps, eps, eps, bp)
-        assert ok.mean() > 0.6, ok.mean()
-        assert (got['argmin'][ok] == ref['argmin'][ok]).all() and (got['status'][ok] == ref['status'][ok]).all()
-        sol = ok & (ref['status'] == 0)
-        assert sol.sum() > 30 and rel_err(got['x'][sol], ref['x'][sol]).max() <= tolx
+            pos, _ = PC.solve_args(case, 32)
+            all_ = s.rollout_all(*pos)
+            got = PC.device_solve(s, case)
+        oracle = PC.oracle_passes(case)
+        ref = oracle[0][0]
+        clear = O.breakpoint_distance(oracle[1][:32], ref['U'][:32], oracle[2][:32], P) > eps
+        assert rel_err(all_['U'][clear], ref['U'][:32][clear]).max() <= (1e-12 if dtype == 'f64' else 2e-5)
+        m = PC.check_case(case, got, oracle)
+        assert m['solved'] > 30
         res[vcap] = (got, ref)
     got1, ref1 = res[1.0]
     got0, ref0 = res[0.0]
@@ -1040,24 +842,18 @@ def test_tracking_envelope_scale_matches_oracle(igt, env):
     """igt_params.track_env: 0 switches the acceleration envelope off (constant targets), any other scale moves the
     line E_k = env dt^2 (N - k - 1/2) / (2 w_u); every candidate's controls and the solve agree with the oracle run at
     the same scale, and the scale changes the answer.  A negative scale is refused."""
-    B = 96
-    b = _batch(B, np.float64)
-    f = lambda k: np.asarray(b[k], dtype=np.float64)
-    args = (b['x0'], b['u_prev'], b['kparams'], b['flags'], b['obs_xy'])
-    with igt.BatchSolver(dtype='f64', cand_mode='track', track_env=env) as s:
-        P = oracle_params(s)
-        s.set_cinf(*_cinf())
-        all_ = s.rollout_all(*[a[:32] for a in args])
-        got = s.solve(*args)
-    with igt.BatchSolver(dtype='f64', cand_mode='track') as s1:
-        s1.set_cinf(*_cinf())
-        dflt = s1.solve(*args)
-    ref = O.solve_batch_refined(f('x0'), f('u_prev'), f('kparams'), b['flags'], f('obs_xy'), *_cinf(), P, cand='track',
-                                track=dict(env=env))[0]
-    kp = f('kparams')[:, None, :]
-    x0 = O.apply_flags(f('x0'), b['flags'])[:, None, :]
-    bp = O.breakpoint_distance(x0, ref['U'], kp, P)
-    clear = bp[:32] > 1e-9
+    case = PC.envelope_case(env)
+    P = case['P']
+    f = lambda k: np.asarray(case['args'][k], dtype=np.float64)
+    with PC.open_solver(igt, case) as s:
+        pos, _ = PC.solve_args(case, 32)
+        all_ = s.rollout_all(*pos)
+        got = PC.device_solve(s, case)
+    with PC.open_solver(igt, dict(case, limits={}, P=PC.host_params(), tk=PC.host_track())) as s1:
+        dflt = PC.device_solve(s1, case)
+    oracle = PC.oracle_passes(case)
+    ref = oracle[0][0]
+    clear = O.breakpoint_distance(oracle[1][:32], ref['U'][:32], oracle[2][:32], P) > 1e-9
     assert rel_err(all_['U'][clear], ref['U'][:32][clear]).max() <= 1e-12
     slope = O.track_env_slope(P, env)
     E = slope * (P.N - np.arange(P.N) - 0.5)
@@ -1065,11 +861,8 @@ def test_tracking_envelope_scale_matches_oracle(igt, env):
     a_before = np.concatenate([np.broadcast_to(f('u_prev')[:, None, 0, None], a.shape[:2] + (1,)), a[..., :-1]], axis=-1)
     # above the line a candidate can only be on its way down at the jerk limit
     assert (a <= np.maximum(E, a_before - P.dt * P.jerk) + 1e-12).all()
-    ok = ~ambiguous_mask(ref, P, 1e-9, 1e-9, 1e-9, bp)
-    assert ok.mean() > 0.7
-    assert (got['argmin'][ok] == ref['argmin'][ok]).all() and (got['status'][ok] == ref['status'][ok]).all()
-    sol = ok & (ref['status'] == 0)
-    assert sol.sum() > 30 and rel_err(got['x'][sol], ref['x'][sol]).max() <= 1e-9
+    m = PC.check_case(case, got, oracle)
+    assert m['solved'] > 30
     both = (got['status'] == 0) & (dflt['status'] == 0)
     assert np.abs(got['cost'][both] - dflt['cost'][both]).max() > 1e-3
     with pytest.raises(Exception):
