@@ -667,6 +667,105 @@ int cost_gradient_impl(igt_handle* h, int32_t B, const double* x0, const double*
     return IGT_OK;
 }
 
+// what the two value-network gradient entries refuse before they look at their buffers
+int check_value_handle(const igt_handle* h, const char* what) {
+    if (!h) return fail(IGT_E_INVALID, "null handle");
+    if (h->p.cost_mode != IGT_COST_VALUE_NET)
+        return fail(IGT_E_INVALID, std::string(what) + " needs a handle created with IGT_COST_VALUE_NET");
+    return IGT_OK;
+}
+
+int terminal_value_impl(igt_handle* h, int32_t n, const double* sv, const double* tv_sv, const double* enc, double* V_out,
+                        double* dV_out, int mem, void* stream) {
+    if (int rc = check_value_handle(h, "igt_terminal_value_f64")) return rc;
+    if (n < 0) return fail(IGT_E_INVALID, "n < 0");
+    if (mem != IGT_MEM_DEVICE && mem != IGT_MEM_HOST) return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
+    if (n == 0) return IGT_OK;
+    if (!V_out) return fail(IGT_E_INVALID, "null output buffer (V_out)");
+    if (!sv || !tv_sv || !enc) return fail(IGT_E_INVALID, "null buffer");
+    if (!h->net_set) return fail(IGT_E_STATE, "value net not set (igt_set_value_net)");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const size_t n2 = (size_t)n * 2;
+    const double *ds = sv, *dt = tv_sv, *de = enc;
+    double *dV = V_out, *dG = dV_out;
+    if (mem == IGT_MEM_HOST) {
+        double *a, *b, *c;
+        const auto carve = [&](Arena& ar) {
+            a = ar.take<double>(n2); b = ar.take<double>(n2); c = ar.take<double>(n2);
+            dV = ar.take<double>((size_t)n); dG = dV_out ? ar.take<double>(n2) : nullptr;
+        };
+        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
+        Arena ar{(char*)h->d_stage, 0};
+        carve(ar);
+        HIPCHK(hipMemcpyAsync(a, sv, n2 * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b, tv_sv, n2 * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(c, enc, n2 * 8, hipMemcpyHostToDevice, st));
+        ds = a; dt = b; de = c;
+    }
+    HIPCHK(igt::launch_terminal_value(h->net_d, h->n_cu, n, ds, dt, de, dV, dG, st));
+    if (mem == IGT_MEM_HOST) {
+        HIPCHK(hipMemcpyAsync(V_out, dV, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        if (dV_out) HIPCHK(hipMemcpyAsync(dV_out, dG, n2 * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return IGT_OK;
+}
+
+// Three launches: the forward sweep leaves (s_N, v_N) in the workspace, the network answers V_out and its
+// partials there, and the sweep kernel runs again with that terminal seed.  The scratch is VnScratch (igt_launch.h), carved
+// from the handle's workspace like a solve's: it grows on first use and cannot grow under stream capture.
+int cost_gradient_vn_impl(igt_handle* h, int32_t B, const double* x0, const double* kparams, const uint32_t* flags,
+                          const double* tv_sv, const double* enc, const double* U, double* cost_out, double* grad_out, int mem,
+                          void* stream) {
+    if (int rc = check_value_handle(h, "igt_cost_gradient_vn_f64")) return rc;
+    if (B < 0) return fail(IGT_E_INVALID, "B < 0");
+    if (mem != IGT_MEM_DEVICE && mem != IGT_MEM_HOST) return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
+    if (B == 0) return IGT_OK;
+    if (!cost_out || !grad_out) return fail(IGT_E_INVALID, "null output buffer (cost_out, grad_out)");
+    if (!x0 || !kparams || !flags || !U) return fail(IGT_E_INVALID, "null buffer");
+    if (!tv_sv || !enc) return fail(IGT_E_INVALID, "tv_sv / enc required for the value-net cost");
+    if (!h->net_set) return fail(IGT_E_STATE, "value net not set (igt_set_value_net)");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const size_t n_x = (size_t)B * 7, n_k = (size_t)B * 3, n_2 = (size_t)B * 2, n_u = (size_t)B * 2 * h->p.N;
+    const double *dx = x0, *dk = kparams, *du = U, *dt = tv_sv, *de = enc;
+    double *dc = cost_out, *dg = grad_out;
+    if (mem == IGT_MEM_HOST) {
+        double *a, *b, *c, *d, *e;
+        const auto carve = [&](Arena& ar) {
+            a = ar.take<double>(n_x); b = ar.take<double>(n_k); c = ar.take<double>(n_u);
+            d = ar.take<double>(n_2); e = ar.take<double>(n_2);
+            dc = ar.take<double>((size_t)B); dg = ar.take<double>(n_u);
+        };
+        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
+        Arena ar{(char*)h->d_stage, 0};
+        carve(ar);
+        HIPCHK(hipMemcpyAsync(a, x0, n_x * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b, kparams, n_k * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(c, U, n_u * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d, tv_sv, n_2 * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(e, enc, n_2 * 8, hipMemcpyHostToDevice, st));
+        dx = a; dk = b; du = c; dt = d; de = e;
+    }
+    double* vn = nullptr;
+    const auto carve = [&](Arena& wa) { vn = wa.take<double>(igt::VnScratch::doubles(B)); };
+    if (int rc = ensure_work(h, arena_bytes(carve), st)) return rc;
+    Arena wa{(char*)h->d_work, 0};
+    carve(wa);
+    const igt::VnScratch S(vn, B);
+    // the flags only act on psi_0, which neither the stage terms nor the network's features read
+    HIPCHK(igt::launch_cost_gradient_vn(h->kp, B, true, dx, dk, du, dc, dg, vn, st));
+    HIPCHK(igt::launch_terminal_value(h->net_d, h->n_cu, B, S.sv(), dt, de, S.V(), S.dV(), st));
+    HIPCHK(igt::launch_cost_gradient_vn(h->kp, B, false, dx, dk, du, dc, dg, vn, st));
+    if (mem == IGT_MEM_HOST) {
+        HIPCHK(hipMemcpyAsync(cost_out, dc, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(grad_out, dg, n_u * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return IGT_OK;
+}
+
 template <typename T>
 int forecast_impl(igt_handle* h, int32_t B, const T* ego_xyh, const T* opp, const T* opp_a, const int32_t* opp_route,
                   const T* plan_x, const T* plan_u, const int32_t* has_plan, T* obs_xy, T* tv_sv, int mem, void* stream) {
@@ -1283,6 +1382,17 @@ int igt_set_polish_gradient(igt_handle* h, int mode) {
 int igt_cost_gradient_f64(igt_handle* h, int32_t B, const double* x0, const double* kparams, const uint32_t* flags,
                           const double* U, double* cost_out, double* grad_out, int mem, void* stream) {
     return cost_gradient_impl(h, B, x0, kparams, flags, U, cost_out, grad_out, mem, stream);
+}
+
+int igt_terminal_value_f64(igt_handle* h, int32_t n, const double* sv, const double* tv_sv, const double* enc, double* V_out,
+                           double* dV_out, int mem, void* stream) {
+    return terminal_value_impl(h, n, sv, tv_sv, enc, V_out, dV_out, mem, stream);
+}
+
+int igt_cost_gradient_vn_f64(igt_handle* h, int32_t B, const double* x0, const double* kparams, const uint32_t* flags,
+                             const double* tv_sv, const double* enc, const double* U, double* cost_out, double* grad_out,
+                             int mem, void* stream) {
+    return cost_gradient_vn_impl(h, B, x0, kparams, flags, tv_sv, enc, U, cost_out, grad_out, mem, stream);
 }
 
 int igt_set_profiling(igt_handle* h, int enable) {

@@ -760,12 +760,35 @@ hipError_t prepare_value_kernels(int n_hidden_mats) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&value_mfma_f64_kernel<2>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FRAGD_LDS * sizeof(double)));
     if (e != hipSuccess) return e;
+    const void* tv[] = {reinterpret_cast<const void*>(&terminal_value_f64_kernel<1, false>),
+                        reinterpret_cast<const void*>(&terminal_value_f64_kernel<1, true>),
+                        reinterpret_cast<const void*>(&terminal_value_f64_kernel<2, false>),
+                        reinterpret_cast<const void*>(&terminal_value_f64_kernel<2, true>)};
+    for (const void* f : tv) {
+        e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FRAGD_LDS * sizeof(double)));
+        if (e != hipSuccess) return e;
+    }
     const size_t lds_f = (size_t)frag_floats(n_hidden_mats) * sizeof(float);
     if (n_hidden_mats > 1)
         return hipFuncSetAttribute(reinterpret_cast<const void*>(&value_mfma_kernel<2>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&value_mfma_kernel<1>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
+}
+
+// igt_terminal_value_f64: one wave per 16 states, 4 waves per workgroup, at most one workgroup per CU (each stages the
+// fragment block into its LDS), grid-stride over the groups
+hipError_t launch_terminal_value(const DevNet<double>& net, int n_cu, int n, const double* sv, const double* tv_sv,
+                                 const double* enc, double* V_out, double* dV_out, hipStream_t st) {
+    const int groups = (n + 15) / 16;
+    const dim3 grid(groups < n_cu ? groups : n_cu), block(256);
+    const size_t lds = (size_t)FRAGD_LDS * sizeof(double);
+#define IGT_LAUNCH_TV(NM_, GRAD_) \
+    hipLaunchKernelGGL((terminal_value_f64_kernel<NM_, GRAD_>), grid, block, lds, st, net, n, sv, tv_sv, enc, V_out, dV_out)
+    if (net.n_hidden_mats > 1) { if (dV_out) IGT_LAUNCH_TV(2, true); else IGT_LAUNCH_TV(2, false); }
+    else { if (dV_out) IGT_LAUNCH_TV(1, true); else IGT_LAUNCH_TV(1, false); }
+#undef IGT_LAUNCH_TV
+    return hipGetLastError();
 }
 
 template <typename T>

@@ -6,7 +6,8 @@
 //   emit_gather_f64_kernel   small batches: the winner's trajectory copied out of the unit that rolled it
 //   rollout_all_f64_kernel   debug / parity: every candidate's trajectory, cost and verdict bits
 //   polish_f64_kernel     projected-gradient steps on the winner (forward-difference or adjoint gradient)
-//   cost_gradient_f64_kernel   dJ/du of the progress cost for one control sequence per scenario (igt_adjoint64.h)
+//   cost_gradient_f64_kernel   dJ/du of the progress cost for one control sequence per scenario (igt_adjoint64.h); templated on the
+//                         terminal term: the two sweeps of igt_cost_gradient_vn_f64 around the value network are instantiations
 //   search_kernel / emit_kernel / rollout_all_kernel<ExactStepper<double>>   the oracle's operation order (IGT_DEV_FLAGS=1024)
 //   search_literal_f64_kernel   the literal north_star mapping, a measurement variant (IGT_DEV_FLAGS=2048)
 // Compiled on its own so that the two heavy translation units build in parallel.
@@ -880,11 +881,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 // way), the write-out reads one lane's slots (stride 3 x 65 words: spread over the banks; 3 x 64 would put them all on one).
 // x, y, psi feed nothing back and are not rolled, so IGT_FLAG_ABS_HEADING (|psi_0|) changes nothing here.  A non-finite cost
 // gives a NaN row.  No workspace, no wave votes: lanes past B idle.
+// TERM: the terminal term of the cost.  TERM_PROGRESS: -(s_N - s_0) (mpc.py:372), seed (-1, 2 ey_N, 2 epsi_N, 0); vn is not read.
+// The value-network cost (igt_cost_gradient_vn_f64, mpc.py:369) runs the kernel twice around terminal_value_f64_kernel, on the
+// scratch vn (igt_launch.h VnScratch): TERM_LEAVE is the forward sweep alone and leaves (s_N, v_N); TERM_VALUE reads the network's
+// answer for them, J = stage terms - V_out, seed (-dV_out/ds_N, 2 ey_N, 2 epsi_N, -dV_out/dv_N) -- v_N = v_0 + dt sum a_k, so the
+// last entry reaches every a_k through costate_step's dt lam[3].
 constexpr int GRAD_STRIDE = 65;
+enum { TERM_PROGRESS = 0, TERM_LEAVE = 1, TERM_VALUE = 2 };
 __host__ __device__ inline size_t grad_lds_doubles(int N) { return (size_t)3 * (N + 1) * GRAD_STRIDE; }
+template <int TERM>
 __global__ __launch_bounds__(64) void cost_gradient_f64_kernel(KP P, int B, const double* __restrict__ x0,
                                                                const double* __restrict__ kparams, const double* __restrict__ U,
-                                                               double* __restrict__ cost_out, double* __restrict__ grad_out) {
+                                                               double* __restrict__ cost_out, double* __restrict__ grad_out,
+                                                               double* __restrict__ vn) {
     extern __shared__ double grad_lds[];
     const int lane = threadIdx.x, N = P.N, n2 = 2 * N;
     const int b0 = blockIdx.x * 64, b = b0 + lane;
@@ -910,9 +919,21 @@ __global__ __launch_bounds__(64) void cost_gradient_f64_kernel(KP P, int B, cons
         }
         J = J + ep * ep;
         J = J + ey * ey;
-        J = J - (s - s0);                                                            // mpc.py:372
+        if constexpr (TERM == TERM_LEAVE) {
+            double* sv = VnScratch(vn, B).sv();
+            sv[(size_t)b * 2 + 0] = s; sv[(size_t)b * 2 + 1] = v;
+            return;
+        }
+        double seed_s = -1.0, seed_v = 0.0;                                          // d (terminal term) / d (s_N, v_N)
+        if constexpr (TERM == TERM_VALUE) {
+            const VnScratch S(vn, B);
+            J = J - S.V()[b];                                                        // mpc.py:369
+            seed_s = -S.dV()[(size_t)b * 2 + 0]; seed_v = -S.dV()[(size_t)b * 2 + 1];
+        } else {
+            J = J - (s - s0);                                                        // mpc.py:372
+        }
         cost_out[b] = J;
-        double lam[4] = {-1.0, 2.0 * ey, 2.0 * ep, 0.0};
+        double lam[4] = {seed_s, 2.0 * ey, 2.0 * ep, seed_v};
         for (int k = N - 1; k >= 0; --k) {
             const double a = ua[k], df = ua[N + k];
             v = fma(-M.dt, a, v);
@@ -926,6 +947,7 @@ __global__ __launch_bounds__(64) void cost_gradient_f64_kernel(KP P, int B, cons
         }
         node[0] = finite_d(J) ? 1.0 : 0.0;                                           // node 0's s slot: the row's verdict
     }
+    if constexpr (TERM == TERM_LEAVE) return;
     __syncthreads();
     const int nS = B - b0 < 64 ? B - b0 : 64;
     double* go = grad_out + (size_t)b0 * n2;
@@ -1311,7 +1333,9 @@ hipError_t prepare_emit_kernels() {
     if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<false, 4, true>);
     if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<false, 0, true>);
     if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<true, 0, true>);
-    if (e == hipSuccess) e = seg_lds_opt_in(cost_gradient_f64_kernel);
+    if (e == hipSuccess) e = seg_lds_opt_in(cost_gradient_f64_kernel<TERM_PROGRESS>);
+    if (e == hipSuccess) e = seg_lds_opt_in(cost_gradient_f64_kernel<TERM_LEAVE>);
+    if (e == hipSuccess) e = seg_lds_opt_in(cost_gradient_f64_kernel<TERM_VALUE>);
     return e;
 }
 
@@ -1359,8 +1383,17 @@ hipError_t launch_polish(const KP& P, int B, int iters, bool adjoint, const Solv
 // igt_cost_gradient_f64: one wave per 64 scenarios; the LDS passes 64 KB from N = 41 on (asked for in prepare_emit_kernels)
 hipError_t launch_cost_gradient(const KP& P, int B, const double* x0, const double* kparams, const double* U, double* cost_out,
                                 double* grad_out, hipStream_t st) {
-    hipLaunchKernelGGL(cost_gradient_f64_kernel, dim3((B + 63) / 64), dim3(64), grad_lds_doubles(P.N) * 8, st, P, B, x0, kparams, U,
-                       cost_out, grad_out);
+    hipLaunchKernelGGL(cost_gradient_f64_kernel<TERM_PROGRESS>, dim3((B + 63) / 64), dim3(64), grad_lds_doubles(P.N) * 8, st, P, B,
+                       x0, kparams, U, cost_out, grad_out, (double*)nullptr);
+    return hipGetLastError();
+}
+// igt_cost_gradient_vn_f64: the sweeps before (leave = true: (s_N, v_N) into vn) and behind launch_terminal_value
+hipError_t launch_cost_gradient_vn(const KP& P, int B, bool leave, const double* x0, const double* kparams, const double* U,
+                                   double* cost_out, double* grad_out, double* vn, hipStream_t st) {
+    const dim3 grid((B + 63) / 64), block(64);
+    const size_t lds = grad_lds_doubles(P.N) * 8;
+    if (leave) hipLaunchKernelGGL(cost_gradient_f64_kernel<TERM_LEAVE>, grid, block, lds, st, P, B, x0, kparams, U, cost_out, grad_out, vn);
+    else hipLaunchKernelGGL(cost_gradient_f64_kernel<TERM_VALUE>, grid, block, lds, st, P, B, x0, kparams, U, cost_out, grad_out, vn);
     return hipGetLastError();
 }
 

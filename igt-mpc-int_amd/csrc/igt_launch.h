@@ -84,6 +84,19 @@ struct PartJTail {
     __host__ __device__ double* ck_records() const { return part_J + B * W + 2 * B + B * G; }
 };
 
+// What igt_cost_gradient_vn_f64 keeps in the workspace between its three launches, per scenario: the terminal ego state the
+// forward sweep leaves, [B, 2] (s_N, v_N); the network's scaled value for it, [B]; its partials by (s_N, v_N), [B, 2].  The
+// host takes doubles(B) of the workspace, the sweep kernel finds the pieces from the base through the same declaration.
+struct VnScratch {
+    double* base;
+    size_t B;
+    __host__ __device__ VnScratch(double* base_, int B_) : base(base_), B((size_t)B_) {}
+    __host__ __device__ static size_t doubles(int B_) { return (size_t)5 * (size_t)B_; }
+    __host__ __device__ double* sv() const { return base; }
+    __host__ __device__ double* V() const { return base + 2 * B; }
+    __host__ __device__ double* dV() const { return base + 3 * B; }
+};
+
 // work_counter is followed by the developer unit trace (DEV_TRACE): u64[queue items][4]
 constexpr size_t WORK_COUNTER_WORDS = 1024;
 __host__ __device__ inline unsigned long long* unit_trace(unsigned* work_counter) {
@@ -107,6 +120,12 @@ hipError_t prepare_emit_kernels();                     // once per igt_create: t
 hipError_t launch_polish(const KP& P, int B, int iters, bool adjoint, const SolveArgs<double>& A, hipStream_t st);
 hipError_t launch_cost_gradient(const KP& P, int B, const double* x0, const double* kparams, const double* U, double* cost_out,
                                 double* grad_out, hipStream_t st);
+// igt_cost_gradient_vn_f64: the sweep before (leave: forward only, (s_N, v_N) into vn) and behind launch_terminal_value
+hipError_t launch_cost_gradient_vn(const KP& P, int B, bool leave, const double* x0, const double* kparams, const double* U,
+                                   double* cost_out, double* grad_out, double* vn, hipStream_t st);
+// igt_terminal_value_f64 (igt_value_net.h terminal_value_f64_kernel); dV_out null: the values alone
+hipError_t launch_terminal_value(const DevNet<double>& net, int n_cu, int n, const double* sv, const double* tv_sv,
+                                 const double* enc, double* V_out, double* dV_out, hipStream_t st);
 template <typename T> hipError_t launch_reduce(int B, int W, const SolveArgs<T>& A, hipStream_t st);
 // ramp-hold refinement: winner of the pass just finished -> centre/span of the next pass (cpar[B,4])
 template <typename T>

@@ -558,6 +558,141 @@ __global__ __launch_bounds__(512) void value_mfma_f64_kernel(DevNet<double> net,
 }
 
 // ---------------------------------------------------------------------------------------
+// The scaled terminal value and its partials by (s_N, v_N) for n terminal ego states of their own scenarios
+// (igt_terminal_value_f64; the seed of igt_cost_gradient_vn_f64's costate): no list, no atomics -- state i is column i.
+// The same Y = W X chain on the same fragd A fragments as value_mfma_f64_kernel, with two forward-mode tangents beside the
+// values.  Only features 3 and 4 depend on (s_N, v_N) (mpc.py:326-338), so a group of 16 states takes three output tiles at the
+// same column: values, d/ds_N, d/dv_N.  The tangent columns of layer 1 are the unit features e_3 / e_4 (bias feature 0)
+// through the layer-1 fragments; behind every hidden layer h = tanh(y), h' = (1 - h^2) y' -- lane (g, col) holds value and
+// tangents of the same (neuron, state), so the epilogue is lane-local -- and the output row contracts all three.  Every A
+// fragment is read once for the three chains, which also cover the dependent-MFMA latency.
+//   wave = 16 states; 4 waves per workgroup (one per SIMD: value and tangent tiles of two layers are 384 registers)
+//   GRAD = false (dV_out == NULL): the value chain alone, the same operations in the same order -> the same V bits
+// Columns past n carry zero features (finite everywhere) and store nothing.  A non-finite (s_N, v_N, tv_sv, enc) gives NaN
+// outputs (tanh_d clamps its argument: it would hide a NaN).
+// ---------------------------------------------------------------------------------------
+template <int NM, bool GRAD>
+__global__ __launch_bounds__(256) void terminal_value_f64_kernel(DevNet<double> net, int n, const double* __restrict__ sv,
+                                                                 const double* __restrict__ tv_sv, const double* __restrict__ enc,
+                                                                 double* __restrict__ V_out, double* __restrict__ dV_out) {
+    extern __shared__ double ldsd[];
+    constexpr int NC = GRAD ? 3 : 1;                          // chains: value, d/ds_N, d/dv_N
+    const double* __restrict__ WFg = net.fragd + FRAGD_A1;
+    double* const A1F = ldsd + FRAGD_W;
+    double* const BF = A1F + FRAGD_A1;
+    double* const WOF = BF + 2 * FRAGD_B;
+    for (int i = threadIdx.x; i < FRAGD_W; i += 256) ldsd[i] = WFg[i];
+    for (int i = threadIdx.x; i < FRAGD_A1; i += 256) A1F[i] = net.fragd[i];
+    for (int i = threadIdx.x; i < NM * FRAGD_B; i += 256) BF[i] = WFg[NM * FRAGD_W + i];
+    for (int i = threadIdx.x; i < FRAGD_B; i += 256) WOF[i] = WFg[NM * FRAGD_W + NM * FRAGD_B + i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, g = lane >> 4, col = lane & 15;
+    const int groups = (n + 15) / 16;
+    // consecutive groups go to different workgroups: a small n spreads over the compute units
+    const int wave = (int)(threadIdx.x >> 6) * (int)gridDim.x + (int)blockIdx.x, nwaves = (int)gridDim.x * 4;
+    for (int grp = wave; grp < groups; grp += nwaves) {
+        const int i = grp * 16 + col;
+        const bool live = i < n;
+        const size_t i2 = live ? (size_t)i * 2 : 0;
+        const double sN = live ? sv[i2] : 0.0, vN = live ? sv[i2 + 1] : 0.0;
+        const double s_tv = live ? tv_sv[i2] : 0.0, v_tv = live ? tv_sv[i2 + 1] : 0.0;
+        const double e_ego = live ? enc[i2] : 0.0, e_tv = live ? enc[i2 + 1] : 0.0;
+        // B operands of layer 1, feature 4 s + g: the state's x_N (value_mfma_f64_kernel), and e_3 / e_4 for the tangents
+        const double x0 = g == 0 ? s_tv : g == 1 ? v_tv : g == 2 ? e_tv : sN - s_tv;
+        const double x1 = g == 0 ? vN - v_tv : g == 1 ? e_ego - e_tv : g == 2 ? 1.0 : 0.0;
+        const double e3 = g == 3 ? 1.0 : 0.0, e4 = g == 0 ? 1.0 : 0.0;
+        const double* wg = WFg + lane;                       // the second matrix through L2 (value_mfma_f64_kernel)
+        asm volatile("" : "+v"(wg));
+        f64x4 Ha[NC][8], Hb[NC][8];
+        double out[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) out[c] = 0.0;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            f64x4 acc[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) acc[c] = f64x4{0.0, 0.0, 0.0, 0.0};
+            acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(A1F[(t * 2 + 0) * 64 + lane], x0, acc[0], 0, 0, 0);
+            if (GRAD) {
+                acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(A1F[(t * 2 + 0) * 64 + lane], e3, acc[1], 0, 0, 0);
+                acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(A1F[(t * 2 + 1) * 64 + lane], e4, acc[2], 0, 0, 0);
+            }
+            acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(A1F[(t * 2 + 1) * 64 + lane], x1, acc[0], 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double hv = tanh_d(acc[0][r]);
+                Ha[0][t][r] = hv;
+                if (GRAD) {
+                    const double d = fma(-hv, hv, 1.0);
+                    Ha[1][t][r] = d * acc[1][r];
+                    Ha[NC - 1][t][r] = d * acc[NC - 1][r];
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int m = 0; m < NM; ++m) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                f64x4 acc[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) acc[c] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[0][r] = BF[m * FRAGD_B + (t * 4 + r) * 4 + g];
+#pragma unroll
+                for (int ti = 0; ti < 8; ++ti) {
+                    double af[4];                            // fenced as in value_mfma_f64_kernel
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int i0 = ((t * 8 + ti) * 4 + r) * 64;
+                        af[r] = (m == 0) ? ldsd[i0 + lane] : wg[(size_t)m * FRAGD_W + i0];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) {
+                            const double bop = (m == 0) ? Ha[c][ti][r] : Hb[c][ti][r];
+                            acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[r], bop, acc[c], 0, 0, 0);
+                        }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    double hc[NC];
+                    hc[0] = tanh_d(acc[0][r]);
+                    if (GRAD) {
+                        const double d = fma(-hc[0], hc[0], 1.0);
+                        hc[1] = d * acc[1][r];
+                        hc[NC - 1] = d * acc[NC - 1][r];
+                    }
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        if (m == NM - 1) out[c] = fma(WOF[(t * 4 + r) * 4 + g], hc[c], out[c]);      // the output row, as it comes
+                        else Hb[c][t][r] = hc[c];
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            out[c] += __shfl_xor(out[c], 16, 64);
+            out[c] += __shfl_xor(out[c], 32, 64);
+        }
+        if (live && g == 0) {
+            const double chk = ((sN + vN) + (s_tv + v_tv)) + (e_ego + e_tv);
+            const bool fin = fabs(chk) < 1.79e308;
+            V_out[i] = fin ? (out[0] + net.bout) * net.sigma_t + net.mu_t : (double)NAN;      // mpc.py:369
+            if (GRAD) {
+                dV_out[i2] = fin ? out[1] * net.sigma_t : (double)NAN;
+                dV_out[i2 + 1] = fin ? out[NC - 1] * net.sigma_t : (double)NAN;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // Pruning the compact list before the network runs (double path).  The cost of an entry is J_e - V(x_e) (mpc.py:369) and
 // the hidden layers are tanh, so V is bounded on any box of features.  Per scenario -- only s_N and v_N differ between its
 // entries -- one wave

@@ -242,13 +242,53 @@ class BatchSolver:
         self._check(self._rollout(self._h, B, *ptrs, mode, self._stream_ptr(stream, False)))
         return dict(X=X, U=U, cost=cost, viol=viol)
 
-    def cost_gradient(self, x0, kparams, flags, U, out=None, stream=None):
+    def _entry(self, name):
+        """An entry added without a change of IGT_VERSION: a library from before it (IGT_LIB_PATH) does not export it."""
+        fn = getattr(self.lib, name, None)
+        if fn is None:
+            raise L.IgtError(f'this libigtmpc.so does not export {name}: it was built before the entry was added; rebuild it '
+                             f'(`make -C igt-mpc-int_amd/csrc`)')
+        return fn
+
+    def terminal_value(self, sv, tv_sv, enc, want_grad=True, out=None, stream=None):
+        """The terminal term of the gt_mpc cost, V(Wn (x_N - mu_f)) sigma_t + mu_t (mpc.py:326-338, 369), for n terminal ego states
+        of their own scenarios and -- want_grad -- its partials by (s_N, v_N) (igtmpc.h igt_terminal_value_f64):
+        sv[n,2] = (s_N, v_N), tv_sv[n,2], enc[n,2] -> dict(V[n], dV[n,2] | None).  float64 solvers with cost_mode='value_net' and a
+        network set; numpy arrays or tensors on the solver's GPU, as solve."""
+        if self.dtype != 'f64':
+            raise ValueError("terminal_value needs dtype='f64'")
+        fn = self._entry('igt_terminal_value_f64')
+        n = int(sv.shape[0])
+        if out is None:
+            if _is_torch(sv):
+                import torch
+                out = dict(V=torch.empty((n,), dtype=torch.float64, device=sv.device),
+                           dV=torch.empty((n, 2), dtype=torch.float64, device=sv.device) if want_grad else None)
+            else:
+                out = dict(V=np.empty((n,), np.float64), dV=np.empty((n, 2), np.float64) if want_grad else None)
+        f8 = np.float64
+        dV = out.get('dV') if want_grad else None
+        if want_grad and dV is None:
+            raise ValueError("want_grad=True needs out['dV']")
+        mode, ptrs, keep = self._prep([sv, tv_sv, enc, out['V'], dV], [(n, 2), (n, 2), (n, 2), (n,), (n, 2)], [f8] * 5)
+        if mode == L.IGT_MEM_HOST:
+            for k, i in (('V', 3), ('dV', 4)):
+                if ptrs[i] is not None and keep_is_copy(out[k], ptrs[i]):
+                    raise ValueError(f'out[{k!r}] must be a contiguous float64 array')
+        self._check(fn(self._h, n, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        return out
+
+    def cost_gradient(self, x0, kparams, flags, U, out=None, stream=None, tv_sv=None, enc=None):
         """dJ/du of the progress cost (mpc.py:356-373) for one control sequence per scenario, no projection and no verdicts
         (igtmpc.h igt_cost_gradient_f64): x0[B,7] kparams[B,3] flags[B] U[B,2,N] -> dict(cost[B], grad[B,2,N]); a non-finite
-        cost gives a NaN row.  float64 solvers with the progress cost; numpy arrays or tensors on the solver's GPU, as solve."""
+        cost gives a NaN row.  float64 solvers with the progress cost; numpy arrays or tensors on the solver's GPU, as solve.
+        With tv_sv[B,2] and enc[B,2] on a cost_mode='value_net' solver: the same for the value-network cost, whose terminal term
+        is -terminal_value(s_N, v_N) (igtmpc.h igt_cost_gradient_vn_f64)."""
         if self.dtype != 'f64':
             raise ValueError("cost_gradient needs dtype='f64'")
         B, N = int(x0.shape[0]), self.N
+        if tv_sv is not None and enc is not None and self.params.cost_mode == L.IGT_COST_VALUE_NET:
+            return self._cost_gradient_vn(B, x0, kparams, flags, tv_sv, enc, U, out, stream)
         torch_mode = _is_torch(x0)
         if out is None:
             if torch_mode:
@@ -265,6 +305,27 @@ class BatchSolver:
                 if keep_is_copy(out[k], ptrs[i]):
                     raise ValueError(f'out[{k!r}] must be a contiguous float64 array')
         self._check(self.lib.igt_cost_gradient_f64(self._h, B, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        return out
+
+    def _cost_gradient_vn(self, B, x0, kparams, flags, tv_sv, enc, U, out, stream):
+        fn = self._entry('igt_cost_gradient_vn_f64')
+        N = self.N
+        if out is None:
+            if _is_torch(x0):
+                import torch
+                out = dict(cost=torch.empty((B,), dtype=torch.float64, device=x0.device),
+                           grad=torch.empty((B, 2, N), dtype=torch.float64, device=x0.device))
+            else:
+                out = dict(cost=np.empty((B,), np.float64), grad=np.empty((B, 2, N), np.float64))
+        f8 = np.float64
+        mode, ptrs, keep = self._prep([x0, kparams, flags, tv_sv, enc, U, out['cost'], out['grad']],
+                                      [(B, 7), (B, 3), (B,), (B, 2), (B, 2), (B, 2, N), (B,), (B, 2, N)],
+                                      [f8, f8, np.uint32, f8, f8, f8, f8, f8])
+        if mode == L.IGT_MEM_HOST:
+            for k, i in (('cost', 6), ('grad', 7)):
+                if keep_is_copy(out[k], ptrs[i]):
+                    raise ValueError(f'out[{k!r}] must be a contiguous float64 array')
+        self._check(fn(self._h, B, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
         return out
 
     def set_routes(self, table=None):

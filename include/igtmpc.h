@@ -369,6 +369,38 @@ int igt_set_polish_gradient(igt_handle* h, int mode);
 int igt_cost_gradient_f64(igt_handle* h, int32_t B, const double* x0, const double* kparams, const uint32_t* flags,
                           const double* U, double* cost_out, double* grad_out, int mem, void* stream);
 
+/* The terminal term of the gt_mpc cost and its partials, for n terminal ego states of their own scenarios:
+ *   V_out[i] = V(Wn (x_N - mu_f)) * sigma_t + mu_t,   x_N = [s_tv, v_tv, e_tv, s_N - s_tv, v_N - v_tv, e_ego - e_tv]
+ * -- the amount mpc.py:369 subtracts from the cost -- with the network, whitening and scaling of igt_set_value_net, and
+ *   dV_out[i] = (dV_out/ds_N, dV_out/dv_N)
+ * by two forward-mode tangents through the same layers (only features 3 and 4 depend on the plan, mpc.py:326-338).
+ *   sv [n,2] = (s_N, v_N)  tv_sv [n,2]  enc [n,2] = (e_ego, e_tv)  ->  V_out [n]  dV_out [n,2] (may be NULL: values alone, same bits)
+ * float64 matrix cores on the weight fragments the solve uses; agrees with the value inside igt_rollout_batch_f64's cost to
+ * rounding (~1e-13), not bit for bit.  A non-finite input gives that state NaN outputs.  IGT_MEM_DEVICE: one kernel enqueued on
+ * `stream`, no workspace, no allocation, no host synchronisation (capturable).  IGT_E_INVALID on a handle that is not
+ * IGT_COST_VALUE_NET, for n < 0, for null buffers (dV_out excepted) and for a bad mem; IGT_E_STATE when no network is loaded;
+ * n = 0 is a no-op.  There is no _f32 entry.  (Added without a change of IGT_VERSION; callers probe the symbol.) */
+int igt_terminal_value_f64(igt_handle* h, int32_t n, const double* sv, const double* tv_sv, const double* enc,
+                           double* V_out, double* dV_out, int mem, void* stream);
+
+/* dJ/du of the value-network cost (gt_mpc) for one control sequence per scenario:
+ *   J(u) = sum_{k<=N} (epsi_k^2 + ey_k^2) + w_u sum_{k<N} (a_k^2 + df_k^2) - V_out(s_N, v_N)         (mpc.py:356-369)
+ * with V_out as igt_terminal_value_f64 defines it.  Shapes and conventions are igt_cost_gradient_f64's -- no projection, no
+ * verdicts, K(s) locally constant, a non-finite cost gives a NaN row, IGT_FLAG_ABS_HEADING accepted and inert -- plus the
+ * scenario's tv_sv [B,2] and enc [B,2] as a solve takes them:
+ *   x0 [B,7]  kparams [B,3]  flags [B]  tv_sv [B,2]  enc [B,2]  U [B,2,N]  ->  cost_out [B]  grad_out [B,2,N]
+ * The costate starts at (-dV_out/ds_N, 2 ey_N, 2 epsi_N, -dV_out/dv_N); v_N = v_0 + dt sum a_k carries the last entry to
+ * every a_k.  cost_out agrees with igt_rollout_batch_f64's cost of the same controls on a value-network handle to rounding.
+ * Three kernels (forward sweep, network, forward and backward sweep) and 40 B of workspace per scenario, which grows as a
+ * solve's does (below).  IGT_MEM_DEVICE: after one call at that B the call only enqueues kernels on `stream` -- no allocation,
+ * no host synchronisation (capturable); growth under capture returns IGT_E_STATE.  IGT_E_INVALID on a handle that is not
+ * IGT_COST_VALUE_NET (igt_cost_gradient_f64 keeps refusing those), for B < 0, for null buffers and for a bad mem; IGT_E_STATE
+ * when no network is loaded; B = 0 is a no-op.  There is no _f32 entry.  (Added without a change of IGT_VERSION; callers
+ * probe the symbol.) */
+int igt_cost_gradient_vn_f64(igt_handle* h, int32_t B, const double* x0, const double* kparams, const uint32_t* flags,
+                             const double* tv_sv, const double* enc, const double* U, double* cost_out, double* grad_out,
+                             int mem, void* stream);
+
 /* Workspace (owned by the handle, grown on the first solve of a batch size, never shrunk; growth synchronises the stream and is
  * refused under stream capture with IGT_E_STATE).  Per scenario, C = 256: 48 B of slice partials, 16 B of live-row masks and
  * incumbent keys (float64; float32: 8 B), 128 B of the acceleration rows' travel sums (float64), 768 B of horizon checkpoints of
