@@ -117,8 +117,11 @@ struct Fast64 {
     // MODE 0: general (K decided per stage argument); 1: K == 0 at every stage argument of every lane; 2: every stage
     // argument of every lane lies strictly inside the arc, K == kv.  All three give identical bits where they apply.
     // XY = false (search units whose obstacles are out of every candidate's reach): the Cartesian rows are not integrated
-    template <int MODE, bool XY = true>
+    // KEEP_D = false (MODE 1, a whole control step taken as K == 0): d0, d1 are left alone -- nothing reads them before
+    // step_head sets them again from s (substeps)
+    template <int MODE, bool XY = true, bool KEEP_D = true>
     __device__ __forceinline__ void substep(const StepConst& sc, Work& w) const {
+        static_assert(KEEP_D || MODE == 1, "only the K == 0 variant reads neither d0 nor d1");
         constexpr bool K0 = MODE == 1, KC = MODE == 2;
         const double ha = sc.ha, sblr = sc.sblr;
         const double v1 = w.v1;
@@ -200,7 +203,8 @@ struct Fast64 {
         }
         w.acc_psi = fma(h6, w1 + 4.0 * w2 + w4, w.acc_psi);
         w.acc_s += is; w.acc_ey += ie; w.acc_ep += ip;
-        w.d0 += is; w.d1 += is; w.ey += ie; w.v1 = v4;
+        if (KEEP_D) { w.d0 += is; w.d1 += is; }
+        w.ey += ie; w.v1 = v4;
         // ---- base pairs for the next sub-step: (psi+beta) advances by h w2, (beta+epsi) by h w2 - corr: the psi
         // advance turned back by corr.  K == 0: corr = 0 exactly, the extra turn is by (0, 1) -- bit-identical variants.
         if (XY) rotate(w.s2, w.c2, sdP, cdP);
@@ -219,12 +223,13 @@ struct Fast64 {
     // found by the N = 64 fuzz draws of round 4: an infeasible candidate 6 m off the road travelled 3.5 |v| dt in a step).
     // UNIFORM = false (emit: the lanes of a wave belong to different scenarios): the same choice by votes over the lanes.
     // the n_rk4 sub-steps of one variant; the reference's discretisation (4) is unrolled: no loop-carried register copies
-    template <int MODE, bool XY>
+    template <int MODE, bool XY, bool KEEP_D = true>
     __device__ __forceinline__ void run(const StepConst& sc, Work& w) const {
         if (NRK == 4 || (NRK == 0 && n_rk4 == 4)) {
-            substep<MODE, XY>(sc, w); substep<MODE, XY>(sc, w); substep<MODE, XY>(sc, w); substep<MODE, XY>(sc, w);
+            substep<MODE, XY, KEEP_D>(sc, w); substep<MODE, XY, KEEP_D>(sc, w);
+            substep<MODE, XY, KEEP_D>(sc, w); substep<MODE, XY, KEEP_D>(sc, w);
         } else {
-            for (int j = 0; j < nrk(); ++j) substep<MODE, XY>(sc, w);
+            for (int j = 0; j < nrk(); ++j) substep<MODE, XY, KEEP_D>(sc, w);
         }
     }
 
@@ -244,7 +249,9 @@ struct Fast64 {
         return sc;
     }
 
-    template <bool UNIFORM, bool XY = true>
+    // WHOLE_D = false (rollout_pool): a whole step taken as K == 0 leaves d0, d1 alone -- the next reader is the next control
+    // step's vote, and step_head sets both from s before it (kv_d; a straight route never reads them)
+    template <bool UNIFORM, bool XY = true, bool WHOLE_D = true>
     __device__ __forceinline__ void substeps(double a, double sblr, Work& w) const {
         const double ha = hh * a;
         const StepConst sc = step_const(a, sblr, w);
@@ -252,7 +259,7 @@ struct Fast64 {
         // scenario per lane) the whole-step decisions are taken by votes over the active lanes -- the variants are
         // bit-identical where they apply
         if (UNIFORM && kv == 0.0) {
-            run<1, XY>(sc, w);
+            run<1, XY, WHOLE_D>(sc, w);
             return;
         }
         {   // the whole control step: |travel| <= 2 dt (|v| + dt |a|)   (a straight route's d0, d1 are -inf: clear)
@@ -262,7 +269,7 @@ struct Fast64 {
             // every stage (|ey| moves by at most m / 2 within the step) -- a candidate metres off the road votes "general"
             const bool inside = (w.d0 - m > 0.0) & (w.d1 + m < 0.0) & (fabs(kv) * (fabs(w.ey) + 0.5 * m) < 0.5);
             if (__all(clear)) {
-                run<1, XY>(sc, w);
+                run<1, XY, WHOLE_D>(sc, w);
                 return;
             }
             if (__all(inside)) {
@@ -346,6 +353,52 @@ __device__ __forceinline__ void fill_steer_table(const KP& P, const Scenario<dou
     }
     __syncthreads();
 }
+// Steering table of a pool (rollout_pool without checkpoint slots): all G columns, [k][column][df, sblr, sdb, cdb] -- what the
+// pooled control step reads of the column and nothing else.  sin beta_k / l_r and the rotation by beta_k - beta_k-1 depend on
+// (column, k) alone; they are formed here once, by the statements step_head / step_tail run per lane and step on the same
+// operands ((sin, cos)(beta_-1) = (0, 1), as a fresh candidate carries them), so the same bits.  (sin, cos)(beta_k) pass
+// through slots 1, 2 on the way: the entries are finished from the last 64 down, each from its own pair and the pair one
+// step earlier (nj entries below it), which no later trip has rewritten yet.
+constexpr int POOL_STAB_FIELDS = 4;
+template <int CAND>
+__device__ __forceinline__ void fill_pool_table(const KP& P, const Scenario<double>& S, int nj, int lane, double lr_ratio,
+                                                double* __restrict__ stab) {
+    constexpr int F = POOL_STAB_FIELDS;
+    if (lane < nj) {
+        const int j = (lane & 1) ? P.G / 2 - 1 - (lane >> 1) : P.G / 2 + (lane >> 1);      // unit_candidate's column order
+        const double ddf = steer_column<CAND>(P, S, j);
+        double df = S.df_prev;
+        for (int k = 0; k < P.N; ++k) {
+            df = steer_next<CAND>(P, S, k, ddf, df);
+            stab[(k * nj + lane) * F] = df;
+        }
+    }
+    __syncthreads();
+    const int ne = nj * P.N;
+    for (int e = lane; e < ne; e += 64) {
+        double sb, cb;
+        slip_trig<CAND>(P, lr_ratio, stab[e * F], sb, cb);
+        stab[e * F + 1] = sb;
+        stab[e * F + 2] = cb;
+    }
+    __syncthreads();
+    const double inv_lr = 1.0 / P.l_r;                                  // Fast64::init
+    for (int base = ((ne - 1) >> 6) << 6; base >= 0; base -= 64) {
+        const int e = base + lane;
+        double sblr = 0.0, sdb = 0.0, cdb = 0.0;
+        if (e < ne) {
+            const double sb = stab[e * F + 1], cb = stab[e * F + 2];
+            double sb_prev = 0.0, cb_prev = 1.0;
+            if (e >= nj) { sb_prev = stab[(e - nj) * F + 1]; cb_prev = stab[(e - nj) * F + 2]; }
+            sblr = sb * inv_lr;                                         // step_head
+            sdb = fma(sb, cb_prev, -(cb * sb_prev));                    // step_tail
+            cdb = fma(cb, cb_prev, sb * sb_prev);
+        }
+        __syncthreads();                                                // every pair of this trip is read
+        if (e < ne) { stab[e * F + 1] = sblr; stab[e * F + 2] = sdb; stab[e * F + 3] = cdb; }
+    }
+    __syncthreads();
+}
 
 // ---- the incumbent bound (search, progress cost; used by the tracking family, whose candidates hardly ever fail a verdict) ----
 // A candidate's cost is  J = (non-negative stage terms, mpc.py:361-364) - (s_N - s_0)  (mpc.py:372), and the progress still to
@@ -402,7 +455,9 @@ struct LaneRoll {
 // roll-out of the float64 path runs these statements, so whatever runs them gives the same bits.
 // LEAN: |ey|, box v and collision folded into the running maximum gmax (search).  stab: the lane's steering column of the
 // table (entry k at stab[k * stab_stride]); CAND_TABLE: the lane's control sequence (see the table branch).
-template <int CAND, bool BOOK, bool LEAN, bool BOUND, bool STAB, int SEGMODE, class FP, class Sink>
+// STEPTAB (rollout_pool without checkpoint slots; lattice, STAB): the column is one of fill_pool_table's -- sblr comes from the
+// table, step_tail reads the rotation there, and (sin, cos)(beta_k), (sin, cos)(beta_k-1) are not carried by the lane at all.
+template <int CAND, bool BOOK, bool LEAN, bool BOUND, bool STAB, int SEGMODE, bool STEPTAB = false, class FP, class Sink>
 __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S, const FP& fp, LaneRoll<FP>& L, int k, int cidx,
                                           const double* __restrict__ table, const double* __restrict__ cinf, Sink& sink,
                                           const double* __restrict__ stab, int stab_stride, const unsigned long long* inc,
@@ -442,7 +497,11 @@ __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S
     }
     sink.ctrl(0, k, L.a, L.df);
     double sb, cb;                               // (sin, cos)(beta), beta = atan(r tan df)
-    if (STAB && (CAND == CAND_LATTICE || CAND == CAND_RAMP_HOLD)) {
+    if (STEPTAB) {
+        static_assert(!STEPTAB || (STAB && CAND == CAND_LATTICE && SEGMODE == 0 && !Sink::kKeepsStates),
+                      "the pool's table: search only, nothing resumes from or records (sin, cos)(beta)");
+        L.sblr = stab[k * stab_stride + 1];
+    } else if (STAB && (CAND == CAND_LATTICE || CAND == CAND_RAMP_HOLD)) {
         sb = stab[k * stab_stride + 1];
         cb = stab[k * stab_stride + 2];
     } else if (CAND == CAND_TRACK) {
@@ -459,9 +518,11 @@ __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S
     } else {
         slip_trig<CAND>(P, fp.lr_ratio, L.df, sb, cb);
     }
-    sink.slip(0, k, sb, cb);
-    L.sb = sb; L.cb = cb;
-    L.sblr = sb * fp.inv_lr;
+    if (!STEPTAB) {
+        sink.slip(0, k, sb, cb);
+        L.sb = sb; L.cb = cb;
+        L.sblr = sb * fp.inv_lr;
+    }
     // ---- bookkeeping of state k (cost in the oracle's order: control effort, epsi^2, ey^2 -- mpc.py:361-364)
     if (BOOK) {
         L.J = L.J + P.w_u * (L.a * L.a + L.df * L.df);
@@ -491,9 +552,11 @@ __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S
     }
     return (L.viol != 0) | (LEAN && L.gmax > P.tol);
 }
-template <bool BOOK, bool LEAN, bool BOUND, bool UNIFORM, bool XY, bool KEEP_PSI, class FP, class Sink>
+template <bool BOOK, bool LEAN, bool BOUND, bool UNIFORM, bool XY, bool KEEP_PSI, bool STEPTAB = false, bool WHOLE_D = true,
+          class FP, class Sink>
 __device__ __forceinline__ void step_tail(const KP& P, const Scenario<double>& S, const FP& fp, LaneRoll<FP>& L, int k, Sink& sink,
-                                          const unsigned long long* inc) {
+                                          const unsigned long long* inc, const double* __restrict__ stab = nullptr,
+                                          int stab_stride = 0) {
     if (BOOK && XY && k >= 1) {                                                  // collision, mpc.py:223-226
         for (int o = 0; o < P.n_obs; ++o) {
             const double dx = L.x - S.obs[(o * 2 + 0) * (P.N + 1) + k], dy = L.y - S.obs[(o * 2 + 1) * (P.N + 1) + k];
@@ -505,9 +568,15 @@ __device__ __forceinline__ void step_tail(const KP& P, const Scenario<double>& S
     // (sin,cos)(psi + beta_k) from (psi + beta_{k-1}), and (sin,cos)(epsi + beta_k) from (epsi + beta_{k-1}): rotate by
     // beta_k - beta_{k-1}, re-normalise (first order: the pairs are within rounding of unit length)
     {
-        const double sb = L.sb, cb = L.cb;
-        const double sdb = fma(sb, L.cb_prev, -(cb * L.sb_prev));
-        const double cdb = fma(cb, L.cb_prev, sb * L.sb_prev);
+        double sdb, cdb;
+        if (STEPTAB) {                                       // fill_pool_table: these statements, once per (column, k)
+            sdb = stab[k * stab_stride + 2];
+            cdb = stab[k * stab_stride + 3];
+        } else {
+            const double sb = L.sb, cb = L.cb;
+            sdb = fma(sb, L.cb_prev, -(cb * L.sb_prev));
+            cdb = fma(cb, L.cb_prev, sb * L.sb_prev);
+        }
         rotate(L.w.s1, L.w.c1, sdb, cdb);
         const double r1 = fma(fma(L.w.s1, L.w.s1, L.w.c1 * L.w.c1), -0.5, 1.5);
         L.w.s1 *= r1; L.w.c1 *= r1;
@@ -516,10 +585,10 @@ __device__ __forceinline__ void step_tail(const KP& P, const Scenario<double>& S
             const double r2 = fma(fma(L.w.s2, L.w.s2, L.w.c2 * L.w.c2), -0.5, 1.5);
             L.w.s2 *= r2; L.w.c2 *= r2;
         }
-        L.cb_prev = cb; L.sb_prev = sb;
+        if (!STEPTAB) { L.cb_prev = L.cb; L.sb_prev = L.sb; }
     }
     L.w.acc_s = 0.0; L.w.acc_ey = 0.0; L.w.acc_ep = 0.0; L.w.acc_x = 0.0; L.w.acc_y = 0.0; L.w.acc_psi = 0.0;
-    fp.template substeps<UNIFORM, XY>(L.a, L.sblr, L.w);
+    fp.template substeps<UNIFORM, XY, WHOLE_D>(L.a, L.sblr, L.w);
     L.s += L.w.acc_s; L.ey += L.w.acc_ey; L.ep += L.w.acc_ep;
     if (XY) { L.x += L.w.acc_x; L.y += L.w.acc_y; }
     if (KEEP_PSI) L.psi += L.w.acc_psi;        // psi feeds nothing back (search: dead code)
@@ -701,14 +770,18 @@ __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>&
 // wave lay out the window that starts at number `base` (igt_kernels_f64.hip search_pool64); it is called when the cursor first
 // reaches past the window (once per item when n <= POOL_TAB, i.e. C <= 256), with the values a refill used to compute on the
 // spot, so the same bits -- and a refill is a wave-uniform branch around a few LDS reads.
+// CKPT: with checkpoint slots (ck, rec: emit in pieces) over the three-double table of fill_steer_table; without them neither
+// is touched, nothing of the checkpoint cursor is carried, and the table is fill_pool_table's (step_head / step_tail STEPTAB).
+// The four-double table does not fit beside the slots in the 20 KB a wave may take (eight waves per compute unit).
 constexpr int POOL_START = 13, POOL_TAB = 256;
-template <int CAND, bool HI_ORDER, int NRK, bool XY, class Fill>
+template <int CAND, bool HI_ORDER, int NRK, bool XY, bool CKPT, class Fill>
 __device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>& S, int n, const Fill& fill,
                                              const double* __restrict__ cinf, const double* __restrict__ stab, int stab_stride,
                                              double* ck, double* rec, double* start, unsigned* tabw, double* tabda,
                                              double& wJ, int& wC) {
     static_assert(CAND == CAND_LATTICE, "pool roll-out: the lattice family (its steering is a column of the table)");
     constexpr int CKF = 5;
+    constexpr int SF = CKPT ? 3 : POOL_STAB_FIELDS;          // doubles per table entry
     typedef Fast64<HI_ORDER, NRK> FP;
     FP fp;
     fp.init(P, S.b0, S.b1, S.kv);
@@ -755,13 +828,15 @@ __device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>
                 const unsigned w = tabw[e];
                 L.da = tabda[e];
                 c = (int)(w & 0xffffu);
-                lstab = stab + (w >> 16) * 3;
+                lstab = stab + (w >> 16) * SF;
                 L.x = start[0]; L.y = start[1]; L.s = start[2]; L.ey = start[3]; L.ep = start[4]; L.v = start[5];
                 L.a = start[7]; L.df = start[8]; L.J = 0.0; L.gmax = -1.0e300; L.viol = 0u;
                 L.w.d0 = L.w.d1 = 0.0;
                 L.w.s1 = start[9]; L.w.c1 = start[10]; L.w.s2 = start[11]; L.w.c2 = start[12];
-                L.cb_prev = 1.0; L.sb_prev = 0.0;
-                L.ck_q = 1; L.ck_k = ck ? ckpt_step(P.N, 1) : -1;
+                if (CKPT) {
+                    L.cb_prev = 1.0; L.sb_prev = 0.0;
+                    L.ck_q = 1; L.ck_k = ck ? ckpt_step(P.N, 1) : -1;
+                }
                 k = 0; hold = true;
             }
             next += cnt;
@@ -772,9 +847,9 @@ __device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>
         bool fin = false;
         double Jq = 0.0;
         if (hold) {
-            const bool lost = step_head<CAND, true, true, false, true, 1>(P, S, fp, L, k, c, nullptr, cinf, sink, lstab, stab_stride,
-                                                                          nullptr, ck, true, kv_d);
-            step_tail<true, true, false, true, XY, false>(P, S, fp, L, k, sink, nullptr);
+            const bool lost = step_head<CAND, true, true, false, true, CKPT ? 1 : 0, !CKPT>(P, S, fp, L, k, c, nullptr, cinf, sink,
+                                                                                            lstab, stab_stride, nullptr, ck, true, kv_d);
+            step_tail<true, true, false, true, XY, false, !CKPT, false>(P, S, fp, L, k, sink, nullptr, lstab, stab_stride);
             ++k;
             if (lost) {
                 hold = false;
@@ -804,7 +879,7 @@ __device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>
             bC = __builtin_amdgcn_readfirstlane(bC);
             if (wC < 0 || bJ < wJ || (bJ == wJ && bC < wC)) {
                 wJ = bJ; wC = bC;
-                if (ck && fin && c == bC) {                   // the new winner's checkpoints, [q][field]
+                if (CKPT && ck && fin && c == bC) {           // the new winner's checkpoints, [q][field]
 #pragma unroll
                     for (int q = 0; q < CK_PARTS - 1; ++q)
 #pragma unroll

@@ -432,7 +432,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 // column rank r from the centre outwards, q the rank among the live rows.  The steering table holds all G columns.  The item
 // leaves the scenario's best (J, c) in slot 0 of its W partials, (0, -1) in the others, and with checkpoint slots the winner's
 // record in slot 0: the emit kernels read the partials as they read the units'.
-template <int CAND, bool HI, int NRK>
+template <int CAND, bool HI, int NRK, bool CKPT>
 __device__ __forceinline__ void search_pool64(const KP& P, int W, int b, const double* __restrict__ x0,
                                               const double* __restrict__ u_prev, const double* __restrict__ kparams,
                                               const uint32_t* __restrict__ flags, const double* __restrict__ obs,
@@ -444,9 +444,10 @@ __device__ __forceinline__ void search_pool64(const KP& P, int W, int b, const d
     const int R = __builtin_amdgcn_readfirstlane(L.R), n = P.G * R;
     constexpr int CKF = 5;
     __shared__ int rank2row[64];
-    __shared__ double stab[f64::STAB_MAX_ENTRIES * 3];
-    __shared__ double ckl[(f64::CK_PARTS - 1) * CKF * 64];
-    __shared__ double rec[(f64::CK_PARTS - 1) * CKF];
+    // CKPT (DEV_LAUNCH_CKPT: emit in pieces): checkpoint slots and the three-double table; else no slots and the pool's table
+    __shared__ double stab[f64::STAB_MAX_ENTRIES * (CKPT ? 3 : f64::POOL_STAB_FIELDS)];
+    __shared__ double ckl[CKPT ? (f64::CK_PARTS - 1) * CKF * 64 : 1];
+    __shared__ double rec[CKPT ? (f64::CK_PARTS - 1) * CKF : 1];
     __shared__ double start[f64::POOL_START];
     __shared__ unsigned tabw[f64::POOL_TAB];
     __shared__ double tabda[f64::POOL_TAB];
@@ -456,7 +457,8 @@ __device__ __forceinline__ void search_pool64(const KP& P, int W, int b, const d
         Scenario<double> S;
         load_scenario<double>(S, P, b, x0, u_prev, kparams, flags, obs, cpar);
         rows_by_rank(L, lane, rank2row);
-        f64::fill_steer_table<CAND>(P, S, P.G, 0, lane, P.lr_ratio, stab);
+        if (CKPT) f64::fill_steer_table<CAND>(P, S, P.G, 0, lane, P.lr_ratio, stab);
+        else f64::fill_pool_table<CAND>(P, S, P.G, lane, P.lr_ratio, stab);
         // the window of the refill table that starts at candidate number `base`: unit_candidate's numbering, cand_increments' da.
         // What it derives from R and G is derived here, behind the refill's branch, not held in registers over the control steps:
         // the empty asm makes the two opaque there.  The ISA is the check (profiles/r07_pool_loop_isa.txt): the reciprocal of R and
@@ -476,16 +478,17 @@ __device__ __forceinline__ void search_pool64(const KP& P, int W, int b, const d
             __syncthreads();
         };
         const bool far = !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
-        double* ck = ck_all ? ckl + lane : nullptr;
-        if (far) f64::rollout_pool<CAND, HI, NRK, false>(P, S, n, fill, cinf, stab, P.G * 3, ck, rec, start, tabw, tabda, wJ, wC);
-        else f64::rollout_pool<CAND, HI, NRK, true>(P, S, n, fill, cinf, stab, P.G * 3, ck, rec, start, tabw, tabda, wJ, wC);
+        double* ck = (CKPT && ck_all) ? ckl + lane : nullptr;
+        const int stride = P.G * (CKPT ? 3 : f64::POOL_STAB_FIELDS);
+        if (far) f64::rollout_pool<CAND, HI, NRK, false, CKPT>(P, S, n, fill, cinf, stab, stride, ck, rec, start, tabw, tabda, wJ, wC);
+        else f64::rollout_pool<CAND, HI, NRK, true, CKPT>(P, S, n, fill, cinf, stab, stride, ck, rec, start, tabw, tabda, wJ, wC);
         __syncthreads();                                  // rec is complete; the next item of this wave rewrites the tables
     }
     if (lane < W) {
         part_J[b * W + lane] = lane == 0 ? wJ : 0.0;
         part_c[b * W + lane] = lane == 0 ? wC : -1;
     }
-    if (ck_all && wC >= 0 && lane < CKF * (f64::CK_PARTS - 1)) {
+    if (CKPT && ck_all && wC >= 0 && lane < CKF * (f64::CK_PARTS - 1)) {
         const int q = lane / CKF, f = lane - q * CKF;
         ck_all[(size_t)(b * W) * CK_RECORD + q * f64::CK_FIELDS + f] = rec[lane];
     }
@@ -499,12 +502,12 @@ __host__ __device__ inline bool search_pools(const KP& P, int cand, bool value, 
            !(P.dev & (DEV_NO_SLICES | DEV_NO_EARLY_EXIT | DEV_NO_STEER_TABLE | DEV_ALL_ROWS | DEV_WHOLE_COLUMNS | DEV_NO_REFILL |
                       DEV_SEPARATE_QUEUES | DEV_WAVES3));
 }
-template <int CAND, bool HI, bool VALUE, int NRK>
+template <int CAND, bool HI, bool VALUE, int NRK, bool CKPT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_f64_kernel_pool(IGT_SEARCH64_ARGS) {
     if constexpr (CAND == CAND_LATTICE && !VALUE) {
         search_waves(P, B, 1, queues, work_counter, order, order_stride, [&](int b, int) {
-            search_pool64<CAND, HI, NRK>(P, W, b, x0, u_prev, kparams, flags, obs, cinf, cpar, part_J, part_c,
-                                         live_rows_of(P, B, W, part_J), checkpoints_of(P, B, W, part_J));
+            search_pool64<CAND, HI, NRK, CKPT>(P, W, b, x0, u_prev, kparams, flags, obs, cinf, cpar, part_J, part_c,
+                                               live_rows_of(P, B, W, part_J), CKPT ? checkpoints_of(P, B, W, part_J) : nullptr);
         });
     }
 }
@@ -1223,14 +1226,16 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
     if constexpr (CAND == CAND_LATTICE && !VALUE) if (pools) {
         const size_t pgrid = (size_t)B < slots ? (size_t)B : slots;
         constexpr int NRK4 = HI ? 0 : 4;
-        if (NRK4 == 4 && P.n_rk4 == 4)
-            hipLaunchKernelGGL((search_f64_kernel_pool<CAND, HI, VALUE, NRK4>), dim3(pgrid), dim3(64), 0, st, Pr, B, W, 8, A.work_counter,
-                               order, order_stride, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J,
-                               A.part_c, A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b, A.unit_seg);
-        else
-            hipLaunchKernelGGL((search_f64_kernel_pool<CAND, HI, VALUE, 0>), dim3(pgrid), dim3(64), 0, st, Pr, B, W, 8, A.work_counter,
-                               order, order_stride, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J,
-                               A.part_c, A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b, A.unit_seg);
+        // with checkpoint records to leave (emit in pieces) the build that carries the slots; else the one without them
+        const bool ckpt = (Pr.dev & DEV_LAUNCH_CKPT) != 0;
+#define IGT_LAUNCH_POOL(NRK_, CKPT_)                                                                                          \
+        hipLaunchKernelGGL((search_f64_kernel_pool<CAND, HI, VALUE, NRK_, CKPT_>), dim3(pgrid), dim3(64), 0, st, Pr, B, W, 8,   \
+                           A.work_counter, order, order_stride, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf,   \
+                           A.centre(), A.part_J, A.part_c, A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b,     \
+                           A.unit_seg)
+        if (NRK4 == 4 && P.n_rk4 == 4) { if (ckpt) IGT_LAUNCH_POOL(NRK4, true); else IGT_LAUNCH_POOL(NRK4, false); }
+        else { if (ckpt) IGT_LAUNCH_POOL(0, true); else IGT_LAUNCH_POOL(0, false); }
+#undef IGT_LAUNCH_POOL
         return hipGetLastError();
     }
 #if IGT_DEV_KERNELS
