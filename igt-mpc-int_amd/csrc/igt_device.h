@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "igt_dispatch.h"   // the CAND_* families
 #include "igt_math64.h"
 
 // Developer kernels (A/B timing and cross-checks, selected at run time through IGT_DEV_FLAGS): the 3-waves-per-SIMD builds
@@ -74,7 +75,6 @@ struct KP {  // kernel parameters (by value -> SGPRs)
     double trk_vmax, inv_dt, inv_rate_a;    // IGT_CAND_TRACK: the speed the cap of the targets looks ahead to (+inf = no cap); 1 / dt, 1 / rate_a
 };
 
-enum { CAND_LATTICE = 0, CAND_TABLE = 1, CAND_RAMP_HOLD = 2, CAND_TRACK = 3 };
 enum { VIOL_BOX_V = 1, VIOL_BOX_U = 2, VIOL_RATE = 4, VIOL_EY = 8, VIOL_TERMINAL = 16,
        VIOL_COLLISION = 32, VIOL_NONFINITE = 64 };
 

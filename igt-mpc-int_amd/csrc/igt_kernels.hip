@@ -674,6 +674,15 @@ bool search_builds_queues(const KP& P, int B, const SolveArgs<float>& A) {
     const int W = (P.C + 127) / 128;
     return A.queue_order && W <= 256 && ((B + 7) / 8) * W <= QB_THREADS * QB_TRIPS && !(P.dev & DEV_NO_QUEUE_ORDER);
 }
+// The arguments every float search kernel takes (IGT_SEARCH_ARGS), out of SolveArgs
+template <class Kernel>
+static hipError_t launch_search_kernel(Kernel kernel, size_t grid, const KP& Pr, int B, int W, int queues, const unsigned* order,
+                                       int order_stride, const SolveArgs<float>& A, hipStream_t st) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, st, Pr, B, W, queues, A.work_counter, order, order_stride, A.ckpt, A.ck_parts,
+                       A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.rec_sN, A.rec_vN,
+                       A.rec_J, A.rec_viol, A.rec_count, A.rec_b);
+    return hipGetLastError();
+}
 template <int CAND, bool HI, bool VALUE>
 static hipError_t launch_search_fast(const KP& P, int B, const SolveArgs<float>& A, hipStream_t st) {
     const int W = (P.C + 127) / 128;
@@ -703,38 +712,19 @@ static hipError_t launch_search_fast(const KP& P, int B, const SolveArgs<float>&
         order = A.queue_order;
     }
 #if IGT_DEV_KERNELS
-    if (o3)
-        hipLaunchKernelGGL((search_fast_kernel_o3<CAND, HI, VALUE>), dim3(grid), dim3(64), 0, st, Pr, B, W, 8, A.work_counter,
-                           order, order_stride, A.ckpt, A.ck_parts, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.rec_sN,
-                           A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b);
-    else
+    if (o3) return launch_search_kernel(search_fast_kernel_o3<CAND, HI, VALUE>, grid, Pr, B, W, 8, order, order_stride, A, st);
 #endif
     if (A.ckpt && A.ck_parts > 1)
-        hipLaunchKernelGGL((search_fast_kernel_o2c<CAND, HI, VALUE>), dim3(grid), dim3(64), 0, st, Pr, B, W, 8, A.work_counter,
-                           order, order_stride, A.ckpt, A.ck_parts, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf,
-                           A.centre(), A.part_J, A.part_c, A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b);
-    else if constexpr (CAND == CAND_TRACK)
-        hipLaunchKernelGGL((search_fast_kernel_o2w<CAND, HI, VALUE>), dim3(grid), dim3(64), 0, st, Pr, B, W, 8, A.work_counter,
-                           order, order_stride, A.ckpt, A.ck_parts, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.rec_sN,
-                           A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b);
+        return launch_search_kernel(search_fast_kernel_o2c<CAND, HI, VALUE>, grid, Pr, B, W, 8, order, order_stride, A, st);
+    if constexpr (CAND == CAND_TRACK)
+        return launch_search_kernel(search_fast_kernel_o2w<CAND, HI, VALUE>, grid, Pr, B, W, 8, order, order_stride, A, st);
     else
-        hipLaunchKernelGGL((search_fast_kernel_o2<CAND, HI, VALUE>), dim3(grid), dim3(64), 0, st, Pr, B, W, 8, A.work_counter,
-                           order, order_stride, A.ckpt, A.ck_parts, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.rec_sN,
-                           A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b);
-    return hipGetLastError();
+        return launch_search_kernel(search_fast_kernel_o2<CAND, HI, VALUE>, grid, Pr, B, W, 8, order, order_stride, A, st);
 }
 template <bool VALUE>
 static hipError_t dispatch_search_fast(const KP& P, int B, const SolveArgs<float>& A, hipStream_t st) {
-    if (P.hi_order) {
-        if (P.cand_mode == CAND_LATTICE) return launch_search_fast<CAND_LATTICE, true, VALUE>(P, B, A, st);
-        if (P.cand_mode == CAND_RAMP_HOLD) return launch_search_fast<CAND_RAMP_HOLD, true, VALUE>(P, B, A, st);
-        if (P.cand_mode == CAND_TRACK) return launch_search_fast<CAND_TRACK, true, VALUE>(P, B, A, st);
-        return launch_search_fast<CAND_TABLE, true, VALUE>(P, B, A, st);
-    }
-    if (P.cand_mode == CAND_LATTICE) return launch_search_fast<CAND_LATTICE, false, VALUE>(P, B, A, st);
-    if (P.cand_mode == CAND_RAMP_HOLD) return launch_search_fast<CAND_RAMP_HOLD, false, VALUE>(P, B, A, st);
-    if (P.cand_mode == CAND_TRACK) return launch_search_fast<CAND_TRACK, false, VALUE>(P, B, A, st);
-    return launch_search_fast<CAND_TABLE, false, VALUE>(P, B, A, st);
+    return with_family(P.cand_mode, P.hi_order,
+                       [&](auto cand, auto hi) { return launch_search_fast<cand(), hi(), VALUE>(P, B, A, st); });
 }
 
 template <>
@@ -783,11 +773,12 @@ hipError_t launch_terminal_value(const DevNet<double>& net, int n_cu, int n, con
     const int groups = (n + 15) / 16;
     const dim3 grid(groups < n_cu ? groups : n_cu), block(256);
     const size_t lds = (size_t)FRAGD_LDS * sizeof(double);
-#define IGT_LAUNCH_TV(NM_, GRAD_) \
-    hipLaunchKernelGGL((terminal_value_f64_kernel<NM_, GRAD_>), grid, block, lds, st, net, n, sv, tv_sv, enc, V_out, dV_out)
-    if (net.n_hidden_mats > 1) { if (dV_out) IGT_LAUNCH_TV(2, true); else IGT_LAUNCH_TV(2, false); }
-    else { if (dV_out) IGT_LAUNCH_TV(1, true); else IGT_LAUNCH_TV(1, false); }
-#undef IGT_LAUNCH_TV
+    with_bool(net.n_hidden_mats > 1, [&](auto deep) {
+        with_bool(dV_out != nullptr, [&](auto grad) {
+            hipLaunchKernelGGL((terminal_value_f64_kernel<deep() ? 2 : 1, grad()>), grid, block, lds, st, net, n, sv, tv_sv, enc, V_out,
+                               dV_out);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -896,38 +887,17 @@ static hipError_t launch_emit_fast(const KP& P, int B, int W, const SolveArgs<fl
 // float path: W per-slice partials per scenario are reduced here; double path: argmin_out is already final
 template <>
 hipError_t launch_emit<float>(const KP& P, int B, int W, const SolveArgs<float>& A, hipStream_t st) {
-    if (P.hi_order) {
-        if (P.cand_mode == CAND_LATTICE) return launch_emit_fast<CAND_LATTICE, true>(P, B, W, A, st);
-        if (P.cand_mode == CAND_RAMP_HOLD) return launch_emit_fast<CAND_RAMP_HOLD, true>(P, B, W, A, st);
-        if (P.cand_mode == CAND_TRACK) return launch_emit_fast<CAND_TRACK, true>(P, B, W, A, st);
-        return launch_emit_fast<CAND_TABLE, true>(P, B, W, A, st);
-    }
-    if (P.cand_mode == CAND_LATTICE) return launch_emit_fast<CAND_LATTICE, false>(P, B, W, A, st);
-    if (P.cand_mode == CAND_RAMP_HOLD) return launch_emit_fast<CAND_RAMP_HOLD, false>(P, B, W, A, st);
-    if (P.cand_mode == CAND_TRACK) return launch_emit_fast<CAND_TRACK, false>(P, B, W, A, st);
-    return launch_emit_fast<CAND_TABLE, false>(P, B, W, A, st);
-}
-template <int CAND, bool HI>
-static hipError_t launch_rollout_all_fast(const KP& P, int B, const SolveArgs<float>& A, float* X_all, float* U_all,
-                                          float* cost_all, uint32_t* viol_all, hipStream_t st) {
-    hipLaunchKernelGGL((rollout_all_fast_kernel<CAND, HI>), dim3((B + 3) / 4), dim3(256), 0, st, P, B, A.x0, A.u_prev,
-                       A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), X_all, U_all, cost_all, viol_all, A.rec_sN, A.rec_vN,
-                       A.rec_J, A.rec_viol);
-    return hipGetLastError();
+    return with_family(P.cand_mode, P.hi_order, [&](auto cand, auto hi) { return launch_emit_fast<cand(), hi()>(P, B, W, A, st); });
 }
 template <>
 hipError_t launch_rollout_all<float>(const KP& P, int B, const SolveArgs<float>& A, float* X_all, float* U_all,
                                      float* cost_all, uint32_t* viol_all, hipStream_t st) {
-    if (P.hi_order) {
-        if (P.cand_mode == CAND_LATTICE) return launch_rollout_all_fast<CAND_LATTICE, true>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-        if (P.cand_mode == CAND_RAMP_HOLD) return launch_rollout_all_fast<CAND_RAMP_HOLD, true>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-        if (P.cand_mode == CAND_TRACK) return launch_rollout_all_fast<CAND_TRACK, true>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-        return launch_rollout_all_fast<CAND_TABLE, true>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-    }
-    if (P.cand_mode == CAND_LATTICE) return launch_rollout_all_fast<CAND_LATTICE, false>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-    if (P.cand_mode == CAND_RAMP_HOLD) return launch_rollout_all_fast<CAND_RAMP_HOLD, false>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-    if (P.cand_mode == CAND_TRACK) return launch_rollout_all_fast<CAND_TRACK, false>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-    return launch_rollout_all_fast<CAND_TABLE, false>(P, B, A, X_all, U_all, cost_all, viol_all, st);
+    return with_family(P.cand_mode, P.hi_order, [&](auto cand, auto hi) {
+        hipLaunchKernelGGL((rollout_all_fast_kernel<cand(), hi()>), dim3((B + 3) / 4), dim3(256), 0, st, P, B, A.x0, A.u_prev,
+                           A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), X_all, U_all, cost_all, viol_all, A.rec_sN, A.rec_vN,
+                           A.rec_J, A.rec_viol);
+        return hipGetLastError();
+    });
 }
 template <>
 hipError_t launch_frenet_step<float>(const KP& P, int n, const float* x, const float* u, const float* kparams,

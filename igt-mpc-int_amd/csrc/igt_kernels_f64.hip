@@ -1095,14 +1095,11 @@ template <bool VALUE>
 static hipError_t launch_search_exact(const KP& P, int B, const SolveArgs<double>& A, hipStream_t st) {
     typedef ExactStepper<double> St;
     const dim3 grid((B + 3) / 4), block(256);
-    if (P.cand_mode != CAND_TABLE)
-        hipLaunchKernelGGL((search_kernel<St, double, 1, true, VALUE>), grid, block, 0, st, P, B, A.x0, A.u_prev,
+    with_bool(P.cand_mode != CAND_TABLE, [&](auto shared_df) {
+        hipLaunchKernelGGL((search_kernel<St, double, 1, shared_df(), VALUE>), grid, block, 0, st, P, B, A.x0, A.u_prev,
                            A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.cost_out, A.argmin_out, A.status_out,
                            A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol);
-    else
-        hipLaunchKernelGGL((search_kernel<St, double, 1, false, VALUE>), grid, block, 0, st, P, B, A.x0, A.u_prev,
-                           A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.cost_out, A.argmin_out, A.status_out,
-                           A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol);
+    });
     return hipGetLastError();
 }
 
@@ -1160,8 +1157,26 @@ static bool packs_live_rows(const KP& P, int B, const SolveArgs<double>& A) {
            !(P.dev & (DEV_NO_SLICES | DEV_EXACT64 | DEV_LITERAL | DEV_ALL_ROWS)) && !captures_trajectories(P, A) && (size_t)B * W > (size_t)A.n_cu * 16;
 }
 
+// The arguments every float64 search kernel takes (IGT_SEARCH64_ARGS), out of SolveArgs; more: what one kernel takes behind
+// them (search_f64_kernel_cap: the trajectories)
+template <class Kernel, class... More>
+static hipError_t launch_search_kernel(Kernel kernel, size_t grid, const KP& Pr, int B, int W, int queues, const unsigned* order,
+                                       int order_stride, const SolveArgs<double>& A, hipStream_t st, More... more) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, st, Pr, B, W, queues, A.work_counter, order, order_stride, A.x0, A.u_prev,
+                       A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.rec_sN, A.rec_vN, A.rec_J,
+                       A.rec_viol, A.rec_count, A.rec_b, A.unit_seg, more...);
+    return hipGetLastError();
+}
+// f(CAND, HI, NRK) as constants: the candidate family and the build of the control step that P asks for (igt_dispatch.h)
+template <class F>
+static hipError_t with_build(const KP& P, F&& f) {
+    return with_cand(P.cand_mode, [&](auto cand) {
+        return with_discretisation(P.hi_order, P.n_rk4, [&](auto hi, auto nrk) { return f(cand, hi, nrk); });
+    });
+}
+
 // float64 search: persistent waves on the per-XCD queues, one 64-candidate unit at a time
-template <int CAND, bool HI, bool VALUE>
+template <int CAND, bool HI, int NRK, bool VALUE>
 static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A, hipStream_t st) {
     const int W = P.C / 64;
 #if IGT_DEV_KERNELS
@@ -1183,12 +1198,8 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
     // B = 4096: 2 per wave, search 0.208 -> 0.230 ms; four solves in flight, one wave per SIMD: 4 per wave, 23.6 -> 27.0 M solves/s)
     const bool pools = !o3 && search_pools(P, CAND, VALUE, packs_live_rows(P, B, A)) && (size_t)B >= 4 * slots;
     const int order_stride = ((B + 7) / 8) * (pools ? 1 : W);
-    if (!HI && search_is_static(P, B, A)) {
-        hipLaunchKernelGGL((search_f64_kernel_cap<CAND, VALUE>), dim3(total), dim3(64), 0, st, P, B, W, 0, A.work_counter, order,
-                           order_stride, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c,
-                           A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b, A.unit_seg, A.traj);
-        return hipGetLastError();
-    }
+    if (!HI && search_is_static(P, B, A))
+        return launch_search_kernel(search_f64_kernel_cap<CAND, VALUE>, total, P, B, W, 0, order, order_stride, A, st, A.traj);
     // the live-row masks and the checkpoint records live behind the partials (PartJTail): no further kernel argument -- the
     // search kernels spill scalar registers as it is, and every one more shows up as v_readlane in the control-step loop
     KP Pr = P;
@@ -1202,13 +1213,12 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
             const int n_groups = (B + per_block - 1) / per_block;
             // small batches: the same launch sorts the queues (longest units first)
             queues_built = search_builds_queues(P, B, A) && !(P.dev & DEV_SEPARATE_QUEUES);
-#define IGT_LAUNCH_ROWS(QUEUES_)                                                                                              \
-            hipLaunchKernelGGL((accel_rows_kernel<CAND, QUEUES_>), dim3(n_groups + (QUEUES_ ? 8 : 0)), dim3(ROWS_THREADS), 0, st, P, \
-                               B, A.x0, A.u_prev, A.flags, A.cinf, A.centre(), A.row_mask, A.row_rems,        \
-                               W, A.kparams, A.queue_order, order_stride,           \
-                               A.work_counter, pools ? W : 0)
-            if (queues_built) { IGT_LAUNCH_ROWS(true); order = A.queue_order; } else IGT_LAUNCH_ROWS(false);
-#undef IGT_LAUNCH_ROWS
+            with_bool(queues_built, [&](auto queues) {
+                hipLaunchKernelGGL((accel_rows_kernel<CAND, queues()>), dim3(n_groups + (queues() ? 8 : 0)), dim3(ROWS_THREADS), 0, st,
+                                   P, B, A.x0, A.u_prev, A.flags, A.cinf, A.centre(), A.row_mask, A.row_rems, W, A.kparams,
+                                   A.queue_order, order_stride, A.work_counter, pools ? W : 0);
+            });
+            if (queues_built) order = A.queue_order;
             Pr.dev |= DEV_LAUNCH_LIVE_ROWS;
         }
     }
@@ -1217,66 +1227,31 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
                            A.queue_order, order_stride, A.work_counter, rows);
         order = A.queue_order;
     }
-    if (!HI && captures_trajectories(P, A)) {
-        hipLaunchKernelGGL((search_f64_kernel_cap<CAND, VALUE>), dim3(grid), dim3(64), 0, st, P, B, W, 8, A.work_counter, order,
-                           order_stride, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c,
-                           A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b, A.unit_seg, A.traj);
-        return hipGetLastError();
-    }
+    if (!HI && captures_trajectories(P, A))
+        return launch_search_kernel(search_f64_kernel_cap<CAND, VALUE>, grid, P, B, W, 8, order, order_stride, A, st, A.traj);
     if constexpr (CAND == CAND_LATTICE && !VALUE) if (pools) {
         const size_t pgrid = (size_t)B < slots ? (size_t)B : slots;
-        constexpr int NRK4 = HI ? 0 : 4;
         // with checkpoint records to leave (emit in pieces) the build that carries the slots; else the one without them
-        const bool ckpt = (Pr.dev & DEV_LAUNCH_CKPT) != 0;
-#define IGT_LAUNCH_POOL(NRK_, CKPT_)                                                                                          \
-        hipLaunchKernelGGL((search_f64_kernel_pool<CAND, HI, VALUE, NRK_, CKPT_>), dim3(pgrid), dim3(64), 0, st, Pr, B, W, 8,   \
-                           A.work_counter, order, order_stride, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf,   \
-                           A.centre(), A.part_J, A.part_c, A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b,     \
-                           A.unit_seg)
-        if (NRK4 == 4 && P.n_rk4 == 4) { if (ckpt) IGT_LAUNCH_POOL(NRK4, true); else IGT_LAUNCH_POOL(NRK4, false); }
-        else { if (ckpt) IGT_LAUNCH_POOL(0, true); else IGT_LAUNCH_POOL(0, false); }
-#undef IGT_LAUNCH_POOL
-        return hipGetLastError();
+        return with_bool((Pr.dev & DEV_LAUNCH_CKPT) != 0, [&](auto ckpt) {
+            return launch_search_kernel(search_f64_kernel_pool<CAND, HI, VALUE, NRK, ckpt()>, pgrid, Pr, B, W, 8, order,
+                                        order_stride, A, st);
+        });
     }
 #if IGT_DEV_KERNELS
-    if (o3)
-        hipLaunchKernelGGL((search_f64_kernel_o3<CAND, HI, VALUE>), dim3(grid), dim3(64), 0, st, Pr, B, W, 8, A.work_counter, order,
-                           order_stride, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c,
-                           A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b, A.unit_seg);
-    else
+    if (o3) return launch_search_kernel(search_f64_kernel_o3<CAND, HI, VALUE>, grid, Pr, B, W, 8, order, order_stride, A, st);
 #endif
-    {
-        // the reference's discretisation (4 sub-steps, short polynomials) has its own build of the kernel
-        constexpr int NRK4 = HI ? 0 : 4;
-        const bool rk4 = NRK4 == 4 && P.n_rk4 == 4;
-#define IGT_LAUNCH_S64(KERNEL, NRK_)                                                                                          \
-        hipLaunchKernelGGL((KERNEL<CAND, HI, VALUE, NRK_>), dim3(grid), dim3(64), 0, st, Pr, B, W, 8, A.work_counter, order,    \
-                           order_stride, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, \
-                           A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b, A.unit_seg)
-        if constexpr (CAND == CAND_TRACK) {
-            if (rk4) IGT_LAUNCH_S64(search_f64_kernel_o2w, NRK4); else IGT_LAUNCH_S64(search_f64_kernel_o2w, 0);
-        } else {
-            if (rk4) IGT_LAUNCH_S64(search_f64_kernel_o2, NRK4); else IGT_LAUNCH_S64(search_f64_kernel_o2, 0);
-        }
-#undef IGT_LAUNCH_S64
-    }
-    return hipGetLastError();
+    // NRK = 4: the reference's discretisation (4 sub-steps, short polynomials) has its own build of the kernel
+    if constexpr (CAND == CAND_TRACK)
+        return launch_search_kernel(search_f64_kernel_o2w<CAND, HI, VALUE, NRK>, grid, Pr, B, W, 8, order, order_stride, A, st);
+    else
+        return launch_search_kernel(search_f64_kernel_o2<CAND, HI, VALUE, NRK>, grid, Pr, B, W, 8, order, order_stride, A, st);
 }
 template <bool VALUE>
 static hipError_t dispatch_search64(const KP& P, int B, const SolveArgs<double>& A, hipStream_t st) {
 #if IGT_DEV_KERNELS
     if (P.dev & DEV_EXACT64) return launch_search_exact<VALUE>(P, B, A, st);     // developer switch: oracle-order kernels
 #endif
-    if (P.hi_order) {
-        if (P.cand_mode == CAND_LATTICE) return launch_search64<CAND_LATTICE, true, VALUE>(P, B, A, st);
-        if (P.cand_mode == CAND_RAMP_HOLD) return launch_search64<CAND_RAMP_HOLD, true, VALUE>(P, B, A, st);
-        if (P.cand_mode == CAND_TRACK) return launch_search64<CAND_TRACK, true, VALUE>(P, B, A, st);
-        return launch_search64<CAND_TABLE, true, VALUE>(P, B, A, st);
-    }
-    if (P.cand_mode == CAND_LATTICE) return launch_search64<CAND_LATTICE, false, VALUE>(P, B, A, st);
-    if (P.cand_mode == CAND_RAMP_HOLD) return launch_search64<CAND_RAMP_HOLD, false, VALUE>(P, B, A, st);
-    if (P.cand_mode == CAND_TRACK) return launch_search64<CAND_TRACK, false, VALUE>(P, B, A, st);
-    return launch_search64<CAND_TABLE, false, VALUE>(P, B, A, st);
+    return with_build(P, [&](auto cand, auto hi, auto nrk) { return launch_search64<cand(), hi(), nrk(), VALUE>(P, B, A, st); });
 }
 template <>
 hipError_t launch_search<double>(const KP& P, int B, const SolveArgs<double>& A, int, hipStream_t st) {
@@ -1287,60 +1262,38 @@ hipError_t launch_search_records<double>(const KP& P, int B, const SolveArgs<dou
     return dispatch_search64<true>(P, B, A, st);
 }
 
-template <int CAND, bool HI>
+template <int CAND, bool HI, int NRK>
 static hipError_t launch_emit64(const KP& P, int B, int W, const SolveArgs<double>& A, hipStream_t st) {
-    constexpr int NRK4 = HI ? 0 : 4;
     if (!HI && captures_trajectories(P, A)) {
         hipLaunchKernelGGL((emit_gather_f64_kernel<CAND>), dim3(B), dim3(64), 0, st, P, B, W, A.part_J, A.part_c, A.traj, A.cost_out,
                            A.argmin_out, A.status_out, A.x_out, A.u_out);
-        return hipGetLastError();
-    }
-    if (emits_in_pieces(P, A)) {
+    } else if (emits_in_pieces(P, A)) {
         const int S = seg_scenarios_per_block(P);
         const size_t lds = (size_t)S * seg_doubles_per_scenario(P.N) * 8;
-        if (NRK4 == 4 && P.n_rk4 == 4)
-            hipLaunchKernelGGL((emit_seg_f64_kernel<CAND, HI, NRK4>), dim3((B + S - 1) / S), dim3(SEG_THREADS), lds, st, P, B, W, S, A.x0, A.u_prev,
-                               A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.ck_records, A.cost_out, A.argmin_out,
-                               A.status_out, A.x_out, A.u_out);
-        else
-            hipLaunchKernelGGL((emit_seg_f64_kernel<CAND, HI, 0>), dim3((B + S - 1) / S), dim3(SEG_THREADS), lds, st, P, B, W, S, A.x0, A.u_prev,
-                               A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.ck_records, A.cost_out, A.argmin_out,
-                               A.status_out, A.x_out, A.u_out);
-        return hipGetLastError();
+        hipLaunchKernelGGL((emit_seg_f64_kernel<CAND, HI, NRK>), dim3((B + S - 1) / S), dim3(SEG_THREADS), lds, st, P, B, W, S, A.x0,
+                           A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.ck_records,
+                           A.cost_out, A.argmin_out, A.status_out, A.x_out, A.u_out);
+    } else {
+        hipLaunchKernelGGL((emit_f64_kernel<CAND, HI, NRK>), dim3((B + 63) / 64), dim3(64), 0, st, P, B, W, A.x0, A.u_prev, A.kparams,
+                           A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.cost_out, A.argmin_out, A.status_out,
+                           A.x_out, A.u_out);
     }
-    if (NRK4 == 4 && P.n_rk4 == 4)
-        hipLaunchKernelGGL((emit_f64_kernel<CAND, HI, NRK4>), dim3((B + 63) / 64), dim3(64), 0, st, P, B, W, A.x0, A.u_prev, A.kparams,
-                           A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.cost_out, A.argmin_out, A.status_out,
-                           A.x_out, A.u_out);
-    else
-        hipLaunchKernelGGL((emit_f64_kernel<CAND, HI, 0>), dim3((B + 63) / 64), dim3(64), 0, st, P, B, W, A.x0, A.u_prev, A.kparams,
-                           A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.cost_out, A.argmin_out, A.status_out,
-                           A.x_out, A.u_out);
     return hipGetLastError();
 }
 // dynamic LDS above 64 KB has to be asked for, per kernel and device: once per handle at igt_create -- not on the launch path,
-// which must stay a pure sequence of stream operations (stream capture)
-template <int CAND>
-static hipError_t seg_opt_in_family() {
-    hipError_t e = seg_lds_opt_in(emit_seg_f64_kernel<CAND, false, 4>);
-    if (e == hipSuccess) e = seg_lds_opt_in(emit_seg_f64_kernel<CAND, false, 0>);
-    if (e == hipSuccess) e = seg_lds_opt_in(emit_seg_f64_kernel<CAND, true, 0>);
-    return e;
-}
+// which must stay a pure sequence of stream operations (stream capture).  The emit in pieces and the polish kernel: every build
+// the launchers can reach, from the lists they dispatch on.
 hipError_t prepare_emit_kernels() {
-    hipError_t e = seg_opt_in_family<CAND_LATTICE>();
-    if (e == hipSuccess) e = seg_opt_in_family<CAND_TABLE>();
-    if (e == hipSuccess) e = seg_opt_in_family<CAND_RAMP_HOLD>();
-    if (e == hipSuccess) e = seg_opt_in_family<CAND_TRACK>();
-    if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<false, 4>);
-    if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<false, 0>);
-    if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<true, 0>);
-    if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<false, 4, true>);
-    if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<false, 0, true>);
-    if (e == hipSuccess) e = seg_lds_opt_in(polish_f64_kernel<true, 0, true>);
-    if (e == hipSuccess) e = seg_lds_opt_in(cost_gradient_f64_kernel<TERM_PROGRESS>);
-    if (e == hipSuccess) e = seg_lds_opt_in(cost_gradient_f64_kernel<TERM_LEAVE>);
-    if (e == hipSuccess) e = seg_lds_opt_in(cost_gradient_f64_kernel<TERM_VALUE>);
+    hipError_t e = hipSuccess;
+    const auto opt_in = [&](auto kernel) { if (e == hipSuccess) e = seg_lds_opt_in(kernel); };
+    for_each_discretisation([&](auto hi, auto nrk) {
+        for_each_family([&](auto cand) { opt_in(emit_seg_f64_kernel<cand(), hi(), nrk()>); });
+        opt_in(polish_f64_kernel<hi(), nrk(), false>);
+        opt_in(polish_f64_kernel<hi(), nrk(), true>);
+    });
+    opt_in(cost_gradient_f64_kernel<TERM_PROGRESS>);
+    opt_in(cost_gradient_f64_kernel<TERM_LEAVE>);
+    opt_in(cost_gradient_f64_kernel<TERM_VALUE>);
     return e;
 }
 
@@ -1353,16 +1306,7 @@ hipError_t launch_emit<double>(const KP& P, int B, int W, const SolveArgs<double
         return hipGetLastError();
     }
 #endif
-    if (P.hi_order) {
-        if (P.cand_mode == CAND_LATTICE) return launch_emit64<CAND_LATTICE, true>(P, B, W, A, st);
-        if (P.cand_mode == CAND_RAMP_HOLD) return launch_emit64<CAND_RAMP_HOLD, true>(P, B, W, A, st);
-        if (P.cand_mode == CAND_TRACK) return launch_emit64<CAND_TRACK, true>(P, B, W, A, st);
-        return launch_emit64<CAND_TABLE, true>(P, B, W, A, st);
-    }
-    if (P.cand_mode == CAND_LATTICE) return launch_emit64<CAND_LATTICE, false>(P, B, W, A, st);
-    if (P.cand_mode == CAND_RAMP_HOLD) return launch_emit64<CAND_RAMP_HOLD, false>(P, B, W, A, st);
-    if (P.cand_mode == CAND_TRACK) return launch_emit64<CAND_TRACK, false>(P, B, W, A, st);
-    return launch_emit64<CAND_TABLE, false>(P, B, W, A, st);
+    return with_build(P, [&](auto cand, auto hi, auto nrk) { return launch_emit64<cand(), hi(), nrk()>(P, B, W, A, st); });
 }
 
 // polish_iters > 0: after emit, on the same stream (igt_api.hip solve_impl).  The kernel's LDS passes 64 KB from N = 63 on: it is
@@ -1371,18 +1315,13 @@ hipError_t launch_emit<double>(const KP& P, int B, int W, const SolveArgs<double
 hipError_t launch_polish(const KP& P, int B, int iters, bool adjoint, const SolveArgs<double>& A, hipStream_t st) {
     if (P.dev & (DEV_EXACT64 | DEV_LITERAL)) return hipErrorNotSupported;      // the oracle-order developer kernels
     const size_t lds = polish_lds_doubles(P.N) * 8;
-#define IGT_LAUNCH_POLISH(HI_, NRK_, ADJ_)                                                                                    \
-    hipLaunchKernelGGL((polish_f64_kernel<HI_, NRK_, ADJ_>), dim3(B), dim3(64), lds, st, P, B, iters, A.x0, A.u_prev, A.kparams, A.flags, \
-                       A.obs, A.cinf, A.status_out, A.cost_out, A.x_out, A.u_out)
-    if (adjoint) {
-        if (P.hi_order) IGT_LAUNCH_POLISH(true, 0, true);
-        else if (P.n_rk4 == 4) IGT_LAUNCH_POLISH(false, 4, true);
-        else IGT_LAUNCH_POLISH(false, 0, true);
-    } else if (P.hi_order) IGT_LAUNCH_POLISH(true, 0, false);
-    else if (P.n_rk4 == 4) IGT_LAUNCH_POLISH(false, 4, false);
-    else IGT_LAUNCH_POLISH(false, 0, false);
-#undef IGT_LAUNCH_POLISH
-    return hipGetLastError();
+    return with_discretisation(P.hi_order, P.n_rk4, [&](auto hi, auto nrk) {
+        return with_bool(adjoint, [&](auto adj) {
+            hipLaunchKernelGGL((polish_f64_kernel<hi(), nrk(), adj()>), dim3(B), dim3(64), lds, st, P, B, iters, A.x0, A.u_prev,
+                               A.kparams, A.flags, A.obs, A.cinf, A.status_out, A.cost_out, A.x_out, A.u_out);
+            return hipGetLastError();
+        });
+    });
 }
 
 // igt_cost_gradient_f64: one wave per 64 scenarios; the LDS passes 64 KB from N = 41 on (asked for in prepare_emit_kernels)
@@ -1402,14 +1341,6 @@ hipError_t launch_cost_gradient_vn(const KP& P, int B, bool leave, const double*
     return hipGetLastError();
 }
 
-template <int CAND, bool HI>
-static hipError_t launch_rollout_all64(const KP& P, int B, const SolveArgs<double>& A, double* X_all, double* U_all,
-                                       double* cost_all, uint32_t* viol_all, hipStream_t st) {
-    hipLaunchKernelGGL((rollout_all_f64_kernel<CAND, HI>), dim3((B + 3) / 4), dim3(256), 0, st, P, B, A.x0, A.u_prev,
-                       A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), X_all, U_all, cost_all, viol_all, A.rec_sN, A.rec_vN,
-                       A.rec_J, A.rec_viol);
-    return hipGetLastError();
-}
 template <>
 hipError_t launch_rollout_all<double>(const KP& P, int B, const SolveArgs<double>& A, double* X_all, double* U_all,
                                       double* cost_all, uint32_t* viol_all, hipStream_t st) {
@@ -1421,16 +1352,12 @@ hipError_t launch_rollout_all<double>(const KP& P, int B, const SolveArgs<double
         return hipGetLastError();
     }
 #endif
-    if (P.hi_order) {
-        if (P.cand_mode == CAND_LATTICE) return launch_rollout_all64<CAND_LATTICE, true>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-        if (P.cand_mode == CAND_RAMP_HOLD) return launch_rollout_all64<CAND_RAMP_HOLD, true>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-        if (P.cand_mode == CAND_TRACK) return launch_rollout_all64<CAND_TRACK, true>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-        return launch_rollout_all64<CAND_TABLE, true>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-    }
-    if (P.cand_mode == CAND_LATTICE) return launch_rollout_all64<CAND_LATTICE, false>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-    if (P.cand_mode == CAND_RAMP_HOLD) return launch_rollout_all64<CAND_RAMP_HOLD, false>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-    if (P.cand_mode == CAND_TRACK) return launch_rollout_all64<CAND_TRACK, false>(P, B, A, X_all, U_all, cost_all, viol_all, st);
-    return launch_rollout_all64<CAND_TABLE, false>(P, B, A, X_all, U_all, cost_all, viol_all, st);
+    return with_family(P.cand_mode, P.hi_order, [&](auto cand, auto hi) {
+        hipLaunchKernelGGL((rollout_all_f64_kernel<cand(), hi()>), dim3((B + 3) / 4), dim3(256), 0, st, P, B, A.x0, A.u_prev,
+                           A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), X_all, U_all, cost_all, viol_all, A.rec_sN, A.rec_vN,
+                           A.rec_J, A.rec_viol);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace igt

@@ -39,15 +39,15 @@ def _npdt(dtype):
 
 
 def make_case(key, dtype, args, *, N=20, dt=0.1, n_rk4=4, C=256, n_obs=1, cand='lattice', refine=0, limits=None, net=None,
-              cinf=None, eps, tie, tol, utol=1e-7, ctol=None, use_bp=True, first=False, crossing=0, need=0):
+              cinf=None, eps, tie, tol, utol=1e-7, ctol=None, use_bp=True, first=False, crossing=0, need=0, table=None):
     """args: dict(x0, u_prev, kparams, flags, obs[, u_ws, tv_sv, enc]) in the device's dtype.  first: the first pass alone is
     compared as well (key + '/first').  crossing: compared winners that must cross a break-point.  need: the least the recorded
-    min_solved may be."""
+    min_solved may be.  table: the controls [C, 2, N] of cand = 'table'."""
     limits = dict(limits or {})
     return dict(key=key, dtype=dtype, args=args, B=len(args['flags']), N=N, dt=dt, n_rk4=n_rk4, C=C, n_obs=n_obs, cand=cand,
                 refine=refine, limits=limits, net=net, cinf=cinf, P=host_params(N=N, dt=dt, n_rk4=n_rk4, **limits),
                 tk=host_track(**limits), eps=eps, tie=tie, tol=tol, utol=utol, ctol=ctol, use_bp=use_bp, first=first,
-                crossing=crossing, need=need)
+                crossing=crossing, need=need, table=table)
 
 
 def subcase(case, refine, suffix):
@@ -62,8 +62,9 @@ def oracle_passes(case):
     A, b = case['cinf'] if case['cinf'] is not None else (None, None)
     kw = dict(net=case['net'], tv_sv=f('tv_sv'), enc=f('enc')) if case['net'] else {}
     obs = f('obs') if case['n_obs'] else None
-    if case['cand'] == 'lattice':
-        passes = [O.solve_batch(f('x0'), f('u_prev'), f('kparams'), a['flags'], obs, A, b, case['P'], C=case['C'],
+    if case['cand'] in ('lattice', 'table'):
+        U = None if case['cand'] == 'lattice' else np.broadcast_to(case['table'], (case['B'],) + case['table'].shape)
+        passes = [O.solve_batch(f('x0'), f('u_prev'), f('kparams'), a['flags'], obs, A, b, case['P'], C=case['C'], U=U,
                                 return_all=True, **kw)]
     else:
         passes = O.solve_batch_refined(f('x0'), f('u_prev'), f('kparams'), a['flags'], obs, A, b, case['P'], C=case['C'],
@@ -102,6 +103,8 @@ def open_solver(igt, case, refine=None, **kw):
             s.set_cinf(*case['cinf'])
         if case['net']:
             s.set_value_net(**case['net'])
+        if case['table'] is not None:
+            s.set_candidate_table(case['table'])
     except BaseException:
         s.close()
         raise
@@ -637,6 +640,43 @@ def limits_case(seed, dtype):
                      ctol=2e-5 if f32 and net else None)
 
 
+# ----------------------------------------------------------------------------- test_gpu_dispatch_leaves.py
+LEAF_FAMILIES = ('lattice', 'table', 'ramp_hold', 'track')
+LEAF_N_RK4 = (4, 3, 2, 7)
+LEAF_SEED = 0
+
+
+HI_ORDER_RULE = 'k.hi_order = (k.h * vhi * (0.7 / p.l_r + 0.25) > 0.12) ? 1 : 0;'       # csrc/igt_api.hip, with the line before it:
+HI_ORDER_VHI = 'const double vhi = std::fmax(std::fabs(p.v_min), std::fabs(p.v_max)) + 2.0;'
+
+
+def leaf_hi_order(P):
+    """KP::hi_order for the parameters P (np_oracle.Params; the GPU tests hold them equal to the solver's): a restatement of
+    the two statements above, which tests/test_host_logic.py holds to the text of csrc/igt_api.hip."""
+    vhi = max(abs(P.v_min), abs(P.v_max)) + 2.0
+    return (P.dt / P.n_rk4) * vhi * (0.7 / P.l_r + 0.25) > 0.12
+
+
+def leaf_case(dtype, cand, n_rk4):
+    """The smallest solve that selects one leaf of the launchers' dispatch (csrc/igt_dispatch.h): 5 scenarios (no multiple of
+    rollout-all's 4 per workgroup), one 64-candidate unit each, 8 steps of dt = 0.1, one obstacle.  n_rk4 = 4 is the build
+    of the reference's discretisation; 3 and 2 run the long polynomials (h = dt / n_rk4 > 0.0304 at the default limits: leaf_hi_order); 7 the
+    short polynomials with the sub-steps counted at run time.  The table family: scenario 0's lattice as everyone's table,
+    and its previous controls as everyone's (a table's controls are held to the rate limits from u_prev)."""
+    from igtmpc.scenarios import make_batch
+    B, N, C, npdt = 5, 8, 64, _npdt(dtype)
+    b = make_batch(8, N=N, dt=0.1, seed=LEAF_SEED, dtype=npdt)
+    b = {k: np.ascontiguousarray(v[:B]) for k, v in b.items() if isinstance(v, np.ndarray) and len(v) >= B}
+    table = None
+    if cand == 'table':
+        b['u_prev'] = np.ascontiguousarray(np.broadcast_to(b['u_prev'][:1], b['u_prev'].shape))
+        table = np.ascontiguousarray(O.candidates_lattice(b['u_prev'][:1].astype(np.float64), O.Params(N=N, dt=0.1), C)[0])
+    tol, eps, tie = _bars(dtype, F32_EPS, F32_TIE)
+    return make_case(f'leaf[{dtype}-{cand}-{n_rk4}]', dtype, _batch_args(b), N=N, n_rk4=n_rk4, C=C, cand=cand, table=table,
+                     cinf=cinf_default(), eps=eps, tie=tie, tol=tol, utol=1e-7 if cand != 'track' or dtype == 'f64' else REL_TOL,
+                     need=B // 2)
+
+
 # ----------------------------------------------------------------------------- every comparison
 def all_cases():
     """Yields (key, builder): every case the GPU tests compare through check_case, built lazily."""
@@ -660,6 +700,10 @@ def all_cases():
         yield f'{spec[0]}[{spec[3]}' + (f'-sc{spec[4]}]' if spec[4] else ']'), lambda s=spec: fullsize_case(*s)[0]
     for q in range(OVERLAP_MAX_F):
         yield overlap_key(q), lambda q=q: overlap_case(q)[0]
+    for dtype in ('f64', 'f32'):
+        for cand in LEAF_FAMILIES:
+            for n_rk4 in LEAF_N_RK4:
+                yield f'leaf[{dtype}-{cand}-{n_rk4}]', lambda d=dtype, c=cand, n=n_rk4: leaf_case(d, c, n)
     for seeds, dtype in ((range(FUZZ_N_SEEDS), 'f64'), (FUZZ_F32_SEEDS, 'f32'), (FUZZ_EXT_SEEDS, 'f64'), (FUZZ_EXT_F32_SEEDS, 'f32')):
         for seed in seeds:
             yield f'fuzz[{seed}-{dtype}]', lambda s=seed, d=dtype: fuzz_case(s, d)

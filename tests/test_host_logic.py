@@ -358,6 +358,37 @@ def test_public_header_is_plain_c(tmp_path):
     assert re.findall(r'#include\s*[<"]([^>"]+)', hdr) == ['stdint.h']          # nothing but <stdint.h> is pulled in
 
 
+def test_dispatch_helper_reaches_each_leaf_once(tmp_path):
+    """csrc/igt_dispatch.h turns (cand_mode, hi_order, n_rk4) into the template arguments of every launcher.  It is plain
+    C++17, so a host compiler builds tests/dispatch_leaves.cpp against it alone, under the address and undefined-behaviour
+    sanitizers: one callback per call with the expected constants, unknown families are tables, (HI, 4) does not exist (a
+    static_assert in the program: it would not compile), for_each_* visit 4 and 3 leaves."""
+    import shutil
+    import subprocess
+    if not shutil.which('g++'):
+        pytest.skip('no g++')
+    exe = tmp_path / 'dispatch_leaves'
+    r = subprocess.run(['g++', '-std=c++17', '-Wall', '-Wextra', '-Werror', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                        '-I', os.path.join(ROOT, 'igt-mpc-int_amd', 'csrc'), os.path.join(ROOT, 'tests', 'dispatch_leaves.cpp'),
+                        '-o', str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == 'dispatch leaves ok', r.stdout + r.stderr
+    hdr = open(os.path.join(ROOT, 'igt-mpc-int_amd', 'csrc', 'igt_dispatch.h')).read()
+    assert re.findall(r'#include\s*[<"]([^>"]+)', hdr) == ['type_traits']      # no HIP header behind it
+
+
+def test_leaf_cases_restate_the_hi_order_rule():
+    """tests/test_gpu_dispatch_leaves.py picks n_rk4 values by KP::hi_order, which the library does not report:
+    parity_cases.leaf_hi_order restates the rule, and the statements it restates must be the ones in csrc/igt_api.hip."""
+    import parity_cases as PC
+    src = ' '.join(open(os.path.join(ROOT, 'igt-mpc-int_amd', 'csrc', 'igt_api.hip')).read().split())
+    assert PC.HI_ORDER_VHI + ' ' + PC.HI_ORDER_RULE in src
+    assert 'k.h = p.dt / p.n_rk4;' in src or 'k.h = p.dt / (double)p.n_rk4;' in src
+    P = lambda n: PC.leaf_case('f64', 'lattice', n)['P']
+    assert [bool(PC.leaf_hi_order(P(n))) for n in PC.LEAF_N_RK4] == [False, True, True, False]
+
+
 def _build_c_caller(out):
     import shutil
     import subprocess
