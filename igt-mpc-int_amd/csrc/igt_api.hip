@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "igt_launch.h"
+#include "igt_stage.h"
 #include "igtmpc.h"
 
 namespace {
@@ -37,36 +38,36 @@ int fail(int code, const std::string& msg) {
 struct igt_handle {
     igt_params p;
     igt::KP kp;
-    int device;
-    hipStream_t stream;
-    double* d_cinf;
-    double* d_table;
-    bool table_set;
-    bool net_set;
-    void* d_stage;
-    size_t stage_bytes;
-    void* h_stage;         // pinned mirror of the first PACK_BYTES of d_stage (small host-mode solves: one copy each way)
-    void* d_work;          // workspace: per-slice partial arg-min, value-net records
-    size_t work_bytes;
-    double* d_routes;      // [n_routes, 12] route geometry for the forecast kernel
-    int n_routes;
-    void* d_net;           // value-net parameters (float block followed by double block)
+    int device = 0;
+    hipStream_t stream = nullptr;
+    double* d_cinf = nullptr;
+    double* d_table = nullptr;
+    bool table_set = false;
+    bool net_set = false;
+    void* d_stage = nullptr;       // staging arena of the host-mode calls, laid out per call by a StagePlan (Staging below)
+    size_t stage_bytes = 0;
+    void* h_stage = nullptr;       // pinned mirror of the arena's first PACK_BYTES, allocated once (packed calls: one copy each way)
+    void* d_work = nullptr;        // workspace: per-slice partial arg-min, value-net records
+    size_t work_bytes = 0;
+    double* d_routes = nullptr;    // [n_routes, 12] route geometry for the forecast kernel
+    int n_routes = 0;
+    void* d_net = nullptr;         // value-net parameters (float block followed by double block)
     igt::DevNet<float> net_f;
     igt::DevNet<double> net_d;
-    bool prof;
+    bool prof = false;
     hipEvent_t ev[3];
-    bool ev_recorded;
-    int nc;
-    int n_cu;              // compute units of the device (sizes the persistent search grid)
-    int concurrency;       // solves the caller keeps in flight on the device (igt_set_concurrency)
-    int polish_grad;       // IGT_GRAD_FORWARD_DIFF / IGT_GRAD_ADJOINT (igt_set_polish_gradient)
-    void* comm;            // RCCL communicator of igt_comm_init (null: none)
-    int comm_world, comm_rank;
-    int32_t comm_B_local;  // shard size of the communicator's first all-gather (0 = none yet); later calls must match
-    void* d_u0;            // [B_local,2] first-step controls staged for the all-gather
-    size_t u0_bytes;
-    int dev_ckpt;          // IGT_DEV_CKPT / IGT_DEV_TRAJ_MAX (threshold sweeps), read once at igt_create; -1: not set
-    int dev_traj_max;
+    bool ev_recorded = false;
+    int nc = 2;
+    int n_cu = 256;                // compute units of the device (sizes the persistent search grid)
+    int concurrency = 1;           // solves the caller keeps in flight on the device (igt_set_concurrency)
+    int polish_grad = IGT_GRAD_FORWARD_DIFF;      // or IGT_GRAD_ADJOINT (igt_set_polish_gradient)
+    void* comm = nullptr;          // RCCL communicator of igt_comm_init (null: none)
+    int comm_world = 1, comm_rank = 0;
+    int32_t comm_B_local = 0;      // shard size of the communicator's first all-gather (0 = none yet); later calls must match
+    void* d_u0 = nullptr;          // [B_local,2] first-step controls staged for the all-gather
+    size_t u0_bytes = 0;
+    int dev_ckpt = -1;             // IGT_DEV_CKPT / IGT_DEV_TRAJ_MAX (threshold sweeps), read once at igt_create; -1: not set
+    int dev_traj_max = -1;
 };
 
 namespace {
@@ -207,14 +208,8 @@ igt::KP make_kp(const igt_params& p, int F) {
     return k;
 }
 
-// A host-mode solve of a few scenarios is a dozen sub-kilobyte copies around ~120 us of kernels, and every pageable
-// hipMemcpyAsync costs ~7 us whatever its size.  Up to PACK_BYTES the inputs are gathered into a pinned mirror of the
-// staging arena and cross the bus in ONE copy, the outputs come back in one; beyond that the copies go directly (a second
-// pass over megabytes on the host would cost more than the calls).
-constexpr size_t PACK_BYTES = 256 * 1024;
-
 int ensure_stage(igt_handle* h, size_t bytes) {
-    if (!h->h_stage) HIPCHK(hipHostMalloc(&h->h_stage, PACK_BYTES, hipHostMallocDefault));
+    if (!h->h_stage) HIPCHK(hipHostMalloc(&h->h_stage, igt::PACK_BYTES, hipHostMallocDefault));
     if (bytes <= h->stage_bytes) return 0;
     if (h->d_stage) { HIPCHK(hipFree(h->d_stage)); h->d_stage = nullptr; h->stage_bytes = 0; }
     const size_t want = bytes + bytes / 4 + 4096;
@@ -246,9 +241,94 @@ template <typename T> const igt::DevNet<T>& net_of(const igt_handle* h);
 template <> const igt::DevNet<float>& net_of<float>(const igt_handle* h) { return h->net_f; }
 template <> const igt::DevNet<double>& net_of<double>(const igt_handle* h) { return h->net_d; }
 
-// Carves 256-byte aligned pieces out of a device buffer.  Every buffer is laid out by one carve function per entry point, run
-// twice: first on an arena with no base, which only adds up the bytes (arena_bytes; the pointers it hands out are offsets and
-// are never used), then -- once ensure_stage / ensure_work has made the buffer that large -- on the buffer itself.
+// The buffers of one call that takes mem = IGT_MEM_HOST | IGT_MEM_DEVICE ("How an entry stages host
+// buffers").  An entry declares each buffer once -- in(&device pointer, caller's array, elements[, copied]) or out(...) --,
+// then upload(), its launches, download().  IGT_MEM_DEVICE: every pointer is handed back as it came and nothing is allocated,
+// copied or synchronised, so such a call can be captured into a graph.  IGT_MEM_HOST: upload() lays the buffers out in
+// h->d_stage (igt_stage.h StagePlan), points the device pointers there and copies the inputs; download() copies the outputs
+// back and synchronises once.  With `pack` (the solve entries) a call of at most igt::PACK_BYTES crosses in one copy each way,
+// through the pinned mirror.  A null array that would be copied is an absent optional buffer: its device pointer stays null.
+class Staging {
+public:
+    Staging(igt_handle* h, int mem, void* stream, bool pack = false)
+        : h_(h), mem_(mem), st_(stream ? (hipStream_t)stream : h->stream), pack_(pack) {}
+    hipStream_t stream() const { return st_; }
+    // The one `mem` check.  upload() makes it for every entry; terminal_value and cost_gradient_vn also call it themselves
+    // ahead of their empty-batch return, because they refuse a bad `mem` even for n == 0 -- neither call is redundant.
+    int check_mem() const {
+        if (mem_ == IGT_MEM_DEVICE || mem_ == IGT_MEM_HOST) return IGT_OK;
+        return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
+    }
+    template <typename U> void in(const U** dev, const U* host, size_t n, bool copy = true) {
+        *dev = host;
+        if (mem_ == IGT_MEM_HOST) add(dev, plan_.add(host, n * sizeof(U), sizeof(U), false, copy));
+    }
+    template <typename U> void out(U** dev, U* host, size_t n) {
+        *dev = host;
+        if (mem_ == IGT_MEM_HOST) add(dev, plan_.add(host, n * sizeof(U), sizeof(U), true));
+    }
+    // selects the device, refuses a bad `mem` (check_mem: here for the seven entries that answer an empty batch first), and
+    // in host mode stages the inputs
+    int upload() {
+        HIPCHK(hipSetDevice(h_->device));
+        if (int rc = check_mem()) return rc;
+        if (mem_ == IGT_MEM_DEVICE) return IGT_OK;
+        if (plan_.overflow) return fail(IGT_E_STATE, "more staged buffers than igt_stage.h STAGE_MAX_BUFFERS");
+        plan_.layout();
+        if (int rc = ensure_stage(h_, plan_.total)) return rc;
+        char* base = static_cast<char*>(h_->d_stage);
+        for (int i = 0; i < plan_.n; ++i) slot_[i].point(slot_[i].var, base + plan_.buf[i].off);
+        packed_ = pack_ && plan_.packed();
+        if (packed_) {
+            plan_.gather(h_->h_stage);
+            HIPCHK(hipMemcpyAsync(base, h_->h_stage, plan_.in_span, hipMemcpyHostToDevice, st_));
+            return IGT_OK;
+        }
+        for (int i = 0; i < plan_.n; ++i) {
+            const igt::StagePlan::Buf& b = plan_.buf[i];
+            if (!b.out && b.copy) HIPCHK(hipMemcpyAsync(base + b.off, b.host, b.bytes, hipMemcpyHostToDevice, st_));
+        }
+        return IGT_OK;
+    }
+    int download() {
+        if (mem_ != IGT_MEM_HOST) return IGT_OK;
+        const char* base = static_cast<const char*>(h_->d_stage);
+        if (packed_) {
+            char* hs = static_cast<char*>(h_->h_stage);
+            HIPCHK(hipMemcpyAsync(hs + plan_.out_begin, base + plan_.out_begin, plan_.total - plan_.out_begin,
+                                  hipMemcpyDeviceToHost, st_));
+            HIPCHK(hipStreamSynchronize(st_));
+            plan_.scatter(hs);
+            return IGT_OK;
+        }
+        for (int i = 0; i < plan_.n; ++i) {
+            const igt::StagePlan::Buf& b = plan_.buf[i];
+            if (b.out && b.copy) HIPCHK(hipMemcpyAsync(b.host, base + b.off, b.bytes, hipMemcpyDeviceToHost, st_));
+        }
+        HIPCHK(hipStreamSynchronize(st_));
+        return IGT_OK;
+    }
+
+private:
+    // remembers where buffer i's device pointer lives (P = const U* or U*), with the typed assignment that re-points it
+    template <typename P> void add(P* dev, int i) {
+        if (i >= 0) slot_[i] = Slot{dev, [](void* var, void* p) { *static_cast<P*>(var) = static_cast<P>(p); }};
+    }
+    struct Slot {
+        void* var;
+        void (*point)(void* var, void* p);
+    };
+    igt_handle* h_;
+    int mem_;
+    hipStream_t st_;
+    bool pack_, packed_ = false;
+    igt::StagePlan plan_;
+    Slot slot_[igt::STAGE_MAX_BUFFERS];      // each buffer's device pointer, in the entry's frame
+};
+
+// Carves 256-byte aligned pieces out of the workspace.  A call's share is laid out by one carve function, run twice
+// (carve_work): first on an arena with no base, which only adds up the bytes (the pointers it hands out are offsets and are
+// never used), then -- once ensure_work has made the workspace that large -- on the workspace itself.
 struct Arena {
     char* base;
     size_t off;
@@ -259,10 +339,13 @@ struct Arena {
         return p;
     }
 };
-template <class Carve> size_t arena_bytes(const Carve& carve) {
+template <class Carve> int carve_work(igt_handle* h, hipStream_t st, const Carve& carve) {
     Arena sizing{nullptr, 0};
     carve(sizing);
-    return sizing.off;
+    if (int rc = ensure_work(h, sizing.off, st)) return rc;
+    Arena wa{(char*)h->d_work, 0};
+    carve(wa);
+    return IGT_OK;
 }
 
 // The argument checks solve and rollout-all share (each entry point checks its own outputs).  B == 0: IGT_OK with *empty set,
@@ -306,71 +389,22 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     if (p.polish_iters > 0 && (h->kp.dev & (igt::DEV_EXACT64 | igt::DEV_LITERAL)))
         return fail(IGT_E_INVALID, "polish_iters > 0 is not available with the developer kernels of IGT_DEV_FLAGS 1024 / 2048");
     const bool value = p.cost_mode == IGT_COST_VALUE_NET;
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const size_t n_x = (size_t)B * 7, n_u = (size_t)B * 2, n_k = (size_t)B * 3;
     const size_t n_obs = (size_t)B * p.n_obs * 2 * (p.N + 1);
     const size_t n_xo = (size_t)B * 7 * (p.N + 1), n_uo = (size_t)B * 2 * p.N;
 
     igt::SolveArgs<T> A{};
-    bool packed = false;                 // host mode, small: one copy each way through the pinned mirror (ensure_stage)
-    size_t out_begin = 0, out_end = 0;
     A.table = h->table_set ? h->d_table : nullptr;
     A.cinf = h->kp.F > 0 ? h->d_cinf : nullptr;
-    if (mem == IGT_MEM_DEVICE) {
-        A.x0 = x0; A.u_prev = u_prev; A.kparams = kparams; A.flags = flags; A.obs = obs_xy;
-        A.tv_sv = tv_sv; A.enc = enc; A.u_ws = u_ws;
-        A.x_out = x_out; A.u_out = u_out; A.cost_out = cost_out; A.argmin_out = argmin_out; A.status_out = status_out;
-    } else if (mem == IGT_MEM_HOST) {
-        T *dx0, *dup, *dk, *dob, *dtv, *den, *dws, *dxo, *duo, *dco;
-        uint32_t* dfl;
-        int32_t *dam, *dst;
-        size_t in_span = 0;
-        const auto carve = [&](Arena& ar) {      // inputs first, outputs behind them: each group is one contiguous span
-            dx0 = ar.take<T>(n_x); dup = ar.take<T>(n_u); dk = ar.take<T>(n_k);
-            dfl = ar.take<uint32_t>(B); dob = ar.take<T>(n_obs ? n_obs : 1);
-            dtv = ar.take<T>(n_u); den = ar.take<T>(n_u);
-            dws = u_ws ? ar.take<T>(n_uo) : nullptr;
-            in_span = ar.off;
-            dxo = ar.take<T>(n_xo); duo = ar.take<T>(n_uo); dco = ar.take<T>(B);
-            dam = ar.take<int32_t>(B); dst = ar.take<int32_t>(B);
-        };
-        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
-        Arena ar{(char*)h->d_stage, 0};
-        carve(ar);
-        out_begin = (size_t)((char*)dxo - (char*)h->d_stage);
-        out_end = ar.off;
-        packed = out_end <= PACK_BYTES;
-        if (packed) {
-            char* hs = (char*)h->h_stage;
-            auto put = [&](const void* src, const void* d, size_t nbytes) {
-                std::memcpy(hs + ((const char*)d - (const char*)h->d_stage), src, nbytes);
-            };
-            put(x0, dx0, n_x * sizeof(T)); put(u_prev, dup, n_u * sizeof(T)); put(kparams, dk, n_k * sizeof(T));
-            put(flags, dfl, (size_t)B * 4);
-            if (n_obs) put(obs_xy, dob, n_obs * sizeof(T));
-            if (value) { put(tv_sv, dtv, n_u * sizeof(T)); put(enc, den, n_u * sizeof(T)); }
-            if (u_ws) put(u_ws, dws, n_uo * sizeof(T));
-            HIPCHK(hipMemcpyAsync(h->d_stage, hs, in_span, hipMemcpyHostToDevice, st));
-        } else {
-            if (value) {
-                HIPCHK(hipMemcpyAsync(dtv, tv_sv, n_u * sizeof(T), hipMemcpyHostToDevice, st));
-                HIPCHK(hipMemcpyAsync(den, enc, n_u * sizeof(T), hipMemcpyHostToDevice, st));
-            }
-            if (u_ws) HIPCHK(hipMemcpyAsync(dws, u_ws, n_uo * sizeof(T), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(dx0, x0, n_x * sizeof(T), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(dup, u_prev, n_u * sizeof(T), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(dk, kparams, n_k * sizeof(T), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(dfl, flags, (size_t)B * 4, hipMemcpyHostToDevice, st));
-            if (n_obs) HIPCHK(hipMemcpyAsync(dob, obs_xy, n_obs * sizeof(T), hipMemcpyHostToDevice, st));
-        }
-        A.tv_sv = dtv; A.enc = den;
-        if (u_ws) A.u_ws = dws;
-        A.x0 = dx0; A.u_prev = dup; A.kparams = dk; A.flags = dfl; A.obs = dob;
-        A.x_out = dxo; A.u_out = duo; A.cost_out = dco; A.argmin_out = dam; A.status_out = dst;
-    } else {
-        return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
-    }
+    Staging stg(h, mem, stream, /*pack=*/true);
+    stg.in(&A.x0, x0, n_x); stg.in(&A.u_prev, u_prev, n_u); stg.in(&A.kparams, kparams, n_k);
+    stg.in(&A.flags, flags, (size_t)B); stg.in(&A.obs, obs_xy, n_obs);
+    stg.in(&A.tv_sv, tv_sv, n_u, value); stg.in(&A.enc, enc, n_u, value);
+    stg.in(&A.u_ws, u_ws, n_uo);
+    stg.out(&A.x_out, x_out, n_xo); stg.out(&A.u_out, u_out, n_uo); stg.out(&A.cost_out, cost_out, (size_t)B);
+    stg.out(&A.argmin_out, argmin_out, (size_t)B); stg.out(&A.status_out, status_out, (size_t)B);
+    if (int rc = stg.upload()) return rc;
+    hipStream_t st = stg.stream();
 
     // workspace (grows on first use, never shrinks): per-slice partial arg-min [+ value-net records]
     // per-scenario partials: float value path reduces to ONE per scenario (compact list + atomicMin),
@@ -438,9 +472,7 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
             }
         }
     };
-    if (int rc = ensure_work(h, arena_bytes(carve), st)) return rc;
-    Arena wa{(char*)h->d_work, 0};
-    carve(wa);
+    if (int rc = carve_work(h, st, carve)) return rc;
     A.n_cu = h->n_cu;
     A.waves_per_simd = h->concurrency >= 3 ? 1 : 2;      // two solves in flight do not overlap on this runtime (igtmpc.h)
     A.ck_parts = ck_parts;
@@ -493,24 +525,7 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
             if (FILE* f = std::fopen(path, "wb")) { std::fwrite(tr.data(), 8, n, f); std::fclose(f); }
         }
     }
-    if (mem == IGT_MEM_HOST && packed) {
-        char* hs = (char*)h->h_stage;
-        HIPCHK(hipMemcpyAsync(hs + out_begin, (char*)h->d_stage + out_begin, out_end - out_begin, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        auto get = [&](void* dst_, const void* d, size_t nbytes) {
-            std::memcpy(dst_, hs + ((const char*)d - (const char*)h->d_stage), nbytes);
-        };
-        get(x_out, A.x_out, n_xo * sizeof(T)); get(u_out, A.u_out, n_uo * sizeof(T)); get(cost_out, A.cost_out, (size_t)B * sizeof(T));
-        get(argmin_out, A.argmin_out, (size_t)B * 4); get(status_out, A.status_out, (size_t)B * 4);
-    } else if (mem == IGT_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(x_out, A.x_out, n_xo * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(u_out, A.u_out, n_uo * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(cost_out, A.cost_out, (size_t)B * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(argmin_out, A.argmin_out, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(status_out, A.status_out, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return IGT_OK;
+    return stg.download();
 }
 
 template <typename T>
@@ -523,53 +538,23 @@ int rollout_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T
     if (!cost_all || !viol_all) return fail(IGT_E_INVALID, "null buffer");
     const igt_params& p = h->p;
     const bool value = p.cost_mode == IGT_COST_VALUE_NET;
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const size_t n_x = (size_t)B * 7, n_u = (size_t)B * 2, n_k = (size_t)B * 3;
     const size_t n_obs = (size_t)B * p.n_obs * 2 * (p.N + 1);
     const size_t n_X = (size_t)B * p.C * 7 * (p.N + 1), n_U = (size_t)B * p.C * 2 * p.N, n_c = (size_t)B * p.C;
     igt::SolveArgs<T> A{};
     A.table = h->table_set ? h->d_table : nullptr;
     A.cinf = h->kp.F > 0 ? h->d_cinf : nullptr;
-    T *dX = X_all, *dU = U_all, *dc = cost_all;
-    uint32_t* dv = viol_all;
-    if (mem == IGT_MEM_DEVICE) {
-        A.x0 = x0; A.u_prev = u_prev; A.kparams = kparams; A.flags = flags; A.obs = obs_xy;
-        A.tv_sv = tv_sv; A.enc = enc; A.u_ws = u_ws;
-    } else if (mem == IGT_MEM_HOST) {
-        const size_t n_ws = u_ws ? (size_t)B * 2 * p.N : 0;
-        T *dx0, *dup, *dk, *dob, *dtv, *den, *dws;
-        uint32_t* dfl;
-        const auto carve = [&](Arena& ar) {
-            dx0 = ar.take<T>(n_x); dup = ar.take<T>(n_u); dk = ar.take<T>(n_k);
-            dfl = ar.take<uint32_t>(B); dob = ar.take<T>(n_obs ? n_obs : 1);
-            dX = X_all ? ar.take<T>(n_X) : nullptr;
-            dU = U_all ? ar.take<T>(n_U) : nullptr;
-            dc = ar.take<T>(n_c); dv = ar.take<uint32_t>(n_c);
-            dtv = ar.take<T>(n_u); den = ar.take<T>(n_u);
-            dws = u_ws ? ar.take<T>(n_ws) : nullptr;
-        };
-        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
-        Arena ar{(char*)h->d_stage, 0};
-        carve(ar);
-        if (value) {
-            HIPCHK(hipMemcpyAsync(dtv, tv_sv, n_u * sizeof(T), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(den, enc, n_u * sizeof(T), hipMemcpyHostToDevice, st));
-        }
-        A.tv_sv = dtv; A.enc = den;
-        if (u_ws) {
-            HIPCHK(hipMemcpyAsync(dws, u_ws, n_ws * sizeof(T), hipMemcpyHostToDevice, st));
-            A.u_ws = dws;
-        }
-        HIPCHK(hipMemcpyAsync(dx0, x0, n_x * sizeof(T), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(dup, u_prev, n_u * sizeof(T), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(dk, kparams, n_k * sizeof(T), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(dfl, flags, (size_t)B * 4, hipMemcpyHostToDevice, st));
-        if (n_obs) HIPCHK(hipMemcpyAsync(dob, obs_xy, n_obs * sizeof(T), hipMemcpyHostToDevice, st));
-        A.x0 = dx0; A.u_prev = dup; A.kparams = dk; A.flags = dfl; A.obs = dob;
-    } else {
-        return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
-    }
+    T *dX, *dU, *dc;
+    uint32_t* dv;
+    Staging stg(h, mem, stream);
+    stg.in(&A.x0, x0, n_x); stg.in(&A.u_prev, u_prev, n_u); stg.in(&A.kparams, kparams, n_k);
+    stg.in(&A.flags, flags, (size_t)B); stg.in(&A.obs, obs_xy, n_obs);
+    stg.in(&A.tv_sv, tv_sv, n_u, value); stg.in(&A.enc, enc, n_u, value);
+    stg.in(&A.u_ws, u_ws, (size_t)B * 2 * p.N);
+    stg.out(&dX, X_all, n_X); stg.out(&dU, U_all, n_U);      // optional: null = not wanted
+    stg.out(&dc, cost_all, n_c); stg.out(&dv, viol_all, n_c);
+    if (int rc = stg.upload()) return rc;
+    hipStream_t st = stg.stream();
     if (value) {   // records -> value_kernel fills cost_all / viol_all with the terminal term included
         const auto carve = [&](Arena& wa) {
             A.rec_J = wa.take<double>(n_c);
@@ -578,20 +563,11 @@ int rollout_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T
             A.rec_viol = wa.take<uint32_t>(n_c);
             A.p_vec = wa.take<T>((size_t)B * igt::VN_H);
         };
-        if (int rc = ensure_work(h, arena_bytes(carve), st)) return rc;
-        Arena wa{(char*)h->d_work, 0};
-        carve(wa);
+        if (int rc = carve_work(h, st, carve)) return rc;
     }
     HIPCHK(igt::launch_rollout_all<T>(h->kp, B, A, dX, dU, dc, dv, st));
     if (value) HIPCHK(igt::launch_value<T>(h->kp, B, net_of<T>(h), A, dc, dv, st));
-    if (mem == IGT_MEM_HOST) {
-        if (X_all) HIPCHK(hipMemcpyAsync(X_all, dX, n_X * sizeof(T), hipMemcpyDeviceToHost, st));
-        if (U_all) HIPCHK(hipMemcpyAsync(U_all, dU, n_U * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(cost_all, dc, n_c * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(viol_all, dv, n_c * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return IGT_OK;
+    return stg.download();
 }
 
 template <typename T>
@@ -601,30 +577,15 @@ int frenet_step_impl(igt_handle* h, int32_t n, const T* x, const T* u, const T* 
     if (n < 0) return fail(IGT_E_INVALID, "negative size");
     if (n == 0) return IGT_OK;
     if (!x || !u || !kparams || !x_next) return fail(IGT_E_INVALID, "null buffer");
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const size_t n_x = (size_t)n * 7, n_u = (size_t)n * 2, n_k = (size_t)n * 3;
-    const T *dx = x, *du = u, *dk = kparams;
-    T* dout = x_next;
-    if (mem == IGT_MEM_HOST) {
-        T *a, *b, *c;
-        const auto carve = [&](Arena& ar) { a = ar.take<T>(n_x); b = ar.take<T>(n_u); c = ar.take<T>(n_k); dout = ar.take<T>(n_x); };
-        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
-        Arena ar{(char*)h->d_stage, 0};
-        carve(ar);
-        HIPCHK(hipMemcpyAsync(a, x, n_x * sizeof(T), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(b, u, n_u * sizeof(T), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(c, kparams, n_k * sizeof(T), hipMemcpyHostToDevice, st));
-        dx = a; du = b; dk = c;
-    } else if (mem != IGT_MEM_DEVICE) {
-        return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
-    }
-    HIPCHK(igt::launch_frenet_step<T>(h->kp, n, dx, du, dk, dout, st));
-    if (mem == IGT_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(x_next, dout, n_x * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return IGT_OK;
+    const T *dx, *du, *dk;
+    T* dout;
+    Staging stg(h, mem, stream);
+    stg.in(&dx, x, n_x); stg.in(&du, u, n_u); stg.in(&dk, kparams, n_k);
+    stg.out(&dout, x_next, n_x);
+    if (int rc = stg.upload()) return rc;
+    HIPCHK(igt::launch_frenet_step<T>(h->kp, n, dx, du, dk, dout, stg.stream()));
+    return stg.download();
 }
 
 int cost_gradient_impl(igt_handle* h, int32_t B, const double* x0, const double* kparams, const uint32_t* flags, const double* U,
@@ -636,35 +597,16 @@ int cost_gradient_impl(igt_handle* h, int32_t B, const double* x0, const double*
     if (B == 0) return IGT_OK;
     if (!cost_out || !grad_out) return fail(IGT_E_INVALID, "null output buffer (cost_out, grad_out)");
     if (!x0 || !kparams || !flags || !U) return fail(IGT_E_INVALID, "null buffer");
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const size_t n_x = (size_t)B * 7, n_k = (size_t)B * 3, n_u = (size_t)B * 2 * h->p.N;
-    const double *dx = x0, *dk = kparams, *du = U;
-    double *dc = cost_out, *dg = grad_out;
-    if (mem == IGT_MEM_HOST) {
-        double *a, *b, *c;
-        const auto carve = [&](Arena& ar) {
-            a = ar.take<double>(n_x); b = ar.take<double>(n_k); c = ar.take<double>(n_u);
-            dc = ar.take<double>((size_t)B); dg = ar.take<double>(n_u);
-        };
-        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
-        Arena ar{(char*)h->d_stage, 0};
-        carve(ar);
-        HIPCHK(hipMemcpyAsync(a, x0, n_x * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(b, kparams, n_k * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(c, U, n_u * 8, hipMemcpyHostToDevice, st));
-        dx = a; dk = b; du = c;
-    } else if (mem != IGT_MEM_DEVICE) {
-        return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
-    }
+    const double *dx, *dk, *du;
+    double *dc, *dg;
+    Staging stg(h, mem, stream);
+    stg.in(&dx, x0, n_x); stg.in(&dk, kparams, n_k); stg.in(&du, U, n_u);
+    stg.out(&dc, cost_out, (size_t)B); stg.out(&dg, grad_out, n_u);
+    if (int rc = stg.upload()) return rc;
     // the flags only act on psi_0, which the progress cost never reads (igt_kernels_f64.hip cost_gradient_f64_kernel)
-    HIPCHK(igt::launch_cost_gradient(h->kp, B, dx, dk, du, dc, dg, st));
-    if (mem == IGT_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(cost_out, dc, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(grad_out, dg, n_u * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return IGT_OK;
+    HIPCHK(igt::launch_cost_gradient(h->kp, B, dx, dk, du, dc, dg, stg.stream()));
+    return stg.download();
 }
 
 // what the two value-network gradient entries refuse before they look at their buffers
@@ -679,37 +621,20 @@ int terminal_value_impl(igt_handle* h, int32_t n, const double* sv, const double
                         double* dV_out, int mem, void* stream) {
     if (int rc = check_value_handle(h, "igt_terminal_value_f64")) return rc;
     if (n < 0) return fail(IGT_E_INVALID, "n < 0");
-    if (mem != IGT_MEM_DEVICE && mem != IGT_MEM_HOST) return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
+    Staging stg(h, mem, stream);
+    if (int rc = stg.check_mem()) return rc;      // (refused for an empty batch as well)
     if (n == 0) return IGT_OK;
     if (!V_out) return fail(IGT_E_INVALID, "null output buffer (V_out)");
     if (!sv || !tv_sv || !enc) return fail(IGT_E_INVALID, "null buffer");
     if (!h->net_set) return fail(IGT_E_STATE, "value net not set (igt_set_value_net)");
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const size_t n2 = (size_t)n * 2;
-    const double *ds = sv, *dt = tv_sv, *de = enc;
-    double *dV = V_out, *dG = dV_out;
-    if (mem == IGT_MEM_HOST) {
-        double *a, *b, *c;
-        const auto carve = [&](Arena& ar) {
-            a = ar.take<double>(n2); b = ar.take<double>(n2); c = ar.take<double>(n2);
-            dV = ar.take<double>((size_t)n); dG = dV_out ? ar.take<double>(n2) : nullptr;
-        };
-        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
-        Arena ar{(char*)h->d_stage, 0};
-        carve(ar);
-        HIPCHK(hipMemcpyAsync(a, sv, n2 * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(b, tv_sv, n2 * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(c, enc, n2 * 8, hipMemcpyHostToDevice, st));
-        ds = a; dt = b; de = c;
-    }
-    HIPCHK(igt::launch_terminal_value(h->net_d, h->n_cu, n, ds, dt, de, dV, dG, st));
-    if (mem == IGT_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(V_out, dV, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-        if (dV_out) HIPCHK(hipMemcpyAsync(dV_out, dG, n2 * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return IGT_OK;
+    const double *ds, *dt, *de;
+    double *dV, *dG;
+    stg.in(&ds, sv, n2); stg.in(&dt, tv_sv, n2); stg.in(&de, enc, n2);
+    stg.out(&dV, V_out, (size_t)n); stg.out(&dG, dV_out, n2);      // dV_out is optional
+    if (int rc = stg.upload()) return rc;
+    HIPCHK(igt::launch_terminal_value(h->net_d, h->n_cu, n, ds, dt, de, dV, dG, stg.stream()));
+    return stg.download();
 }
 
 // Three launches: the forward sweep leaves (s_N, v_N) in the workspace, the network answers V_out and its
@@ -720,50 +645,30 @@ int cost_gradient_vn_impl(igt_handle* h, int32_t B, const double* x0, const doub
                           void* stream) {
     if (int rc = check_value_handle(h, "igt_cost_gradient_vn_f64")) return rc;
     if (B < 0) return fail(IGT_E_INVALID, "B < 0");
-    if (mem != IGT_MEM_DEVICE && mem != IGT_MEM_HOST) return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
+    Staging stg(h, mem, stream);
+    if (int rc = stg.check_mem()) return rc;      // (refused for an empty batch as well)
     if (B == 0) return IGT_OK;
     if (!cost_out || !grad_out) return fail(IGT_E_INVALID, "null output buffer (cost_out, grad_out)");
     if (!x0 || !kparams || !flags || !U) return fail(IGT_E_INVALID, "null buffer");
     if (!tv_sv || !enc) return fail(IGT_E_INVALID, "tv_sv / enc required for the value-net cost");
     if (!h->net_set) return fail(IGT_E_STATE, "value net not set (igt_set_value_net)");
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const size_t n_x = (size_t)B * 7, n_k = (size_t)B * 3, n_2 = (size_t)B * 2, n_u = (size_t)B * 2 * h->p.N;
-    const double *dx = x0, *dk = kparams, *du = U, *dt = tv_sv, *de = enc;
-    double *dc = cost_out, *dg = grad_out;
-    if (mem == IGT_MEM_HOST) {
-        double *a, *b, *c, *d, *e;
-        const auto carve = [&](Arena& ar) {
-            a = ar.take<double>(n_x); b = ar.take<double>(n_k); c = ar.take<double>(n_u);
-            d = ar.take<double>(n_2); e = ar.take<double>(n_2);
-            dc = ar.take<double>((size_t)B); dg = ar.take<double>(n_u);
-        };
-        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
-        Arena ar{(char*)h->d_stage, 0};
-        carve(ar);
-        HIPCHK(hipMemcpyAsync(a, x0, n_x * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(b, kparams, n_k * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(c, U, n_u * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d, tv_sv, n_2 * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(e, enc, n_2 * 8, hipMemcpyHostToDevice, st));
-        dx = a; dk = b; du = c; dt = d; de = e;
-    }
+    const double *dx, *dk, *du, *dt, *de;
+    double *dc, *dg;
+    stg.in(&dx, x0, n_x); stg.in(&dk, kparams, n_k); stg.in(&du, U, n_u);
+    stg.in(&dt, tv_sv, n_2); stg.in(&de, enc, n_2);
+    stg.out(&dc, cost_out, (size_t)B); stg.out(&dg, grad_out, n_u);
+    if (int rc = stg.upload()) return rc;
+    hipStream_t st = stg.stream();
     double* vn = nullptr;
     const auto carve = [&](Arena& wa) { vn = wa.take<double>(igt::VnScratch::doubles(B)); };
-    if (int rc = ensure_work(h, arena_bytes(carve), st)) return rc;
-    Arena wa{(char*)h->d_work, 0};
-    carve(wa);
+    if (int rc = carve_work(h, st, carve)) return rc;
     const igt::VnScratch S(vn, B);
     // the flags only act on psi_0, which neither the stage terms nor the network's features read
     HIPCHK(igt::launch_cost_gradient_vn(h->kp, B, true, dx, dk, du, dc, dg, vn, st));
     HIPCHK(igt::launch_terminal_value(h->net_d, h->n_cu, B, S.sv(), dt, de, S.V(), S.dV(), st));
     HIPCHK(igt::launch_cost_gradient_vn(h->kp, B, false, dx, dk, du, dc, dg, vn, st));
-    if (mem == IGT_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(cost_out, dc, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(grad_out, dg, n_u * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return IGT_OK;
+    return stg.download();
 }
 
 template <typename T>
@@ -777,50 +682,22 @@ int forecast_impl(igt_handle* h, int32_t B, const T* ego_xyh, const T* opp, cons
     if (!ego_xyh || !opp || !opp_a || !opp_route || !obs_xy || !tv_sv) return fail(IGT_E_INVALID, "null buffer");
     const bool plans = plan_x && plan_u && has_plan;
     if (!plans && (plan_x || plan_u || has_plan)) return fail(IGT_E_INVALID, "plan_x, plan_u, has_plan go together");
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const int N = h->p.N;
     const size_t M1 = (size_t)h->p.n_obs;            // other vehicles per scene: every per-opponent array is [B, n_obs, ...]
-    const size_t n_e = (size_t)B * 3, n_o = (size_t)B * M1 * 4, n_px = (size_t)B * M1 * 7 * (N + 1), n_pu = (size_t)B * M1 * 2 * N;
-    const size_t n_out = (size_t)B * M1 * 2 * (N + 1), n_tv = (size_t)B * M1 * 2;
-    const size_t n_pairs = (size_t)B * M1;
-    const T *de = ego_xyh, *dop = opp, *da = opp_a, *dpx = plan_x, *dpu = plan_u;
-    const int32_t *dr = opp_route, *dhp = has_plan;
-    T *dout = obs_xy, *dtv = tv_sv;
-    if (mem == IGT_MEM_HOST) {
-        T *a0, *a1, *a2, *a5, *a6;
-        int32_t *a3, *a4;
-        const auto carve = [&](Arena& ar) {
-            a0 = ar.take<T>(n_e); a1 = ar.take<T>(n_o); a2 = ar.take<T>(n_pairs);
-            a3 = ar.take<int32_t>(n_pairs); a4 = ar.take<int32_t>(n_pairs);
-            a5 = ar.take<T>(plans ? n_px : 1); a6 = ar.take<T>(plans ? n_pu : 1);
-            dout = ar.take<T>(n_out); dtv = ar.take<T>(n_tv);
-        };
-        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
-        Arena ar{(char*)h->d_stage, 0};
-        carve(ar);
-        HIPCHK(hipMemcpyAsync(a0, ego_xyh, n_e * sizeof(T), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(a1, opp, n_o * sizeof(T), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(a2, opp_a, n_pairs * sizeof(T), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(a3, opp_route, n_pairs * 4, hipMemcpyHostToDevice, st));
-        de = a0; dop = a1; da = a2; dr = a3;
-        if (plans) {
-            HIPCHK(hipMemcpyAsync(a4, has_plan, n_pairs * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(a5, plan_x, n_px * sizeof(T), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(a6, plan_u, n_pu * sizeof(T), hipMemcpyHostToDevice, st));
-            dhp = a4; dpx = a5; dpu = a6;
-        }
-    } else if (mem != IGT_MEM_DEVICE) {
-        return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
-    }
+    const size_t n_e = (size_t)B * 3, n_o = (size_t)B * M1 * 4, n_pairs = (size_t)B * M1;
+    const size_t n_px = plans ? n_pairs * 7 * (N + 1) : 0, n_pu = plans ? n_pairs * 2 * N : 0;      // without plans: reserved only
+    const size_t n_out = n_pairs * 2 * (N + 1), n_tv = n_pairs * 2;
+    const T *de, *dop, *da, *dpx, *dpu;
+    const int32_t *dr, *dhp;
+    T *dout, *dtv;
+    Staging stg(h, mem, stream);
+    stg.in(&de, ego_xyh, n_e); stg.in(&dop, opp, n_o); stg.in(&da, opp_a, n_pairs); stg.in(&dr, opp_route, n_pairs);
+    stg.in(&dhp, has_plan, n_pairs, plans); stg.in(&dpx, plan_x, n_px); stg.in(&dpu, plan_u, n_pu);
+    stg.out(&dout, obs_xy, n_out); stg.out(&dtv, tv_sv, n_tv);
+    if (int rc = stg.upload()) return rc;
     HIPCHK(igt::launch_forecast<T>(h->kp, B, h->d_routes, h->n_routes, de, dop, da, dr, plans ? dpx : nullptr,
-                                   plans ? dpu : nullptr, plans ? dhp : nullptr, dout, dtv, st));
-    if (mem == IGT_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(obs_xy, dout, n_out * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(tv_sv, dtv, n_tv * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return IGT_OK;
+                                   plans ? dpu : nullptr, plans ? dhp : nullptr, dout, dtv, stg.stream()));
+    return stg.download();
 }
 
 template <typename T>
@@ -837,45 +714,20 @@ int forecast_scene_impl(igt_handle* h, int32_t E, const T* x, const T* a_prev, c
     const int N = h->p.N;
     const size_t M = (size_t)h->p.n_obs + 1;         // agents per scene; problem e M + i = agent i of scene e as ego
     if ((size_t)E > (size_t)0x7fffffff / (M * (M - 1))) return fail(IGT_E_INVALID, "E (n_obs + 1) n_obs exceeds int32");
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    const size_t n_ag = (size_t)E * M, n_x = n_ag * 7, n_px = n_ag * 7 * (N + 1), n_pu = n_ag * 2 * N;
+    const size_t n_ag = (size_t)E * M, n_x = n_ag * 7;
+    const size_t n_px = plans ? n_ag * 7 * (N + 1) : 0, n_pu = plans ? n_ag * 2 * N : 0;      // without plans: reserved only
     const size_t n_pairs = n_ag * (M - 1), n_out = n_pairs * 2 * (N + 1), n_tv = n_pairs * 2;
-    const T *dx = x, *da = a_prev, *dpx = plan_x, *dpu = plan_u;
-    const int32_t *dr = route, *dhp = has_plan;
-    T *dout = obs_xy, *dtv = tv_sv;
-    if (mem == IGT_MEM_HOST) {
-        T *a0, *a1, *a4, *a5;
-        int32_t *a2, *a3;
-        const auto carve = [&](Arena& ar) {
-            a0 = ar.take<T>(n_x); a1 = ar.take<T>(n_ag); a2 = ar.take<int32_t>(n_ag); a3 = ar.take<int32_t>(n_ag);
-            a4 = ar.take<T>(plans ? n_px : 1); a5 = ar.take<T>(plans ? n_pu : 1);
-            dout = ar.take<T>(n_out); dtv = ar.take<T>(n_tv);
-        };
-        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
-        Arena ar{(char*)h->d_stage, 0};
-        carve(ar);
-        HIPCHK(hipMemcpyAsync(a0, x, n_x * sizeof(T), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(a1, a_prev, n_ag * sizeof(T), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(a2, route, n_ag * 4, hipMemcpyHostToDevice, st));
-        dx = a0; da = a1; dr = a2;
-        if (plans) {
-            HIPCHK(hipMemcpyAsync(a3, has_plan, n_ag * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(a4, plan_x, n_px * sizeof(T), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(a5, plan_u, n_pu * sizeof(T), hipMemcpyHostToDevice, st));
-            dhp = a3; dpx = a4; dpu = a5;
-        }
-    } else if (mem != IGT_MEM_DEVICE) {
-        return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
-    }
+    const T *dx, *da, *dpx, *dpu;
+    const int32_t *dr, *dhp;
+    T *dout, *dtv;
+    Staging stg(h, mem, stream);
+    stg.in(&dx, x, n_x); stg.in(&da, a_prev, n_ag); stg.in(&dr, route, n_ag);
+    stg.in(&dhp, has_plan, n_ag, plans); stg.in(&dpx, plan_x, n_px); stg.in(&dpu, plan_u, n_pu);
+    stg.out(&dout, obs_xy, n_out); stg.out(&dtv, tv_sv, n_tv);
+    if (int rc = stg.upload()) return rc;
     HIPCHK(igt::launch_forecast_scene<T>(h->kp, E, h->d_routes, h->n_routes, dx, da, dr, plans ? dpx : nullptr,
-                                         plans ? dpu : nullptr, plans ? dhp : nullptr, dout, dtv, st));
-    if (mem == IGT_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(obs_xy, dout, n_out * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(tv_sv, dtv, n_tv * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return IGT_OK;
+                                         plans ? dpu : nullptr, plans ? dhp : nullptr, dout, dtv, stg.stream()));
+    return stg.download();
 }
 
 template <typename T>
@@ -884,29 +736,15 @@ int cartesian_impl(igt_handle* h, int32_t n, int32_t steps, const T* z0, const T
     if (n < 0 || steps < 0) return fail(IGT_E_INVALID, "negative size");
     if (n == 0) return IGT_OK;
     if (!z0 || !z_out || (steps > 0 && !u)) return fail(IGT_E_INVALID, "null buffer");
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const size_t n_z = (size_t)n * 4, n_u = (size_t)n * 2 * steps, n_o = (size_t)n * 4 * (steps + 1);
-    const T *dz = z0, *du = u;
-    T* dout = z_out;
-    if (mem == IGT_MEM_HOST) {
-        T *a, *b;
-        const auto carve = [&](Arena& ar) { a = ar.take<T>(n_z); b = ar.take<T>(n_u ? n_u : 1); dout = ar.take<T>(n_o); };
-        if (int rc = ensure_stage(h, arena_bytes(carve))) return rc;
-        Arena ar{(char*)h->d_stage, 0};
-        carve(ar);
-        HIPCHK(hipMemcpyAsync(a, z0, n_z * sizeof(T), hipMemcpyHostToDevice, st));
-        if (n_u) HIPCHK(hipMemcpyAsync(b, u, n_u * sizeof(T), hipMemcpyHostToDevice, st));
-        dz = a; du = b;
-    } else if (mem != IGT_MEM_DEVICE) {
-        return fail(IGT_E_INVALID, "mem must be IGT_MEM_DEVICE or IGT_MEM_HOST");
-    }
-    HIPCHK(igt::launch_cartesian<T>(n, steps, h->p.dt, h->p.l_r, h->p.l_f, dz, du, dout, st));
-    if (mem == IGT_MEM_HOST) {
-        HIPCHK(hipMemcpyAsync(z_out, dout, n_o * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return IGT_OK;
+    const T *dz, *du;
+    T* dout;
+    Staging stg(h, mem, stream);
+    stg.in(&dz, z0, n_z); stg.in(&du, u, n_u);      // steps == 0: u is reserved only
+    stg.out(&dout, z_out, n_o);
+    if (int rc = stg.upload()) return rc;
+    HIPCHK(igt::launch_cartesian<T>(n, steps, h->p.dt, h->p.l_r, h->p.l_f, dz, du, dout, stg.stream()));
+    return stg.download();
 }
 
 template <typename T>
@@ -992,23 +830,12 @@ int igt_create(const igt_params* p, int device, igt_handle** out) {
     h->p = *p;
     h->kp = make_kp(*p, 0);
     h->device = device;
-    h->d_cinf = nullptr; h->d_table = nullptr; h->table_set = false; h->net_set = false;
-    h->d_stage = nullptr; h->stage_bytes = 0; h->h_stage = nullptr;
-    h->d_work = nullptr; h->work_bytes = 0;
-    h->d_net = nullptr;
-    h->d_routes = nullptr; h->n_routes = 0;
-    h->prof = false; h->ev_recorded = false;
-    h->comm = nullptr; h->comm_world = 1; h->comm_rank = 0; h->comm_B_local = 0; h->d_u0 = nullptr; h->u0_bytes = 0;
-    h->nc = 2;
     if (const char* e = std::getenv("IGT_NC")) {
         const int v = std::atoi(e);
         if (v == 1 || v == 2 || v == 4) h->nc = v;
     }
     while ((p->C / 64) % h->nc) h->nc /= 2;
-    h->n_cu = 256;
-    h->concurrency = 1;
-    h->polish_grad = IGT_GRAD_FORWARD_DIFF;
-    h->dev_ckpt = -1; h->dev_traj_max = -1;      // developer sweeps: the environment is read here, not on every solve
+    // developer sweeps: the environment is read here, not on every solve
     if (const char* e = std::getenv("IGT_DEV_CKPT")) h->dev_ckpt = std::max(std::atoi(e), 0);
     if (const char* e = std::getenv("IGT_DEV_TRAJ_MAX")) h->dev_traj_max = std::max(std::atoi(e), 0);
     { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0) h->n_cu = v; }

@@ -378,6 +378,26 @@ def test_dispatch_helper_reaches_each_leaf_once(tmp_path):
     assert re.findall(r'#include\s*[<"]([^>"]+)', hdr) == ['type_traits']      # no HIP header behind it
 
 
+def test_stage_plan_lays_host_buffers_out_without_overlap(tmp_path):
+    """csrc/igt_stage.h is where every host-mode call's staging layout comes from (igt_api.hip Staging).  It is plain C++17, so
+    a host compiler builds tests/stage_plan.cpp against it alone, under the address and undefined-behaviour sanitizers:
+    aligned, disjoint offsets with the inputs below in_span and the outputs in [out_begin, total), absent and reserved
+    buffers, a solve's totals worked out by hand, the 256 KiB packing rule, gather / scatter on exactly-sized heap blocks."""
+    import shutil
+    import subprocess
+    if not shutil.which('g++'):
+        pytest.skip('no g++')
+    exe = tmp_path / 'stage_plan'
+    r = subprocess.run(['g++', '-std=c++17', '-Wall', '-Wextra', '-Werror', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                        '-I', os.path.join(ROOT, 'igt-mpc-int_amd', 'csrc'), os.path.join(ROOT, 'tests', 'stage_plan.cpp'),
+                        '-o', str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == 'stage plan ok', r.stdout + r.stderr
+    hdr = open(os.path.join(ROOT, 'igt-mpc-int_amd', 'csrc', 'igt_stage.h')).read()
+    assert re.findall(r'#include\s*[<"]([^>"]+)', hdr) == ['cstddef', 'cstring']      # no HIP header behind it
+
+
 def test_leaf_cases_restate_the_hi_order_rule():
     """tests/test_gpu_dispatch_leaves.py picks n_rk4 values by KP::hi_order, which the library does not report:
     parity_cases.leaf_hi_order restates the rule, and the statements it restates must be the ones in csrc/igt_api.hip."""
