@@ -457,7 +457,10 @@ struct LaneRoll {
 // table (entry k at stab[k * stab_stride]); CAND_TABLE: the lane's control sequence (see the table branch).
 // STEPTAB (rollout_pool without checkpoint slots; lattice, STAB): the column is one of fill_pool_table's -- sblr comes from the
 // table, step_tail reads the rotation there, and (sin, cos)(beta_k), (sin, cos)(beta_k-1) are not carried by the lane at all.
-template <int CAND, bool BOOK, bool LEAN, bool BOUND, bool STAB, int SEGMODE, bool STEPTAB = false, class FP, class Sink>
+// EY_FOLDED (rollout_pool): |ey_k| - ey_lim is in gmax already -- the pool folds it where it decides whether the lane keeps its
+// candidate, at the end of step k - 1 (at the refill for state 0) -- and is not folded a second time here.
+template <int CAND, bool BOOK, bool LEAN, bool BOUND, bool STAB, int SEGMODE, bool STEPTAB = false, bool EY_FOLDED = false,
+          class FP, class Sink>
 __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S, const FP& fp, LaneRoll<FP>& L, int k, int cidx,
                                           const double* __restrict__ table, const double* __restrict__ cinf, Sink& sink,
                                           const double* __restrict__ stab, int stab_stride, const unsigned long long* inc,
@@ -529,7 +532,7 @@ __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S
         L.J = L.J + L.ep * L.ep;
         L.J = L.J + L.ey * L.ey;
         if (LEAN) {
-            L.gmax = fmax(L.gmax, fabs(L.ey) - P.ey_lim);                                  // mpc.py:296-299
+            if (!EY_FOLDED) L.gmax = fmax(L.gmax, fabs(L.ey) - P.ey_lim);                  // mpc.py:296-299
             if (!rows_judged) L.gmax = fmax(L.gmax, fmax(P.v_min - L.v, L.v - P.v_max));   // mpc.py:316-317 (k < N)
         } else {
             if (fabs(L.ey) - P.ey_lim > P.tol) L.viol |= VIOL_EY;
@@ -755,7 +758,8 @@ __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>&
 // rarely (5 %) and dies mostly between steps 4 and 12: a unit's wave spends much of its time issuing for lanes that are dead
 // already.  Here one wave owns all n candidates of its scenario as a pool: every lane holds a candidate number, a step k of
 // its own and its state; one iteration is one control step for every lane that holds a candidate, each at its own k; a lane
-// whose candidate failed a verdict in its last step (step_head) or reached k = N (horizon_end) takes the pool's next number -- numbers are handed
+// whose candidate has failed a verdict by the end of its step (|ey| of the state it reached, a collision of the one it left) or
+// reached k = N (horizon_end) takes the pool's next number -- numbers are handed
 // out by a ballot and a prefix count from a wave-uniform cursor, no atomics (tools/refill_model.py: 0.52 -> 0.39 of the
 // wave-steps on the benchmark batch).  The statements are rollout_one's (step_head / step_tail / horizon_end), so every
 // candidate's cost and verdicts are the bits the units compute; the sub-step votes run over lanes at different k and may pick
@@ -830,7 +834,8 @@ __device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>
                 c = (int)(w & 0xffffu);
                 lstab = stab + (w >> 16) * SF;
                 L.x = start[0]; L.y = start[1]; L.s = start[2]; L.ey = start[3]; L.ep = start[4]; L.v = start[5];
-                L.a = start[7]; L.df = start[8]; L.J = 0.0; L.gmax = -1.0e300; L.viol = 0u;
+                L.a = start[7]; L.df = start[8]; L.J = 0.0; L.viol = 0u;
+                L.gmax = fmax(-1.0e300, fabs(L.ey) - P.ey_lim);         // the |ey| verdict of state 0 (step_head EY_FOLDED)
                 L.w.d0 = L.w.d1 = 0.0;
                 L.w.s1 = start[9]; L.w.c1 = start[10]; L.w.s2 = start[11]; L.w.c2 = start[12];
                 if (CKPT) {
@@ -842,16 +847,22 @@ __device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>
             next += cnt;
         }
         if (__ballot(hold) == 0ull) break;
-        // ---- control step k for every lane that holds a candidate; it retires a candidate that failed a verdict of state k,
+        // ---- control step k for every lane that holds a candidate; it retires a candidate whose state k + 1 < N fails already,
         // and one that reached state N after the bookkeeping of the end of the horizon
         bool fin = false;
         double Jq = 0.0;
         if (hold) {
-            const bool lost = step_head<CAND, true, true, false, true, CKPT ? 1 : 0, !CKPT>(P, S, fp, L, k, c, nullptr, cinf, sink,
-                                                                                            lstab, stab_stride, nullptr, ck, true, kv_d);
+            step_head<CAND, true, true, false, true, CKPT ? 1 : 0, !CKPT, true>(P, S, fp, L, k, c, nullptr, cinf, sink, lstab,
+                                                                                stab_stride, nullptr, ck, true, kv_d);
             step_tail<true, true, false, true, XY, false, !CKPT, false>(P, S, fp, L, k, sink, nullptr, lstab, stab_stride);
             ++k;
-            if (lost) {
+            // state k is complete.  A candidate that fails its |ey| verdict, or failed the collision verdict of state k - 1
+            // (step_tail), can never finish feasible -- gmax only grows -- and gives up its lane now, not after one more step.
+            // The fold is step_head's own for state k, made here once (EY_FOLDED); step_head's verdict is not read: all it
+            // can report in a pool is gmax > tol, which this test sees at the end of the same step.  State N is horizon_end's,
+            // and so is a candidate that reaches it with a failed verdict (N = 1): it finishes infeasible.
+            if (k < P.N) L.gmax = fmax(L.gmax, fabs(L.ey) - P.ey_lim);                          // mpc.py:296-299
+            if (k < P.N && L.gmax > P.tol) {
                 hold = false;
             } else if (k == P.N) {
                 double J, sN, vN;

@@ -9,7 +9,9 @@ from oracle import np_oracle as O
 from igtmpc.scenarios import make_batch
 from igtmpc.cinf import cinf_halfplanes
 
-def death_steps(B=256, N=20, C=256, seed=0):
+def first_failures(B=256, N=20, C=256, seed=0):
+    """First state k < N at which each verdict of the search fails, per candidate (N + 1: never): 'v' the speed box, 'ey' the
+    lane, 'col' the collision (states 1 .. N - 1).  -> ({verdict: [B, C]}, P)"""
     P = O.Params(N=N)
     sc = make_batch(B, N, P.dt, seed=seed, dtype=np.float64)
     A, b = cinf_halfplanes(dt=P.dt, jerk=P.jerk)
@@ -17,18 +19,19 @@ def death_steps(B=256, N=20, C=256, seed=0):
     U = O.candidates_lattice(sc['u_prev'], P, C)                 # [B,C,2,N]
     X = O.rollout_frenet(x0[:, None, :], U, sc['kparams'][:, None, :], P)   # [B,C,7,N+1]
     tol = P.feas_tol
-    dead = np.full((B, C), N + 1, dtype=np.int64)                # step at which the kernel would know (N+1 = never)
-    def mark(viol_k):  # viol_k [B,C,K] for k = 0..K-1 -> step index where bit is first seen
-        K = viol_k.shape[-1]
-        first = np.where(viol_k.any(-1), viol_k.argmax(-1), N + 1)
-        np.minimum(dead, first, out=dead)
-    v = X[..., O.IV, :N]; mark(np.maximum(P.v_min - v, v - P.v_max) > tol)
-    mark((np.abs(X[..., O.IEY, :N]) - P.ey_lim) > tol)
+    first = lambda viol_k: np.where(viol_k.any(-1), viol_k.argmax(-1), N + 1)   # viol_k [B,C,K], k = 0..K-1
+    v = X[..., O.IV, :N]
     ob = sc['obs_xy']                                            # [B,n_obs,2,N+1]
     dx = X[:, :, None, O.IX, :] - ob[:, None, :, 0, :]; dy = X[:, :, None, O.IY, :] - ob[:, None, :, 1, :]
     col = (P.d_min ** 2 - (dx * dx + dy * dy)) > tol; col[..., 0] = False
-    mark(col.any(2)[..., :N])
-    return dead, P
+    return dict(v=first(np.maximum(P.v_min - v, v - P.v_max) > tol),
+                ey=first((np.abs(X[..., O.IEY, :N]) - P.ey_lim) > tol),
+                col=first(col.any(2)[..., :N])), P
+
+def death_steps(B=256, N=20, C=256, seed=0):
+    """step at which the kernel would know that a candidate failed a verdict (N + 1 = never)"""
+    f, P = first_failures(B, N, C, seed)
+    return np.minimum(np.minimum(f['v'], f['ey']), f['col']).astype(np.int64), P
 
 def saved(dead, groups, N):
     """groups: list of index arrays (one per wave).  Fraction of wave-steps executed with whole-wave early exit."""
