@@ -494,6 +494,11 @@ struct Ckpt {
     int unit, slot0;
     int every;               // control steps between checkpoints = N / parts
 };
+struct PairIn {              // the optional run-time inputs of rollout_pair (igt_fast_impl.inc), by name
+    Ckpt ck{nullptr, 0, 0, 0, 0};
+    Seg seg{0, 0, nullptr, 0};
+    const unsigned long long* inc = nullptr;      // the scenario's incumbent key (search, tracking family; null: no bound)
+};
 
 struct NullSink {
     static constexpr bool kKeepsStates = false;

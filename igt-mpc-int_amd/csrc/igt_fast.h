@@ -25,6 +25,7 @@
 #pragma once
 #include <type_traits>
 #include "igt_device.h"
+#include "igt_roll_options.h"
 
 namespace igt {
 

@@ -21,6 +21,7 @@
 #pragma once
 #include "igt_device.h"
 #include "igt_math64.h"
+#include "igt_roll_options.h"
 
 namespace igt {
 namespace f64 {
@@ -297,9 +298,9 @@ struct Fast64 {
 // one pass over ONE candidate per lane
 // ---------------------------------------------------------------------------------------
 // CAND = CAND_LATTICE / CAND_RAMP_HOLD: generated controls, input box / rate limits hold by construction;
-// CAND_TABLE: controls come from the table and are checked.  BOOK = false (emit): cost and verdicts are skipped.
-// EARLY_EXIT (search): the unit stops once every candidate of the wave has failed a verdict; then only "failed" is
-// reported (vout != 0), the verdict bits are those found so far.
+// CAND_TABLE: controls come from the table and are checked.  Without ROLL_BOOK (emit) cost and verdicts are skipped.
+// ROLL_EARLY_EXIT (search): the unit stops once every candidate of the wave has failed a verdict; then only "failed" is
+// reported (vout != 0), the verdict bits are those found so far.  (The options: igt_roll_options.h.)
 // Steering angle of step k for the generated families whose steering does not depend on the rolled state.
 template <int CAND>
 __device__ __forceinline__ double steer_next(const KP& P, const Scenario<double>& S, int k, double ddf, double df) {
@@ -415,21 +416,22 @@ __device__ __forceinline__ void fill_pool_table(const KP& P, const Scenario<doub
 // steps a unit rolls depends on which incumbents it saw (tools/bound_prune_probe.py: 0.84 -> 0.46 of the wave-steps).
 // (VIOL_PRUNED, cost_key / cost_of_key, progress_slack: igt_device.h -- the float path prunes the same way)
 
-// XY = false (search only, decided per unit by obstacles_out_of_reach): x, y are neither integrated nor judged -- no candidate
+// ROLL_NO_XY (search, decided per unit by obstacles_out_of_reach): x, y are neither integrated nor judged -- no candidate
 // that holds the speed box can come within d_min of any forecast position, and one that does not is infeasible already.
 // inc (search, CAND_TRACK, progress cost; may be null): the scenario's incumbent key, see above.
-// ---- horizon checkpoints (SEGMODE): the winner's trajectory in pieces ----
+// ---- horizon checkpoints (ROLL_LEAVE_CKPT, ROLL_RESUME): the winner's trajectory in pieces ----
 // emit rolls the winner again (keeping 147 state values per candidate alive in the search would cost more), and one roll-out is
 // a serial chain: 51 us at N = 20, all of it exposed when solves do not overlap.  The search pass therefore leaves, at the three
 // steps k = i N / 4, what a roll-out needs to RESUME there exactly: (s, ey, epsi), the carried pair (sin, cos)(epsi + beta_k-1)
 // and -- tracking family, whose steering is a feedback on the rolled state -- (df_k-1, sin beta_k-1, cos beta_k-1); everything
 // else of the state at node k is a function of the candidate alone (a and v: the row's recurrence; df of the lattice / ramp-hold /
-// table families: the column's) and is replayed.  SEGMODE 1 (search): every lane writes its values to its LDS slots `ck`
-// (field-major, stride 64: igt_kernels_f64.hip search_unit64 copies the unit winner's to HBM).  SEGMODE 2 (emit_seg_f64_kernel):
+// table families: the column's) and is replayed.  ROLL_LEAVE_CKPT (search): every lane writes its values to its LDS slots `ck`
+// (field-major, stride 64: igt_kernels_f64.hip search_unit64 copies the unit winner's to HBM).  ROLL_RESUME (emit_seg_f64_kernel):
 // rolls steps [seg_k0, seg_k1) from the record `ck` (stride 1) of the checkpoint at seg_k0 -- the same statements on the same
 // numbers, so the four pieces are the unsegmented roll-out bit for bit.  x, y, psi feed nothing back and are rolled on their own
 // from the controls (cartesian_rows below).
 constexpr int CK_FIELDS = 8, CK_PARTS = 4;                      // record: s ey epsi s1 c1 [df sb cb]; pieces of the horizon
+constexpr int ck_fields(int cand) { return cand == CAND_TRACK ? 8 : 5; }                   // fields the family writes of a record
 __host__ __device__ inline int ckpt_step(int N, int i) { return (i * N) / CK_PARTS; }      // first step of piece i
 
 // What one lane carries from control step to control step (rollout_one, rollout_pool): the state, the candidate's control
@@ -448,26 +450,77 @@ struct LaneRoll {
     double rem, jcut, seg_scale;
 };
 
+// What a build is, from (CAND, options, Sink): the options by name and the constants derived from them, in one place.
+template <int CAND, unsigned O, class Sink>
+struct Roll {
+    static constexpr bool BOOK = (O & ROLL_BOOK) != 0, UNIFORM = (O & ROLL_UNIFORM) != 0, EARLY_EXIT = (O & ROLL_EARLY_EXIT) != 0;
+    static constexpr bool STAB = (O & ROLL_STEER_TABLE) != 0, XY = !(O & ROLL_NO_XY), STEPTAB = (O & ROLL_STEP_TABLE) != 0;
+    static constexpr bool LEAVE_CKPT = (O & ROLL_LEAVE_CKPT) != 0, RESUME = (O & ROLL_RESUME) != 0;
+    static constexpr bool EY_FOLDED = (O & ROLL_EY_FOLDED) != 0, WHOLE_D = !(O & ROLL_PART_D);
+    static constexpr bool LEAN = roll_lean(O), BOUND = roll_bound(CAND, O);
+    static constexpr bool KEEP_PSI = Sink::kKeepsStates;        // psi feeds nothing back (search: dead code)
+    static constexpr int CKF = ck_fields(CAND);
+    static_assert(roll_supported(O), "ROLL_RESUME with ROLL_LEAVE_CKPT, or ROLL_STEP_TABLE without ROLL_STEER_TABLE");
+    static_assert(!STEPTAB || (CAND == CAND_LATTICE && !LEAVE_CKPT && !RESUME && !Sink::kKeepsStates),
+                  "the pool's table: search only, nothing resumes from or records (sin, cos)(beta)");
+};
+// the control increments of a generated candidate: (da, ddf) of the lattice (SURVEY 8d; oracle candidates_lattice), the
+// target OFFSETS from the base sequence of the ramp-hold and tracking families (igt_device.h cand_m, ramp_base; tracking: ddf is
+// the slip-angle offset of the steering feedback, track_steer)
+template <int CAND>
+__device__ __forceinline__ void cand_increments(const KP& P, const Scenario<double>& S, int cidx, double& da, double& ddf) {
+    if (CAND == CAND_LATTICE) {
+        const int i = cidx / P.G, j = cidx - i * P.G;
+        da = -P.rate_a + (2 * P.rate_a) * (double)i / (double)(P.G - 1);
+        ddf = steer_column<CAND>(P, S, j);
+    } else if (CAND == CAND_RAMP_HOLD || CAND == CAND_TRACK) {
+        const int i = cidx / P.G, j = cidx - i * P.G;
+        da = S.cpar[0] + cand_m(i, P.G, P.refine_it == 0) * S.cpar[2];
+        ddf = S.cpar[1] + cand_m(j, P.G, P.refine_it == 0) * S.cpar[3];
+    }
+}
+// The controls of step k from those of step k - 1 where they are a function of the candidate alone (lattice, ramp-hold, table;
+// no steering table): the replay of a resumed piece and StepControls.  The statements are step_head's, which keeps its own
+// (with the table reads, the table family's verdicts and the tracking family): routed through here, two kernels came out with
+// their instructions in another order (profiles/rollout_options_identity.txt).
+template <int CAND>
+__device__ __forceinline__ void control_step(const KP& P, const Scenario<double>& S, int k, int cidx, const double* __restrict__ table,
+                                             double da, double ddf, double& a, double& df) {
+    if (CAND == CAND_LATTICE) {
+        a = clampd(a + da, P.a_min, P.a_max);
+        df = steer_next<CAND>(P, S, k, ddf, df);
+    } else if (CAND == CAND_RAMP_HOLD) {
+        double ba, bdf;
+        ramp_base<double>(S.ws, P.N, k, S.a_prev, S.df_prev, ba, bdf);
+        const double ta = clampd(ba + da, P.a_min, P.a_max);
+        a = clampd(a + clampd(ta - a, -P.rate_a, P.rate_a), P.a_min, P.a_max);
+        df = steer_next<CAND>(P, S, k, ddf, df);
+    } else {
+        a = table[((size_t)cidx * 2 + 0) * P.N + k];
+        df = table[((size_t)cidx * 2 + 1) * P.N + k];
+    }
+}
+
 // The body of one control step k, in two pieces around the point where a search wave may leave early (rollout_one) and a
 // pooled lane retires a candidate that failed (rollout_pool): step_head -- checkpoint, controls of step k, slip trigonometry,
 // bookkeeping of state k and its verdicts, the incumbent bound -- returns whether the candidate is lost; step_tail -- the
 // collision check of state k, the rotation of the carried pairs, the sub-steps -- takes the lane to state k + 1.  Every
-// roll-out of the float64 path runs these statements, so whatever runs them gives the same bits.
-// LEAN: |ey|, box v and collision folded into the running maximum gmax (search).  stab: the lane's steering column of the
-// table (entry k at stab[k * stab_stride]); CAND_TABLE: the lane's control sequence (see the table branch).
-// STEPTAB (rollout_pool without checkpoint slots; lattice, STAB): the column is one of fill_pool_table's -- sblr comes from the
-// table, step_tail reads the rotation there, and (sin, cos)(beta_k), (sin, cos)(beta_k-1) are not carried by the lane at all.
-// EY_FOLDED (rollout_pool): |ey_k| - ey_lim is in gmax already -- the pool folds it where it decides whether the lane keeps its
-// candidate, at the end of step k - 1 (at the refill for state 0) -- and is not folded a second time here.
-template <int CAND, bool BOOK, bool LEAN, bool BOUND, bool STAB, int SEGMODE, bool STEPTAB = false, bool EY_FOLDED = false,
-          class FP, class Sink>
+// roll-out of the float64 path runs these statements, so whatever runs them gives the same bits.  Both halves of a step take
+// the same option word O (Roll<CAND, O, Sink> names what it switches on and derives LEAN, BOUND, KEEP_PSI, CKF).  stab: the
+// lane's steering column of the table (entry k at stab[k * stab_stride]); CAND_TABLE: the lane's control sequence (see the
+// table branch).  ROLL_STEP_TABLE: the column is one of fill_pool_table's -- sblr comes from the table, step_tail reads the
+// rotation there, and (sin, cos)(beta_k), (sin, cos)(beta_k-1) are not carried by the lane at all.  ROLL_EY_FOLDED: the pool
+// folds |ey_k| - ey_lim where it decides whether the lane keeps its candidate, at the end of step k - 1 (at the refill for
+// state 0); it is not folded a second time here.
+template <int CAND, unsigned O, class FP, class Sink>
 __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S, const FP& fp, LaneRoll<FP>& L, int k, int cidx,
                                           const double* __restrict__ table, const double* __restrict__ cinf, Sink& sink,
                                           const double* __restrict__ stab, int stab_stride, const unsigned long long* inc,
                                           double* ck, bool rows_judged, bool kv_d) {
-    constexpr int CKF = CAND == CAND_TRACK ? 8 : 5;            // fields this family writes
-    if (SEGMODE == 1 && k == L.ck_k) {          // node k: what a roll-out needs to resume here
-        double* c = ck + (size_t)(L.ck_q - 1) * CKF * 64;
+    typedef Roll<CAND, O, Sink> R;
+    constexpr bool BOOK = R::BOOK, LEAN = R::LEAN, STAB = R::STAB, STEPTAB = R::STEPTAB;
+    if (R::LEAVE_CKPT && k == L.ck_k) {          // node k: what a roll-out needs to resume here
+        double* c = ck + (size_t)(L.ck_q - 1) * R::CKF * 64;
         c[0] = L.s; c[64] = L.ey; c[128] = L.ep; c[192] = L.w.s1; c[256] = L.w.c1;
         if (CAND == CAND_TRACK) { c[320] = L.df; c[384] = L.sb_prev; c[448] = L.cb_prev; }
         ++L.ck_q;
@@ -501,8 +554,6 @@ __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S
     sink.ctrl(0, k, L.a, L.df);
     double sb, cb;                               // (sin, cos)(beta), beta = atan(r tan df)
     if (STEPTAB) {
-        static_assert(!STEPTAB || (STAB && CAND == CAND_LATTICE && SEGMODE == 0 && !Sink::kKeepsStates),
-                      "the pool's table: search only, nothing resumes from or records (sin, cos)(beta)");
         L.sblr = stab[k * stab_stride + 1];
     } else if (STAB && (CAND == CAND_LATTICE || CAND == CAND_RAMP_HOLD)) {
         sb = stab[k * stab_stride + 1];
@@ -532,7 +583,7 @@ __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S
         L.J = L.J + L.ep * L.ep;
         L.J = L.J + L.ey * L.ey;
         if (LEAN) {
-            if (!EY_FOLDED) L.gmax = fmax(L.gmax, fabs(L.ey) - P.ey_lim);                  // mpc.py:296-299
+            if (!R::EY_FOLDED) L.gmax = fmax(L.gmax, fabs(L.ey) - P.ey_lim);                  // mpc.py:296-299
             if (!rows_judged) L.gmax = fmax(L.gmax, fmax(P.v_min - L.v, L.v - P.v_max));   // mpc.py:316-317 (k < N)
         } else {
             if (fabs(L.ey) - P.ey_lim > P.tol) L.viol |= VIOL_EY;
@@ -544,7 +595,7 @@ __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S
     // unused on straight routes; with one scenario per lane the votes of substeps() read them on every lane
     // (a straight route's break-points are +inf: d = -inf, "clear")
     if (kv_d) { L.w.d0 = L.s - fp.b0; L.w.d1 = L.s - fp.b1; }
-    if (BOUND && inc) {
+    if (R::BOUND && inc) {
         // the incumbent is re-read every fourth step (a unit that started before its scenario's first unit finished picks it
         // up on the way); agent scope: the units of a scenario may run on different XCDs, whose L2s are not coherent
         if ((k & 3) == 0) {
@@ -555,11 +606,12 @@ __device__ __forceinline__ bool step_head(const KP& P, const Scenario<double>& S
     }
     return (L.viol != 0) | (LEAN && L.gmax > P.tol);
 }
-template <bool BOOK, bool LEAN, bool BOUND, bool UNIFORM, bool XY, bool KEEP_PSI, bool STEPTAB = false, bool WHOLE_D = true,
-          class FP, class Sink>
+template <int CAND, unsigned O, class FP, class Sink>
 __device__ __forceinline__ void step_tail(const KP& P, const Scenario<double>& S, const FP& fp, LaneRoll<FP>& L, int k, Sink& sink,
                                           const unsigned long long* inc, const double* __restrict__ stab = nullptr,
                                           int stab_stride = 0) {
+    typedef Roll<CAND, O, Sink> R;
+    constexpr bool BOOK = R::BOOK, LEAN = R::LEAN, XY = R::XY, STEPTAB = R::STEPTAB;
     if (BOOK && XY && k >= 1) {                                                  // collision, mpc.py:223-226
         for (int o = 0; o < P.n_obs; ++o) {
             const double dx = L.x - S.obs[(o * 2 + 0) * (P.N + 1) + k], dy = L.y - S.obs[(o * 2 + 1) * (P.N + 1) + k];
@@ -591,19 +643,20 @@ __device__ __forceinline__ void step_tail(const KP& P, const Scenario<double>& S
         if (!STEPTAB) { L.cb_prev = L.cb; L.sb_prev = L.sb; }
     }
     L.w.acc_s = 0.0; L.w.acc_ey = 0.0; L.w.acc_ep = 0.0; L.w.acc_x = 0.0; L.w.acc_y = 0.0; L.w.acc_psi = 0.0;
-    fp.template substeps<UNIFORM, XY, WHOLE_D>(L.a, L.sblr, L.w);
+    fp.template substeps<R::UNIFORM, XY, R::WHOLE_D>(L.a, L.sblr, L.w);
     L.s += L.w.acc_s; L.ey += L.w.acc_ey; L.ep += L.w.acc_ep;
     if (XY) { L.x += L.w.acc_x; L.y += L.w.acc_y; }
-    if (KEEP_PSI) L.psi += L.w.acc_psi;        // psi feeds nothing back (search: dead code)
-    if (BOUND && inc) L.rem -= L.seg_scale * fmax(fabs(L.v), fabs(fma(fp.dt, L.a, L.v)));      // this step's share of the bound is spent
+    if (R::KEEP_PSI) L.psi += L.w.acc_psi;
+    if (R::BOUND && inc) L.rem -= L.seg_scale * fmax(fabs(L.v), fabs(fma(fp.dt, L.a, L.v)));      // this step's share of the bound is spent
     L.v = fma(fp.dt, L.a, L.v);
     const double nxt[7] = {L.x, L.y, L.s, L.ey, L.ep, L.v, L.psi};
     sink.state(0, k + 1, nxt);
 }
 // the bookkeeping of state N, after the last control step
-template <bool LEAN, bool XY, class FP>
+template <unsigned O, class FP>
 __device__ __forceinline__ void horizon_end(const KP& P, const Scenario<double>& S, LaneRoll<FP>& L, double& Jout, unsigned& vout,
                                             double& sN, double& vN) {
+    constexpr bool LEAN = roll_lean(O), XY = !(O & ROLL_NO_XY);
     L.J = L.J + L.ep * L.ep;
     L.J = L.J + L.ey * L.ey;
     if (LEAN) L.gmax = fmax(L.gmax, fabs(L.ey) - P.ey_lim);
@@ -620,39 +673,24 @@ __device__ __forceinline__ void horizon_end(const KP& P, const Scenario<double>&
         L.viol |= VIOL_NONFINITE;
     sN = L.s; vN = L.v; Jout = L.J; vout = L.viol;
 }
-// the control increments of a generated candidate: (da, ddf) of the lattice (SURVEY 8d; oracle candidates_lattice), the
-// target OFFSETS from the base sequence of the ramp-hold and tracking families (igt_device.h cand_m, ramp_base; tracking: ddf is
-// the slip-angle offset of the steering feedback, track_steer)
-template <int CAND>
-__device__ __forceinline__ void cand_increments(const KP& P, const Scenario<double>& S, int cidx, double& da, double& ddf) {
-    if (CAND == CAND_LATTICE) {
-        const int i = cidx / P.G, j = cidx - i * P.G;
-        da = -P.rate_a + (2 * P.rate_a) * (double)i / (double)(P.G - 1);
-        ddf = steer_column<CAND>(P, S, j);
-    } else if (CAND == CAND_RAMP_HOLD || CAND == CAND_TRACK) {
-        const int i = cidx / P.G, j = cidx - i * P.G;
-        da = S.cpar[0] + cand_m(i, P.G, P.refine_it == 0) * S.cpar[2];
-        ddf = S.cpar[1] + cand_m(j, P.G, P.refine_it == 0) * S.cpar[3];
-    }
-}
 
-template <int CAND, bool HI_ORDER, bool BOOK, bool UNIFORM, class Sink, bool EARLY_EXIT = false, bool STAB = false, int NRK = 0,
-          bool XY = true, int SEGMODE = 0>
+// One candidate per lane over the horizon (ROLL_RESUME: over steps [seg_k0, seg_k1) from the record ck).  O: the build's
+// options, a role of igt_roll_options.h and what the call site adds to it.  The optional inputs stay positional scalars: as
+// one aggregate, by value or by reference, and behind forwarding functions that name them, they changed the order of some
+// kernels' instructions (profiles/rollout_options_identity.txt).
+template <int CAND, bool HI_ORDER, unsigned O, int NRK = 0, class Sink>
 __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>& S, int cidx,
                                             const double* __restrict__ table, const double* __restrict__ cinf,
                                             Sink& sink, double& Jout, unsigned& vout, double& sN, double& vN,
                                             const double* __restrict__ stab = nullptr, int stab_stride = 0,
                                             const unsigned long long* inc = nullptr, double* ck = nullptr, int seg_k0 = 0,
                                             int seg_k1 = 0, const double* __restrict__ rem_rows = nullptr) {
-    constexpr bool BOUND = CAND == CAND_TRACK && BOOK && UNIFORM && EARLY_EXIT;
+    typedef Roll<CAND, O, Sink> R;
+    constexpr bool BOOK = R::BOOK, UNIFORM = R::UNIFORM, EARLY_EXIT = R::EARLY_EXIT, XY = R::XY, RESUME = R::RESUME;
     // search on units of live acceleration rows (igt_kernels_f64.hip accel_rows_kernel; DEV_LAUNCH_LIVE_ROWS): the speed
     // box and the terminal set read the row's (a, v) recurrence alone and were judged there, with these statements -- every lane
     // that holds a candidate holds one of a row that passed: not judged again (74 half-planes per lane at the last step)
     const bool rows_judged = BOOK && EARLY_EXIT && UNIFORM && CAND != CAND_TABLE && (P.dev & DEV_LAUNCH_LIVE_ROWS) != 0;
-    constexpr bool KEEP_PSI = Sink::kKeepsStates;
-    // search only needs feasible-or-not: |ey|, box v and collision are folded into one running maximum, compared with
-    // the tolerance when it is read (x > tol for some x  <=>  max x > tol; a NaN operand is ignored by both forms)
-    constexpr bool LEAN = BOOK && EARLY_EXIT;
     typedef Fast64<HI_ORDER, NRK> FP;
     FP fp;
     fp.init(P, S.b0, S.b1, S.kv);
@@ -665,7 +703,7 @@ __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>&
     if (cidx < 0) cidx = 0;
     bool dead = false;
     cand_increments<CAND>(P, S, cidx, L.da, L.ddf);
-    if (SEGMODE != 2 || seg_k0 == 0) sink.state(0, 0, S.x0);
+    if (!RESUME || seg_k0 == 0) sink.state(0, 0, S.x0);
     L.w.d0 = L.w.d1 = 0.0;
     if (XY) sincos_reduced(S.x0[6], L.w.s2, L.w.c2);       // carried as (sin,cos)(psi + beta_k); beta_{-1} = 0
     else { L.w.s2 = 0.0; L.w.c2 = 1.0; }
@@ -676,27 +714,17 @@ __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>&
     L.trk_sb = 0.0; L.trk_cb = 1.0;
     L.trk_followed = false;
     int k_first = 0, k_last = P.N;
-    if (SEGMODE == 2) { k_first = seg_k0; k_last = seg_k1; }
-    if (SEGMODE == 2 && seg_k0 > 0) {
-        // resume at node seg_k0: the controls' own recurrences are replayed (the statements of step_head), the state that
-        // depends on the roll-out comes from the checkpoint
+    if (RESUME) { k_first = seg_k0; k_last = seg_k1; }
+    if (RESUME && seg_k0 > 0) {
+        // resume at node seg_k0: the controls' own recurrences are replayed, the state that depends on the roll-out comes from
+        // the checkpoint
         for (int k = 0; k < seg_k0; ++k) {
-            if (CAND == CAND_LATTICE) {
-                L.a = clampd(L.a + L.da, P.a_min, P.a_max);
-                L.df = steer_next<CAND>(P, S, k, L.ddf, L.df);
-            } else if (CAND == CAND_RAMP_HOLD || CAND == CAND_TRACK) {
+            if (CAND == CAND_TRACK) {                  // a only: the steering comes from the record
                 double ba, bdf;
                 ramp_base<double>(S.ws, P.N, k, S.a_prev, S.df_prev, ba, bdf);
-                if (CAND == CAND_TRACK) {
-                    L.a = track_accel_next(P, k, ba, L.da, L.v, L.a);
-                } else {
-                    const double ta = clampd(ba + L.da, P.a_min, P.a_max);
-                    L.a = clampd(L.a + clampd(ta - L.a, -P.rate_a, P.rate_a), P.a_min, P.a_max);
-                }
-                if (CAND == CAND_RAMP_HOLD) L.df = steer_next<CAND>(P, S, k, L.ddf, L.df);
+                L.a = track_accel_next(P, k, ba, L.da, L.v, L.a);
             } else {
-                L.a = table[((size_t)cidx * 2 + 0) * P.N + k];
-                L.df = table[((size_t)cidx * 2 + 1) * P.N + k];
+                control_step<CAND>(P, S, k, cidx, table, L.da, L.ddf, L.a, L.df);
             }
             L.v = fma(fp.dt, L.a, L.v);
         }
@@ -706,14 +734,14 @@ __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>&
     } else {
         sincos_reduced(S.x0[4], L.w.s1, L.w.c1);
     }
-    L.ck_q = 1; L.ck_k = (SEGMODE == 1 && ck) ? ckpt_step(P.N, 1) : -1;  // next checkpoint and its step (search; none without slots)
+    L.ck_q = 1; L.ck_k = (R::LEAVE_CKPT && ck) ? ckpt_step(P.N, 1) : -1;  // next checkpoint and its step (search; none without slots)
     // incumbent bound: rem = bound of the progress still to come (the row's own (a, v) recurrence rolled ahead, the statements of
     // the loop below), jcut = incumbent + a margin far above the rounding of LB_k (1e-9: the comparison is mathematically strict)
     L.rem = 0.0; L.jcut = (double)INFINITY; L.seg_scale = 0.0;
-    if (BOUND && inc) {
+    if (R::BOUND && inc) {
         L.seg_scale = progress_slack(P, S) * P.dt;
         if (L.seg_scale > 0.0) {
-            if (rem_rows) {          // the row's sum as accel_rows_kernel left it (the statements of the loop in the other branch)
+            if (rem_rows) {       // the row's sum as accel_rows_kernel left it (the statements of the loop in the other branch)
                 L.rem = rem_rows[cidx / P.G];
             } else {
                 double a2 = S.a_prev, v2 = S.x0[5];
@@ -734,20 +762,19 @@ __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>&
 
     const bool kv_d = !UNIFORM || fp.kv != 0.0;
     for (int k = k_first; k < k_last; ++k) {
-        const bool lost = step_head<CAND, BOOK, LEAN, BOUND, STAB, SEGMODE>(P, S, fp, L, k, cidx, table, cinf, sink, stab, stab_stride,
-                                                                            inc, ck, rows_judged, kv_d);
+        const bool lost = step_head<CAND, O>(P, S, fp, L, k, cidx, table, cinf, sink, stab, stab_stride, inc, ck, rows_judged, kv_d);
         if (BOOK && UNIFORM && EARLY_EXIT) {
             // search only: once every candidate of the slice has failed a verdict, nothing rolled further can win
             if (__all(lost) && !(P.dev & DEV_NO_EARLY_EXIT)) { dead = true; break; }
         }
-        step_tail<BOOK, LEAN, BOUND, UNIFORM, XY, KEEP_PSI>(P, S, fp, L, k, sink, inc);
+        step_tail<CAND, O>(P, S, fp, L, k, sink, inc);
     }
     if (dead) {            // costs are meaningless; "failed" is what is reported
-        Jout = 0.0; vout = L.viol | ((LEAN && L.gmax > P.tol) ? VIOL_EY : 0u); sN = 0.0; vN = 0.0;
+        Jout = 0.0; vout = L.viol | ((R::LEAN && L.gmax > P.tol) ? VIOL_EY : 0u); sN = 0.0; vN = 0.0;
         return;
     }
     if (BOOK) {
-        horizon_end<LEAN, XY>(P, S, L, Jout, vout, sN, vN);
+        horizon_end<O>(P, S, L, Jout, vout, sN, vN);
     } else {
         Jout = 0.0; vout = 0; sN = 0.0; vN = 0.0;
     }
@@ -774,17 +801,20 @@ __device__ __forceinline__ void rollout_one(const KP& P, const Scenario<double>&
 // wave lay out the window that starts at number `base` (igt_kernels_f64.hip search_pool64); it is called when the cursor first
 // reaches past the window (once per item when n <= POOL_TAB, i.e. C <= 256), with the values a refill used to compute on the
 // spot, so the same bits -- and a refill is a wave-uniform branch around a few LDS reads.
-// CKPT: with checkpoint slots (ck, rec: emit in pieces) over the three-double table of fill_steer_table; without them neither
-// is touched, nothing of the checkpoint cursor is carried, and the table is fill_pool_table's (step_head / step_tail STEPTAB).
+// O: ROLL_POOL and one of ROLL_LEAVE_CKPT -- checkpoint slots (ck, rec: emit in pieces) over the three-double table of
+// fill_steer_table -- and ROLL_STEP_TABLE -- neither is touched, nothing of the checkpoint cursor is carried, and the table is
+// fill_pool_table's; ROLL_NO_XY as the item decides.  Both halves of the step get this word.
 // The four-double table does not fit beside the slots in the 20 KB a wave may take (eight waves per compute unit).
 constexpr int POOL_START = 13, POOL_TAB = 256;
-template <int CAND, bool HI_ORDER, int NRK, bool XY, bool CKPT, class Fill>
+template <int CAND, bool HI_ORDER, int NRK, unsigned O, class Fill>
 __device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>& S, int n, const Fill& fill,
                                              const double* __restrict__ cinf, const double* __restrict__ stab, int stab_stride,
                                              double* ck, double* rec, double* start, unsigned* tabw, double* tabda,
                                              double& wJ, int& wC) {
     static_assert(CAND == CAND_LATTICE, "pool roll-out: the lattice family (its steering is a column of the table)");
-    constexpr int CKF = 5;
+    static_assert((O & ROLL_POOL) == ROLL_POOL && ((O & ROLL_LEAVE_CKPT) != 0) != ((O & ROLL_STEP_TABLE) != 0), "see above");
+    constexpr bool XY = !(O & ROLL_NO_XY), CKPT = (O & ROLL_LEAVE_CKPT) != 0;
+    constexpr int CKF = ck_fields(CAND);
     constexpr int SF = CKPT ? 3 : POOL_STAB_FIELDS;          // doubles per table entry
     typedef Fast64<HI_ORDER, NRK> FP;
     FP fp;
@@ -852,9 +882,9 @@ __device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>
         bool fin = false;
         double Jq = 0.0;
         if (hold) {
-            step_head<CAND, true, true, false, true, CKPT ? 1 : 0, !CKPT, true>(P, S, fp, L, k, c, nullptr, cinf, sink, lstab,
-                                                                                stab_stride, nullptr, ck, true, kv_d);
-            step_tail<true, true, false, true, XY, false, !CKPT, false>(P, S, fp, L, k, sink, nullptr, lstab, stab_stride);
+            const bool rows_judged = true;              // a pool is of live rows
+            step_head<CAND, O>(P, S, fp, L, k, c, nullptr, cinf, sink, lstab, stab_stride, nullptr, ck, rows_judged, kv_d);
+            step_tail<CAND, O>(P, S, fp, L, k, sink, nullptr, lstab, stab_stride);
             ++k;
             // state k is complete.  A candidate that fails its |ey| verdict, or failed the collision verdict of state k - 1
             // (step_tail), can never finish feasible -- gmax only grows -- and gives up its lane now, not after one more step.
@@ -867,7 +897,7 @@ __device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>
             } else if (k == P.N) {
                 double J, sN, vN;
                 unsigned viol;
-                horizon_end<true, XY>(P, S, L, J, viol, sN, vN);
+                horizon_end<O>(P, S, L, J, viol, sN, vN);
                 Jq = J - (sN - start[2]);                      // mpc.py:372 (start[2] = x0[2])
                 fin = viol == 0 && fabs(Jq) < 1.79e308;        // finite_d
                 hold = false;
@@ -954,29 +984,10 @@ struct StepControls {
     double a, df, da, ddf, lr_ratio;
     __device__ __forceinline__ StepControls(const KP& P_, const Scenario<double>& S_, int c, const double* t)
         : P(P_), S(S_), table(t), cidx(c), a(S_.a_prev), df(S_.df_prev), da(0.0), ddf(0.0), lr_ratio(P_.lr_ratio) {
-        const int i = cidx / P.G, j = cidx - i * P.G;
-        if (CAND == CAND_LATTICE) {
-            da = -P.rate_a + (2 * P.rate_a) * (double)i / (double)(P.G - 1);
-            ddf = steer_column<CAND>(P, S, j);
-        } else if (CAND == CAND_RAMP_HOLD) {
-            da = S.cpar[0] + cand_m(i, P.G, P.refine_it == 0) * S.cpar[2];
-            ddf = S.cpar[1] + cand_m(j, P.G, P.refine_it == 0) * S.cpar[3];
-        }
+        cand_increments<CAND>(P, S, cidx, da, ddf);
     }
     __device__ __forceinline__ void operator()(int k, double& a_out, double& sb, double& cb) {
-        if (CAND == CAND_LATTICE) {
-            a = clampd(a + da, P.a_min, P.a_max);
-            df = steer_next<CAND>(P, S, k, ddf, df);
-        } else if (CAND == CAND_RAMP_HOLD) {
-            double ba, bdf;
-            ramp_base<double>(S.ws, P.N, k, S.a_prev, S.df_prev, ba, bdf);
-            const double ta = clampd(ba + da, P.a_min, P.a_max);
-            a = clampd(a + clampd(ta - a, -P.rate_a, P.rate_a), P.a_min, P.a_max);
-            df = steer_next<CAND>(P, S, k, ddf, df);
-        } else {
-            a = table[((size_t)cidx * 2 + 0) * P.N + k];
-            df = table[((size_t)cidx * 2 + 1) * P.N + k];
-        }
+        control_step<CAND>(P, S, k, cidx, table, da, ddf, a, df);
         slip_trig<CAND>(P, lr_ratio, df, sb, cb);
         a_out = a;
     }

@@ -267,29 +267,33 @@ struct FastPair {
 // ---------------------------------------------------------------------------------------
 // CAND = CAND_LATTICE / CAND_RAMP_HOLD: both candidates share the steering profile (c and c+64 have the same j)
 // and satisfy the input box / rate limits by construction; CAND_TABLE: controls come from the table and are checked.
-// BOOK = false (emit): cost and verdicts are skipped, only the trajectory is produced.
-// CKPT (search, small batches): the state at N/4, N/2, 3N/4 is left in HBM for emit.  SEG (emit): only control steps
-// [seg.k0, seg.k1) are rolled, resuming from such a record.
-// XY = false (search only, decided per unit by obstacles_out_of_reach; never with CKPT): x, y are neither integrated nor judged.
-template <int CAND, bool HI_ORDER, bool BOOK, bool UNIFORM, typename T, class Sink, bool EARLY_EXIT = false,
-          bool CKPT = false, bool SEG = false, bool XY = true>
+// O: the options of igt_roll_options.h that have a meaning here.  Without ROLL_BOOK (emit) cost and verdicts are skipped, only
+// the trajectory is produced.  ROLL_LEAVE_CKPT (search, small batches): the state at N/4, N/2, 3N/4 is left in HBM for emit
+// (in.ck).  ROLL_RESUME (emit): only control steps [in.seg.k0, in.seg.k1) are rolled, resuming from such a record.
+// ROLL_NO_XY (search only, decided per unit by obstacles_out_of_reach; never with ROLL_LEAVE_CKPT): x, y are neither integrated
+// nor judged.
+template <int CAND, bool HI_ORDER, unsigned O, typename T, class Sink>
 __device__ __forceinline__ void rollout_pair(const KP& P, const Scenario<T>& S, const int (&cidx)[NV],
                                              const double* __restrict__ table,
                                              const double* __restrict__ cinf, Sink& sink, double (&Jout)[NV],
-                                             unsigned (&vout)[NV], double (&sN)[NV], double (&vN)[NV],
-                                             const Ckpt& ck = Ckpt{nullptr, 0, 0, 0, 0},
-                                             const Seg& seg = Seg{0, 0, nullptr, 0}, const unsigned long long* inc = nullptr) {
+                                             unsigned (&vout)[NV], double (&sN)[NV], double (&vN)[NV], const PairIn& in = PairIn()) {
+    static_assert(roll_supported(O) && !(O & (ROLL_STEER_TABLE | ROLL_STEP_TABLE | ROLL_EY_FOLDED | ROLL_PART_D)), "float64 only");
+    constexpr bool BOOK = (O & ROLL_BOOK) != 0, UNIFORM = (O & ROLL_UNIFORM) != 0, EARLY_EXIT = (O & ROLL_EARLY_EXIT) != 0;
+    constexpr bool CKPT = (O & ROLL_LEAVE_CKPT) != 0, SEG = (O & ROLL_RESUME) != 0, XY = !(O & ROLL_NO_XY);
+    const Ckpt& ck = in.ck;
+    const Seg& seg = in.seg;
+    const unsigned long long* inc = in.inc;
     constexpr bool KEEP_PSI = Sink::kKeepsStates || CKPT || SEG;
     // inc (search, tracking family, progress cost; may be null): the scenario's incumbent key -- a candidate whose lower bound
     // LB_k = J_k - (s_k - s_0) - rem_k exceeds it cannot win (igt_fast64.h rollout_one has the derivation; here the stage terms
     // are float sums, so the margin of the comparison is 1e-4 instead of 1e-9)
-    constexpr bool BOUND = CAND == CAND_TRACK && BOOK && UNIFORM && EARLY_EXIT && !SEG;
+    constexpr bool BOUND = roll_bound(CAND, O);
     constexpr bool LATTICE = CAND == CAND_LATTICE || CAND == CAND_RAMP_HOLD;   // generated, steering shared by the pair
     constexpr bool GENERATED = CAND != CAND_TABLE;                           // box / rate limits hold by construction
     // search only needs feasible-or-not: the float-side verdicts (|ey|, box v, collision) are folded into one running
     // maximum per candidate, compared with the tolerance when it is read (x > tol for some x  <=>  max x > tol; a NaN
     // operand is ignored by both forms).  Everything that reports verdict BITS keeps them.
-    constexpr bool LEAN = BOOK && EARLY_EXIT;
+    constexpr bool LEAN = roll_lean(O);
     float gmax[NV];
     typedef FastPair<HI_ORDER> FP;
     FP fp;

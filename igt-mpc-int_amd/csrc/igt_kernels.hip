@@ -175,19 +175,19 @@ __device__ __forceinline__ void search_unit(const KP& P, int W, int b, int p, do
     slice_candidates<CAND>(P, W, p, lane, cidx);
     double J[2], sN[2], vN[2];
     unsigned viol[2];
-    const Ckpt ck{CKPT && ck_parts > 1 ? ckpt : nullptr, (size_t)n_units, gw, lane, ck_parts > 1 ? P.N / ck_parts : 0};
+    PairIn in;
+    in.ck = Ckpt{CKPT && ck_parts > 1 ? ckpt : nullptr, (size_t)n_units, gw, lane, ck_parts > 1 ? P.N / ck_parts : 0};
     // the scenario's incumbent (tracking family, progress cost): behind the partials (PartJTail)
     unsigned long long* inc = (CAND == CAND_TRACK && !VALUE && (P.dev & DEV_LAUNCH_INCUMBENTS))
                                   ? PartJTail<float>(part_J, B, W, P.G).incumbents() + b
                                   : nullptr;
+    in.inc = inc;
     // units whose obstacles are out of every speed-feasible candidate's reach roll without the Cartesian rows (igt_device.h
     // obstacles_out_of_reach); the builds that leave checkpoints for emit need x, y
     if (!CKPT && !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<float>(P, S, lane))
-        rollout_pair<CAND, HI, true, true, float, NullSink, true, false, false, false>(P, S, cidx, table, cinf, sink, J, viol, sN, vN, ck,
-                                                                                       Seg{0, 0, nullptr, 0}, inc);
+        rollout_pair<CAND, HI, ROLL_SEARCH | ROLL_NO_XY>(P, S, cidx, table, cinf, sink, J, viol, sN, vN, in);
     else
-        rollout_pair<CAND, HI, true, true, float, NullSink, true, CKPT>(P, S, cidx, table, cinf, sink, J, viol, sN, vN, ck,
-                                                                        Seg{0, 0, nullptr, 0}, inc);
+        rollout_pair<CAND, HI, ROLL_SEARCH | (CKPT ? ROLL_LEAVE_CKPT : 0u)>(P, S, cidx, table, cinf, sink, J, viol, sN, vN, in);
     if (VALUE) {   // terminal value network (mpc.py:369): append the feasible candidates for the value kernels
         const bool dup = cidx[1] == cidx[0];                       // odd chunk count: second half is a duplicate
         const bool ok0 = viol[0] == 0 && finite_d(J[0]), ok1 = viol[1] == 0 && finite_d(J[1]) && !dup;
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(64) void emit_fast_kernel(KP P, int B, int W, const
     const int cidx[1] = {c};
     double J[1], sN[1], vN[1];
     unsigned viol[1];
-    single::rollout_pair<CAND, HI, false, false, float>(P, S, cidx, table, cinf, sink, J, viol, sN, vN);
+    single::rollout_pair<CAND, HI, ROLL_EMIT>(P, S, cidx, table, cinf, sink, J, viol, sN, vN);
 }
 
 // The same, from the search pass's checkpoints (small batches): `parts` lanes per scenario roll the pieces of the
@@ -363,13 +363,13 @@ __global__ __launch_bounds__(64) void emit_seg_kernel(KP P, int B, int W, int Wk
     candidate_slot<CAND>(P, Wk, c, p, slot);
     const int ns = P.N / parts;
     const size_t n_units = (size_t)B * Wk, unit = (size_t)b * Wk + p;
-    const Seg seg{g * ns, (g + 1) * ns, g > 0 ? ckpt + ((size_t)(g - 1) * n_units + unit) * SEG_UNIT_DOUBLES : nullptr, slot};
+    PairIn in;
+    in.seg = Seg{g * ns, (g + 1) * ns, g > 0 ? ckpt + ((size_t)(g - 1) * n_units + unit) * SEG_UNIT_DOUBLES : nullptr, slot};
     PairSink<float> sink{{xo, nullptr}, {uo, nullptr}, P.N};
     const int cidx[1] = {c};
     double J[1], sN[1], vN[1];
     unsigned viol[1];
-    single::rollout_pair<CAND, HI, false, false, float, PairSink<float>, false, false, true>(
-        P, S, cidx, table, cinf, sink, J, viol, sN, vN, Ckpt{nullptr, 0, 0, 0, 0}, seg);
+    single::rollout_pair<CAND, HI, ROLL_EMIT_PIECE>(P, S, cidx, table, cinf, sink, J, viol, sN, vN, in);
 }
 
 template <int CAND, bool HI>
@@ -399,7 +399,7 @@ __global__ __launch_bounds__(256) void rollout_all_fast_kernel(KP P, int B, cons
                              {U_all ? U_all + bc0 * 2 * P.N : nullptr, U_all ? U_all + bc1 * 2 * P.N : nullptr}, P.N};
         double J[2], sN[2], vN[2];
         unsigned viol[2];
-        rollout_pair<CAND, HI, true, true, float>(P, S, cidx, table, cinf, sink, J, viol, sN, vN);
+        rollout_pair<CAND, HI, ROLL_ALL>(P, S, cidx, table, cinf, sink, J, viol, sN, vN);
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const size_t bc = q ? bc1 : bc0;
@@ -633,7 +633,7 @@ __global__ __launch_bounds__(256) void frenet_step_fast_kernel(KP P, int n, cons
     const int cidx[2] = {0, 0};
     double J[2], sN[2], vN[2];
     unsigned viol[2];
-    rollout_pair<CAND_TABLE, HI, false, false, float>(P1, S, cidx, tab, nullptr, sink, J, viol, sN, vN);
+    rollout_pair<CAND_TABLE, HI, ROLL_EMIT>(P1, S, cidx, tab, nullptr, sink, J, viol, sN, vN);
 #pragma unroll
     for (int k = 0; k < 7; ++k) x_next[(size_t)i * 7 + k] = out[k * 2 + 1];
 }

@@ -334,11 +334,11 @@ __device__ __forceinline__ void search_unit64(const KP& P, int W, int b, int p, 
         if (L.kind >= 2 && steer_table_fits(P, W, CAND)) {
             __shared__ double stabc[f64::STAB_MAX_ENTRIES * 3];
             f64::fill_steer_table<CAND>(P, S, nj, r_first, lane, P.lr_ratio, stabc);
-            f64::rollout_one<CAND, HI, true, true, CaptureSink, true, true, NRK, true>(P, S, c, table, cinf, keep, J, viol, sN, vN,
-                                                                                       stabc + col * 3, nj * 3);
+            f64::rollout_one<CAND, HI, ROLL_SEARCH | ROLL_STEER_TABLE, NRK>(P, S, c, table, cinf, keep, J, viol, sN, vN, stabc + col * 3,
+                                                                            nj * 3);
             __syncthreads();
         } else {
-            f64::rollout_one<CAND, HI, true, true, CaptureSink, true, false, NRK, true>(P, S, c, table, cinf, keep, J, viol, sN, vN);
+            f64::rollout_one<CAND, HI, ROLL_SEARCH, NRK>(P, S, c, table, cinf, keep, J, viol, sN, vN);
         }
     } else {
     // steering slices of the families with state-independent steering: the slice's G/W steering columns are laid out in
@@ -346,25 +346,25 @@ __device__ __forceinline__ void search_unit64(const KP& P, int W, int b, int p, 
     // 70 % of the benchmark's scenarios: the other vehicle is out of reach over the whole horizon (or filter_preds moved it
     // away), so the unit rolls without the Cartesian rows -- a sixth of the control step's instructions
     const bool far = !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
-    // horizon checkpoints of every lane in LDS (igt_fast64.h SEGMODE 1); the unit winner's go to HBM below
-    constexpr int SM = VALUE ? 0 : 1;
-    constexpr int CKF = CAND == CAND_TRACK ? 8 : 5;
+    // horizon checkpoints of every lane in LDS (igt_fast64.h ROLL_LEAVE_CKPT); the unit winner's go to HBM below
+    constexpr unsigned UNIT = ROLL_SEARCH | (VALUE ? 0u : ROLL_LEAVE_CKPT);
+    constexpr int CKF = f64::ck_fields(CAND);
     __shared__ double ckl[VALUE ? 1 : (f64::CK_PARTS - 1) * CKF * 64];
     ck_lds = (!VALUE && ck_all) ? ckl + lane : nullptr;
     if (L.kind >= 2 && steer_table_fits(P, W, CAND)) {
         __shared__ double stab[f64::STAB_MAX_ENTRIES * 3];
         f64::fill_steer_table<CAND>(P, S, nj, r_first, lane, P.lr_ratio, stab);
         if (far)
-            f64::rollout_one<CAND, HI, true, true, NullSink, true, true, NRK, false, SM>(P, S, c, table, cinf, sink, J, viol, sN, vN,
-                                                                                         stab + col * 3, nj * 3, nullptr, ck_lds);
+            f64::rollout_one<CAND, HI, UNIT | ROLL_STEER_TABLE | ROLL_NO_XY, NRK>(P, S, c, table, cinf, sink, J, viol, sN, vN,
+                                                                                  stab + col * 3, nj * 3, nullptr, ck_lds);
         else
-            f64::rollout_one<CAND, HI, true, true, NullSink, true, true, NRK, true, SM>(P, S, c, table, cinf, sink, J, viol, sN, vN,
-                                                                                        stab + col * 3, nj * 3, nullptr, ck_lds);
+            f64::rollout_one<CAND, HI, UNIT | ROLL_STEER_TABLE, NRK>(P, S, c, table, cinf, sink, J, viol, sN, vN, stab + col * 3,
+                                                                     nj * 3, nullptr, ck_lds);
         __syncthreads();                                  // the next unit of this wave rewrites the table
     } else if (far) {
-        f64::rollout_one<CAND, HI, true, true, NullSink, true, false, NRK, false, SM>(P, S, c, table, cinf, sink, J, viol, sN, vN, nullptr, 0, inc, ck_lds, 0, 0, rem_rows);
+        f64::rollout_one<CAND, HI, UNIT | ROLL_NO_XY, NRK>(P, S, c, table, cinf, sink, J, viol, sN, vN, nullptr, 0, inc, ck_lds, 0, 0, rem_rows);
     } else {
-        f64::rollout_one<CAND, HI, true, true, NullSink, true, false, NRK, true, SM>(P, S, c, table, cinf, sink, J, viol, sN, vN, nullptr, 0, inc, ck_lds, 0, 0, rem_rows);
+        f64::rollout_one<CAND, HI, UNIT, NRK>(P, S, c, table, cinf, sink, J, viol, sN, vN, nullptr, 0, inc, ck_lds, 0, 0, rem_rows);
     }
     }
     if (VALUE) {   // terminal value network (mpc.py:369): append the feasible candidates for value_mfma_f64_kernel; the
@@ -394,7 +394,7 @@ __device__ __forceinline__ void search_unit64(const KP& P, int W, int b, int p, 
         if (take) { bestJ = oJ; bestC = oC; }
     }
     if (ck_lds && bestC >= 0 && c == bestC) {          // the unit winner's lane: its checkpoints -> HBM, record [q][field]
-        constexpr int CKF2 = CAND == CAND_TRACK ? 8 : 5;
+        constexpr int CKF2 = f64::ck_fields(CAND);
         double* g = ck_all + (size_t)(b * W + p) * CK_RECORD;
 #pragma unroll
         for (int q = 0; q < f64::CK_PARTS - 1; ++q)
@@ -442,7 +442,8 @@ __device__ __forceinline__ void search_pool64(const KP& P, int W, int b, const d
     const int lane = threadIdx.x & 63;
     const UnitLayout L = unit_layout(P, W, CAND, row_mask[b]);
     const int R = __builtin_amdgcn_readfirstlane(L.R), n = P.G * R;
-    constexpr int CKF = 5;
+    constexpr int CKF = f64::ck_fields(CAND);
+    constexpr unsigned POOL = ROLL_POOL | (CKPT ? ROLL_LEAVE_CKPT : ROLL_STEP_TABLE);
     __shared__ int rank2row[64];
     // CKPT (DEV_LAUNCH_CKPT: emit in pieces): checkpoint slots and the three-double table; else no slots and the pool's table
     __shared__ double stab[f64::STAB_MAX_ENTRIES * (CKPT ? 3 : f64::POOL_STAB_FIELDS)];
@@ -480,8 +481,8 @@ __device__ __forceinline__ void search_pool64(const KP& P, int W, int b, const d
         const bool far = !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
         double* ck = (CKPT && ck_all) ? ckl + lane : nullptr;
         const int stride = P.G * (CKPT ? 3 : f64::POOL_STAB_FIELDS);
-        if (far) f64::rollout_pool<CAND, HI, NRK, false, CKPT>(P, S, n, fill, cinf, stab, stride, ck, rec, start, tabw, tabda, wJ, wC);
-        else f64::rollout_pool<CAND, HI, NRK, true, CKPT>(P, S, n, fill, cinf, stab, stride, ck, rec, start, tabw, tabda, wJ, wC);
+        if (far) f64::rollout_pool<CAND, HI, NRK, POOL | ROLL_NO_XY>(P, S, n, fill, cinf, stab, stride, ck, rec, start, tabw, tabda, wJ, wC);
+        else f64::rollout_pool<CAND, HI, NRK, POOL>(P, S, n, fill, cinf, stab, stride, ck, rec, start, tabw, tabda, wJ, wC);
         __syncthreads();                                  // rec is complete; the next item of this wave rewrites the tables
     }
     if (lane < W) {
@@ -606,14 +607,14 @@ __global__ __launch_bounds__(64) void emit_f64_kernel(KP P, int B, int W, const 
     StoreSink<double> sink{xo, uo, P.N};
     double J, sN, vN;
     unsigned viol;
-    f64::rollout_one<CAND, HI, false, false, StoreSink<double>, false, false, NRK>(P, S, c, table, cinf, sink, J, viol, sN, vN);
+    f64::rollout_one<CAND, HI, ROLL_EMIT, NRK>(P, S, c, table, cinf, sink, J, viol, sN, vN);
 }
 
 // ---- emit in pieces (batches that do not keep trajectories; progress cost) ----
 // One roll-out is a serial chain, and a wave issues a float64 instruction every four cycles however few of its lanes are
 // active: emit_f64_kernel's 64 waves at B = 4096 take one roll-out of time, 51 us.  Here a workgroup of four waves owns S
 // scenarios (lane = scenario): wave w rolls steps [w N / 4, (w + 1) N / 4) of each winner's Frenet rows from the checkpoint the
-// search pass left (igt_fast64.h SEGMODE 2) into LDS -- states, controls and (sin, cos)(beta_k) -- , then the first wave rolls the
+// search pass left (igt_fast64.h ROLL_RESUME) into LDS -- states, controls and (sin, cos)(beta_k) -- , then the first wave rolls the
 // Cartesian rows x, y, psi from those controls (cartesian_rows), and the workgroup writes its scenarios' x*[7, N+1] and u*[2, N]
 // out of LDS as they lie in HBM: contiguous, every store of a wave a full line (emit_f64_kernel: one lane per scenario,
 // 64 lines touched per store instruction, 2.6x the bytes at B = 65 536).  The same statements on the same numbers as the
@@ -682,8 +683,7 @@ __global__ __launch_bounds__(SEG_THREADS) void emit_seg_f64_kernel(KP P, int B, 
             double* ck = wave > 0 ? ck_all + ((size_t)b * W + pw) * CK_RECORD + (size_t)(wave - 1) * f64::CK_FIELDS : nullptr;
             double J, sN, vN;
             unsigned viol;
-            f64::rollout_one<CAND, HI, false, false, SegSink, false, false, NRK, false, 2>(P, Sc, c, table, cinf, sink, J, viol, sN, vN,
-                                                                                           nullptr, 0, nullptr, ck, k0, k1);
+            f64::rollout_one<CAND, HI, ROLL_EMIT_PIECE | ROLL_NO_XY, NRK>(P, Sc, c, table, cinf, sink, J, viol, sN, vN, nullptr, 0, nullptr, ck, k0, k1);
         } else if (CAND != CAND_TRACK) {      // beside the pieces: the Cartesian rows, the controls generated on the spot
             f64::StepControls<CAND> ctl(P, Sc, c, table);
             f64::cartesian_rows<HI, NRK>(P, Sc.x0[0], Sc.x0[1], Sc.x0[6], Sc.x0[5], ctl, blk, blk + N1, blk + 6 * N1, 1);
@@ -717,7 +717,7 @@ __global__ __launch_bounds__(SEG_THREADS) void emit_seg_f64_kernel(KP P, int B, 
 // for N <= 32, two up to IGT_MAX_N), then the line search (trial m on lane m: u + 2^(-m/3) d, clamped step by step to the rate
 // window around the clamped step before it and to the input box).  Every lane's control sequence lies in LDS, [2 N][64]: the 64
 // lanes' reads of step k are 64 consecutive doubles, no two on one bank in a pass.  The roll-out is rollout_one itself on the
-// table family with the lane's LDS column as its table (step_head, STAB): the statements of search, emit and rollout-all, so
+// table family with the lane's LDS column as its table (ROLL_STEER_TABLE): the statements of search, emit and rollout-all, so
 // cost and verdicts of a trial are the bits igt_rollout_batch_f64 gives for the same controls, and since all lanes belong to one
 // scenario the sub-step variants are voted as in a search unit.  Scenarios whose obstacles are out of reach roll the trips
 // without the Cartesian rows (obstacles_out_of_reach).  A plan that changed is rolled once more with all rows into LDS and
@@ -820,8 +820,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             }
             double J, sN, vN;
             unsigned viol;
-            if (far) f64::rollout_one<CAND_TABLE, HI, true, true, NullSink, false, true, NRK, false>(P, S, 0, nullptr, cinf, none, J, viol, sN, vN, slot + lane, 64);
-            else f64::rollout_one<CAND_TABLE, HI, true, true, NullSink, false, true, NRK, true>(P, S, 0, nullptr, cinf, none, J, viol, sN, vN, slot + lane, 64);
+            if (far) f64::rollout_one<CAND_TABLE, HI, ROLL_POLISH | ROLL_NO_XY, NRK>(P, S, 0, nullptr, cinf, none, J, viol, sN, vN, slot + lane, 64);
+            else f64::rollout_one<CAND_TABLE, HI, ROLL_POLISH, NRK>(P, S, 0, nullptr, cinf, none, J, viol, sN, vN, slot + lane, 64);
             const double Jq = J - (sN - S.x0[2]);         // mpc.py:372
             if (!search) {
                 const int c = trip * 64 + lane;
@@ -849,7 +849,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             StoreSink<double> keep{lane == bestM ? xl : nullptr, nullptr, N};
             double J, sN, vN;
             unsigned viol;
-            f64::rollout_one<CAND_TABLE, HI, true, true, StoreSink<double>, false, true, NRK, true>(P, S, 0, nullptr, cinf, keep, J, viol, sN, vN, slot + lane, 64);
+            f64::rollout_one<CAND_TABLE, HI, ROLL_POLISH, NRK>(P, S, 0, nullptr, cinf, keep, J, viol, sN, vN, slot + lane, 64);
             J0 = __shfl(J - (sN - S.x0[2]), bestM, 64);
             __syncthreads();
         }
@@ -867,7 +867,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     StoreSink<double> keep{lane == 0 ? xl : nullptr, nullptr, N};
     double J, sN, vN;
     unsigned viol;
-    f64::rollout_one<CAND_TABLE, HI, true, true, StoreSink<double>, false, true, NRK, true>(P, S, 0, nullptr, cinf, keep, J, viol, sN, vN, slot + lane, 64);
+    f64::rollout_one<CAND_TABLE, HI, ROLL_POLISH, NRK>(P, S, 0, nullptr, cinf, keep, J, viol, sN, vN, slot + lane, 64);
     __syncthreads();
     const int nx = 7 * (N + 1);
     for (int i = lane; i < nx; i += 64) x_out[(size_t)b * nx + i] = xl[i];
@@ -984,7 +984,7 @@ __global__ __launch_bounds__(256) void rollout_all_f64_kernel(KP P, int B, const
         StoreSink<double> sink{X_all ? X_all + bc * 7 * (P.N + 1) : nullptr, U_all ? U_all + bc * 2 * P.N : nullptr, P.N};
         double J, sN, vN;
         unsigned viol;
-        f64::rollout_one<CAND, HI, true, true, StoreSink<double>>(P, S, c, table, cinf, sink, J, viol, sN, vN);
+        f64::rollout_one<CAND, HI, ROLL_ALL>(P, S, c, table, cinf, sink, J, viol, sN, vN);
         if (rec_J) {   // value-net cost: value_kernel adds the terminal term and fills cost_all / viol_all
             rec_sN[bc] = sN; rec_vN[bc] = vN; rec_J[bc] = J; rec_viol[bc] = viol;
             continue;
@@ -1039,7 +1039,7 @@ __global__ __launch_bounds__(64 * LIT_WAVES) void search_literal_f64_kernel(
             LdsSink sink{X, U, P.N};
             double J, sN, vN;
             unsigned viol;
-            f64::rollout_one<CAND, HI, false, true, LdsSink>(P, S, c, table, cinf, sink, J, viol, sN, vN);
+            f64::rollout_one<CAND, HI, ROLL_LITERAL>(P, S, c, table, cinf, sink, J, viol, sN, vN);
         }
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");

@@ -16,13 +16,16 @@ What needs a larger batch keeps its tests: the (HI = false, NRK = 4) builds of _
 and emit_seg_f64_kernel: test_gpu_parity.py::test_emit_in_pieces_is_the_emit_in_one_piece (B = 700 to 8200, with and without
 DEV_NO_SEG_EMIT) and test_search_and_emit_agree_bitwise[2304-*-f64]; the pool search and the live rows: test_gpu_pool_loop.py,
 test_gpu_pool_step.py, test_gpu_lane_refill.py; the float search without checkpoints: test_search_and_emit_agree_bitwise at
-B = 2304 and 9000."""
+B = 2304 and 9000.  The roll-out's call sites (csrc/igt_fast64.h rollout_one / rollout_pool, csrc/igt_fast_impl.inc
+rollout_pair) and the tests that reach each are listed in profiles/rollout_options_identity.txt; the one that none of them
+reached, the literal wave-per-trajectory mapping of the developer library, has its case at the end of this file."""
 import numpy as np
 import pytest
 
 import np_oracle as O
 import parity_cases as PC
 from helpers import oracle_params, rel_err
+from igtmpc._lib import DEV_LITERAL
 
 pytestmark = pytest.mark.gpu
 
@@ -104,3 +107,36 @@ def test_polished_solve_is_its_table_rollout_bitwise_and_the_oracles(igt, grad, 
     print(f'polish {grad} n_rk4={n_rk4}: max rel err x {ex:.2e} cost {ej:.2e}; worst margin {g.max():.3e}')
     assert ex <= 1e-9 and ej <= 1e-9
     assert (mask == 0).all()
+
+
+@pytest.mark.parametrize('cand,n_rk4', [(c, 4) for c in PC.LEAF_FAMILIES] + [('lattice', 3)])
+def test_literal_mapping_picks_rollout_alls_minimum(igt, monkeypatch, cand, n_rk4):
+    """search_literal_f64_kernel (libigtmpc_dev.so, IGT_DEV_FLAGS = DEV_LITERAL): lane 0 of a wave rolls the candidate through
+    rollout_one without cost or verdicts, and the wave sums the stage terms of the stored states in another order than the
+    roll-out does (stage-parallel, then a butterfly), so its cost is rollout-all's only to rounding and the bit-for-bit
+    invariant of this file holds for what emit_f64_kernel re-rolls, not for the cost.  Asserted: the same scenarios solved;
+    (x, u) are rollout-all's entry at the arg-min, bit for bit; the cost is rollout-all's at the arg-min, and the arg-min's
+    cost rollout-all's feasible minimum, within the bound of two summations of the same n = 3 N + 2 non-negative terms in any
+    order, 2 (n - 1) 2^-53 times their sum (= cost + progress), plus the rounding of the final subtraction: 64 2^-53 (|cost| +
+    2 |progress|) at N = 8.  n_rk4 = 3: the long polynomials (HI)."""
+    case = PC.leaf_case('f64', cand, n_rk4)
+    monkeypatch.setenv('IGT_DEV_FLAGS', str(DEV_LITERAL))
+    with PC.open_solver(igt, case) as s:
+        got = PC.device_solve(s, case)
+        pos, _ = PC.solve_args(case)
+        allc = s.rollout_all(*pos[:5])
+    J = np.where(allc['viol'] == 0, allc['cost'].astype(np.float64), np.inf)
+    assert 0 < np.isfinite(J.min(axis=1)).sum() < case['B']
+    for i in range(case['B']):
+        if not np.isfinite(J[i].min()):
+            assert got['status'][i] == 1 and got['argmin'][i] == -1
+            continue
+        c = int(got['argmin'][i])
+        assert got['status'][i] == 0 and c >= 0 and allc['viol'][i, c] == 0, (i, c)
+        assert np.array_equal(got['x'][i], allc['X'][i, c]) and np.array_equal(got['u'][i], allc['U'][i, c])
+        ds = allc['X'][i, c, 2, -1] - allc['X'][i, c, 2, 0]
+        bound = 64 * 2.0 ** -53 * (abs(J[i, c]) + 2 * abs(ds))
+        print(f'literal {cand} n_rk4={n_rk4} scenario {i}: |cost - rollout-all| {abs(got["cost"][i] - J[i, c]):.2e}, '
+              f'above the minimum {J[i, c] - J[i].min():.2e}, bound {bound:.2e}')
+        assert abs(got['cost'][i] - J[i, c]) <= bound
+        assert J[i, c] - J[i].min() <= 2 * bound
