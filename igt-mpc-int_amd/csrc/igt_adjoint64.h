@@ -1,6 +1,7 @@
 // igt_adjoint64.h -- the derivative of one control step of the RK4 Frenet model, float64 (gfx950): what the cost gradient
 // (igt_kernels_f64.hip cost_gradient_f64_kernel, igt_cost_gradient_f64) and the adjoint mode of the polish (polish_f64_kernel,
-// igt_set_polish_gradient) are made of.
+// igt_set_polish_gradient) are made of; at the end of the file the Riccati and forward steps of the polish's Newton direction
+// (igt_set_polish_step) over the same Jacobians.
 //
 // The progress cost (mpc.py:356-373) reads (s, ey, epsi) and the inputs only, so the Cartesian rows are left out; s feeds back
 // through the piecewise-constant K(s) alone, which is taken as locally constant -- the derivative wherever no RK stage argument
@@ -158,6 +159,111 @@ __device__ __forceinline__ void costate_step(const double (&T)[3][5], double dt,
     lam[1] = fma(2.0, ey, c[0]);
     lam[2] = fma(2.0, ep, c[1]);
     lam[3] = lam[3] + c[2];
+}
+
+// ---- the Newton (LQ) direction of the polish (igt_set_polish_step IGT_POLISH_STEP_NEWTON) ----
+// The Gauss-Newton model of the progress cost around the plan, over z = (ey, epsi, v): A_k = rows (ey, epsi) of T_k, columns
+// 0..2, over (0, 0, 1); B_k = the same rows, columns 3..4, over (dt, 0); Q = diag(2, 2, 0), R = 2 w_u I.  The s row of T_k
+// enters the linear terms only (the costate of s is -1 throughout): q_k = (2 ey_k, 2 epsi_k, 0) - T_k[0][0..2],
+// r_k = 2 w_u u_k - T_k[0][3..4].  The cost is a sum of squares plus a linear term, so the model is exact in the cost; only
+// the curvature of the dynamics is dropped.  The unit row of A_k and the (dt, 0) row of B_k are written as what they are.
+struct Riccati {
+    double P[3][3], p[3];      // the quadratic and linear terms of the cost-to-go at node k + 1, then at node k
+    bool ok;                   // every determinant so far was finite and > 0
+
+    __device__ __forceinline__ void init(double eyN, double epN) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) P[i][j] = (i == j && i < 2) ? 2.0 : 0.0;
+        p[0] = 2.0 * eyN; p[1] = 2.0 * epN; p[2] = 0.0;
+        ok = true;
+    }
+
+    // one step back: Quu = R + B'PB, Qux = B'PA, Qu = r + B'p, K = -Quu^-1 Qux, kap = -Quu^-1 Qu (the 2 x 2 inverse by the
+    // determinant), P <- Q + A'PA + Qux'K, p <- q + A'p + Qux'kap.  P is symmetric and kept so: Quu's and the new P's upper
+    // triangles are formed and mirrored (the symmetrisation), which is also a third of the multiply-adds less.
+    __device__ __forceinline__ void step(const double (&T)[3][5], double dt, double w_u, double ey, double ep, double a, double df,
+                                         double (&K)[2][3], double (&kap)[2]) {
+        double W[3][3], PB[3][2];                                // P A, P B
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                W[i][j] = fma(P[i][1], T[2][j], P[i][0] * T[1][j]);
+                if (j == 2) W[i][j] += P[i][2];
+            }
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                PB[i][c] = fma(P[i][1], T[2][3 + c], P[i][0] * T[1][3 + c]);
+                if (c == 0) PB[i][c] = fma(P[i][2], dt, PB[i][c]);
+            }
+        }
+        double Quu[2][2], Qux[2][3], Qu[2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+#pragma unroll
+            for (int d = c; d < 2; ++d) {
+                Quu[c][d] = fma(T[2][3 + c], PB[1][d], T[1][3 + c] * PB[0][d]);
+                if (c == 0) Quu[c][d] = fma(dt, PB[2][d], Quu[c][d]);
+                if (c == d) Quu[c][d] += 2.0 * w_u;
+            }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                Qux[c][j] = fma(T[2][3 + c], W[1][j], T[1][3 + c] * W[0][j]);
+                if (c == 0) Qux[c][j] = fma(dt, W[2][j], Qux[c][j]);
+            }
+            Qu[c] = fma(T[2][3 + c], p[1], T[1][3 + c] * p[0]);
+            if (c == 0) Qu[c] = fma(dt, p[2], Qu[c]);
+            Qu[c] += fma(2.0 * w_u, c == 0 ? a : df, -T[0][3 + c]);
+        }
+        const double det = fma(Quu[0][0], Quu[1][1], -(Quu[0][1] * Quu[0][1]));
+        ok = ok && fabs(det) < 1.79e308 && det > 0.0;
+        const double nid = -rcp_nr(det);                         // -Quu^-1 = nid (Quu11, -Quu01; -Quu01, Quu00)
+        const double I00 = Quu[1][1] * nid, I01 = -(Quu[0][1] * nid), I11 = Quu[0][0] * nid;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            K[0][j] = fma(I01, Qux[1][j], I00 * Qux[0][j]);
+            K[1][j] = fma(I11, Qux[1][j], I01 * Qux[0][j]);
+        }
+        kap[0] = fma(I01, Qu[1], I00 * Qu[0]);
+        kap[1] = fma(I11, Qu[1], I01 * Qu[0]);
+        double pn[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            double v = fma(T[2][i], p[1], T[1][i] * p[0]);                           // A'p
+            if (i == 2) v += p[2];
+            v = fma(Qux[1][i], kap[1], fma(Qux[0][i], kap[0], v));
+            pn[i] = v + (i == 0 ? fma(2.0, ey, -T[0][0]) : i == 1 ? fma(2.0, ep, -T[0][1]) : -T[0][2]);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = i; j < 3; ++j) {
+                double v = fma(T[2][i], W[1][j], T[1][i] * W[0][j]);                 // A'PA
+                if (i == 2) v += W[2][j];
+                v = fma(Qux[1][i], K[1][j], fma(Qux[0][i], K[0][j], v));
+                if (i == j && i < 2) v += 2.0;
+                P[i][j] = v;                                                         // W, PB hold what is needed of the old P
+                P[j][i] = v;
+            }
+            p[i] = pn[i];
+        }
+    }
+};
+
+// The forward sweep's step: d = kap_k + K_k dz (steer false: the steering entry is 0), dz <- A_k dz + B_k d.  T: rows 1, 2 are read.
+__device__ __forceinline__ void newton_forward_step(const double (&T)[3][5], double dt, const double (&K)[2][3], const double (&kap)[2],
+                                                    bool steer, double (&dz)[3], double (&d)[2]) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) d[c] = fma(K[c][2], dz[2], fma(K[c][1], dz[1], fma(K[c][0], dz[0], kap[c])));
+    if (!steer) d[1] = 0.0;
+    double nz[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+        nz[i] = fma(T[1 + i][4], d[1], fma(T[1 + i][3], d[0], fma(T[1 + i][2], dz[2], fma(T[1 + i][1], dz[1], T[1 + i][0] * dz[0]))));
+    dz[0] = nz[0]; dz[1] = nz[1];
+    dz[2] = fma(dt, d[0], dz[2]);
 }
 
 }  // namespace adj

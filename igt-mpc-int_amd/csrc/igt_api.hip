@@ -61,6 +61,7 @@ struct igt_handle {
     int n_cu = 256;                // compute units of the device (sizes the persistent search grid)
     int concurrency = 1;           // solves the caller keeps in flight on the device (igt_set_concurrency)
     int polish_grad = IGT_GRAD_FORWARD_DIFF;      // or IGT_GRAD_ADJOINT (igt_set_polish_gradient)
+    int polish_step = IGT_POLISH_STEP_GRADIENT;   // or IGT_POLISH_STEP_NEWTON (igt_set_polish_step)
     void* comm = nullptr;          // RCCL communicator of igt_comm_init (null: none)
     int comm_world = 1, comm_rank = 0;
     int32_t comm_B_local = 0;      // shard size of the communicator's first all-gather (0 = none yet); later calls must match
@@ -512,7 +513,8 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     if (h->prof) HIPCHK(hipEventRecord(h->ev[1], st));
     HIPCHK(igt::launch_emit<T>(kp, B, (int)W, A, st));
     if constexpr (sizeof(T) == 8) {      // the winners, polished in place in the outputs (igt_kernels_f64.hip polish_f64_kernel)
-        if (p.polish_iters > 0) HIPCHK(igt::launch_polish(kp, B, p.polish_iters, h->polish_grad == IGT_GRAD_ADJOINT, A, st));
+        if (p.polish_iters > 0) HIPCHK(igt::launch_polish(kp, B, p.polish_iters, h->polish_grad == IGT_GRAD_ADJOINT,
+                                                       h->polish_step == IGT_POLISH_STEP_NEWTON, A, st));
     }
     if (h->prof) { HIPCHK(hipEventRecord(h->ev[2], st)); h->ev_recorded = true; }
 
@@ -1203,6 +1205,14 @@ int igt_set_polish_gradient(igt_handle* h, int mode) {
     if (mode != IGT_GRAD_FORWARD_DIFF && mode != IGT_GRAD_ADJOINT)
         return fail(IGT_E_INVALID, "mode must be IGT_GRAD_FORWARD_DIFF or IGT_GRAD_ADJOINT");
     h->polish_grad = mode;
+    return IGT_OK;
+}
+
+int igt_set_polish_step(igt_handle* h, int mode) {
+    if (mode != IGT_POLISH_STEP_GRADIENT && mode != IGT_POLISH_STEP_NEWTON)
+        return fail(IGT_E_INVALID, "mode must be IGT_POLISH_STEP_GRADIENT or IGT_POLISH_STEP_NEWTON");
+    if (!h) return fail(IGT_E_INVALID, "null handle (igt_set_polish_step: IGT_POLISH_STEP_GRADIENT or IGT_POLISH_STEP_NEWTON)");
+    h->polish_step = mode;
     return IGT_OK;
 }
 

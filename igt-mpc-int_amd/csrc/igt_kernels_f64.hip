@@ -5,7 +5,7 @@
 //   emit_f64_kernel       one lane per scenario: the winner re-rolled with the same arithmetic -> x*[7,N+1], u*[2,N]
 //   emit_gather_f64_kernel   small batches: the winner's trajectory copied out of the unit that rolled it
 //   rollout_all_f64_kernel   debug / parity: every candidate's trajectory, cost and verdict bits
-//   polish_f64_kernel     projected-gradient steps on the winner (forward-difference or adjoint gradient)
+//   polish_f64_kernel     projected-gradient steps on the winner (forward-difference or adjoint gradient; Newton direction)
 //   cost_gradient_f64_kernel   dJ/du of the progress cost for one control sequence per scenario (igt_adjoint64.h); templated on the
 //                         terminal term: the two sweeps of igt_cost_gradient_vn_f64 around the value network are instantiations
 //   search_kernel / emit_kernel / rollout_all_kernel<ExactStepper<double>>   the oracle's operation order (IGT_DEV_FLAGS=1024)
@@ -732,9 +732,21 @@ __global__ __launch_bounds__(SEG_THREADS) void emit_seg_f64_kernel(KP P, int B, 
 // write-back -- the roll the forward-difference mode does once at the end, moved into the loop (the sub-step variants the
 // wave votes for are bit-identical where they apply, so the states are those of the plan rolled alone).  An iteration is a
 // Jacobian pass, a trial trip and an accepted-plan roll against g_trips + 1 trips; the LDS is polish_lds_doubles(N) either way.
+// NEWTON (igt_set_polish_step IGT_POLISH_STEP_NEWTON; an ADJ build): lane k leaves step k's Jacobian, node values and inputs in
+// one record of the slot region, [N][NEWTON_REC]; every lane then runs the costate recursion and the Riccati sweep of the
+// Gauss-Newton model (igt_adjoint64.h Riccati) in one backward loop over the records, broadcast reads again, lane 0 keeps g and
+// leaves the gains K_k (6) and kappa_k (2) in the record.  The forward sweep dz_0 = 0, dN_k = kappa_k + K_k dz_k,
+// dz_k+1 = A_k dz_k + B_k dN_k then leaves dN [2 N] behind xl -- the 2 N doubles this build's LDS grows by
+// (polish_newton_lds_doubles) --, non-finite entries 0, all of it 0 if a determinant was non-finite or <= 0, the steering row 0
+// when the steering rate is.  Both sweeps are a phase of their own, done before the trials are laid out: nothing of them lives
+// across rollout_one.  Trials: lane m < 32 takes u + 2^(-m/3) dN (not rescaled: trial 0 is the full Newton step), lane m >= 32
+// takes u + 2^(-(m-32)/3) d with d the scaled -g of the gradient modes; projection, verdicts, butterfly, acceptance and the
+// accepted plan's roll are the statements above.
 constexpr double POLISH_EPS = 1e-4;
 __host__ __device__ inline size_t polish_lds_doubles(int N) { return (size_t)2 * N * 64 + 4 * N + 7 * (N + 1); }
-template <bool HI, int NRK, bool ADJ = false>
+__host__ __device__ inline size_t polish_newton_lds_doubles(int N) { return polish_lds_doubles(N) + 2 * N; }
+constexpr int NEWTON_REC = 28;                        // doubles per step in the Newton build's records (16-byte aligned)
+template <bool HI, int NRK, bool ADJ = false, bool NEWTON = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void polish_f64_kernel(
         KP P, int B, int iters, const double* __restrict__ x0, const double* __restrict__ u_prev, const double* __restrict__ kparams,
         const uint32_t* __restrict__ flags, const double* __restrict__ obs, const double* __restrict__ cinf,
@@ -747,6 +759,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     double* u = slot + (size_t)n2 * 64;                   // [2 N] the plan so far
     double* g = u + n2;                                   // [2 N] gradient, then direction
     double* xl = g + n2;                                  // [7][N + 1] the final plan's states
+    static_assert(ADJ || !NEWTON, "the Newton step is built on the adjoint build");
     Scenario<double> S;
     load_scenario<double>(S, P, b, x0, u_prev, kparams, flags, obs);
     const bool far = !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
@@ -769,23 +782,90 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             if (lane < N) {                               // (A_k, B_k) of step k = lane, [15][N] in the slot region
                 double T[3][5];
                 adj::step_jacobian(M, xl[2 * N1 + lane], xl[3 * N1 + lane], xl[4 * N1 + lane], xl[5 * N1 + lane], u[lane], u[N + lane], T);
+                if (NEWTON) {                             // ... NEWTON: step k's record, [N][NEWTON_REC] (see below)
+                    double* rc = slot + (size_t)lane * NEWTON_REC;
 #pragma unroll
-                for (int r = 0; r < 3; ++r)
+                    for (int r = 0; r < 3; ++r)
 #pragma unroll
-                    for (int d = 0; d < 5; ++d) slot[(size_t)(r * 5 + d) * N + lane] = T[r][d];
+                        for (int d = 0; d < 5; ++d) rc[r * 5 + d] = T[r][d];
+                    rc[15] = xl[3 * N1 + lane]; rc[16] = xl[4 * N1 + lane]; rc[17] = u[lane]; rc[18] = u[N + lane];
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 3; ++r)
+#pragma unroll
+                        for (int d = 0; d < 5; ++d) slot[(size_t)(r * 5 + d) * N + lane] = T[r][d];
+                }
             }
             __syncthreads();
-            double lam[4] = {-1.0, 2.0 * xl[3 * N1 + N], 2.0 * xl[4 * N1 + N], 0.0};      // d J / d (s, ey, epsi, v) at node N
-            for (int k = N - 1; k >= 0; --k) {
-                double T[3][5], ga, gd;
+            if (NEWTON) {
+                // One backward loop for the costate recursion and the Riccati sweep, one forward loop: step k's words lie in one
+                // record -- T_k (15), ey_k, epsi_k, a_k, df_k (4), one free, K_k and kappa_k (8) -- so a step is one address and
+                // wide broadcast reads, and the 19 words are read once for both recursions.  The addresses are formed from a
+                // copy of N that the compiler cannot see through: formed from N they are hoisted out of the iteration loop and
+                // held in scalar registers across both roll-outs, which shows as scratch (make resource-usage-polish).
+                int Nn = N;
+                asm volatile("" : "+s"(Nn));
+                const int N1n = Nn + 1;
+                double* dn = xl + 7 * N1n;                 // [2 N] the Newton direction
+                double lam[4] = {-1.0, 2.0 * xl[3 * N1n + Nn], 2.0 * xl[4 * N1n + Nn], 0.0};
+                adj::Riccati ric;
+                ric.init(xl[3 * N1n + Nn], xl[4 * N1n + Nn]);
+                for (int k = Nn - 1; k >= 0; --k) {
+                    double* rc = slot + (size_t)k * NEWTON_REC;
+                    double T[3][5], K[2][3], kap[2], ga, gd;
 #pragma unroll
-                for (int r = 0; r < 3; ++r)
+                    for (int r = 0; r < 3; ++r)
 #pragma unroll
-                    for (int d = 0; d < 5; ++d) T[r][d] = slot[(size_t)(r * 5 + d) * N + k];
-                adj::costate_step(T, P.dt, P.w_u, xl[3 * N1 + k], xl[4 * N1 + k], u[k], u[N + k], lam, ga, gd);
-                if (lane == 0) {
-                    g[k] = finite_d(ga) ? ga : 0.0;
-                    g[N + k] = finite_d(gd) ? gd : 0.0;
+                        for (int d = 0; d < 5; ++d) T[r][d] = rc[r * 5 + d];
+                    const double ey = rc[15], ep = rc[16], a = rc[17], df = rc[18];
+                    adj::costate_step(T, P.dt, P.w_u, ey, ep, a, df, lam, ga, gd);
+                    ric.step(T, P.dt, P.w_u, ey, ep, a, df, K, kap);
+                    if (lane == 0) {
+                        g[k] = finite_d(ga) ? ga : 0.0;
+                        g[Nn + k] = finite_d(gd) ? gd : 0.0;
+#pragma unroll
+                        for (int c = 0; c < 2; ++c) {
+#pragma unroll
+                            for (int j = 0; j < 3; ++j) rc[20 + c * 3 + j] = K[c][j];
+                            rc[26 + c] = kap[c];
+                        }
+                    }
+                }
+                __syncthreads();
+                const bool steer = P.rate_df > 0.0;
+                double dz[3] = {0.0, 0.0, 0.0};
+                for (int k = 0; k < Nn; ++k) {
+                    const double* rc = slot + (size_t)k * NEWTON_REC;
+                    double T[3][5], K[2][3], kap[2], d[2];
+#pragma unroll
+                    for (int r = 1; r < 3; ++r)
+#pragma unroll
+                        for (int c = 0; c < 5; ++c) T[r][c] = rc[r * 5 + c];
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) K[c][j] = rc[20 + c * 3 + j];
+                        kap[c] = rc[26 + c];
+                    }
+                    adj::newton_forward_step(T, P.dt, K, kap, steer, dz, d);
+                    if (lane == 0) {
+                        dn[k] = (ric.ok && finite_d(d[0])) ? d[0] : 0.0;
+                        dn[Nn + k] = (ric.ok && finite_d(d[1])) ? d[1] : 0.0;
+                    }
+                }
+            } else {                                      // (the adjoint build's own text: sharing it with NEWTON moves its code)
+                double lam[4] = {-1.0, 2.0 * xl[3 * N1 + N], 2.0 * xl[4 * N1 + N], 0.0};      // d J / d (s, ey, epsi, v) at node N
+                for (int k = N - 1; k >= 0; --k) {
+                    double T[3][5], ga, gd;
+#pragma unroll
+                    for (int r = 0; r < 3; ++r)
+#pragma unroll
+                        for (int d = 0; d < 5; ++d) T[r][d] = slot[(size_t)(r * 5 + d) * N + k];
+                    adj::costate_step(T, P.dt, P.w_u, xl[3 * N1 + k], xl[4 * N1 + k], u[k], u[N + k], lam, ga, gd);
+                    if (lane == 0) {
+                        g[k] = finite_d(ga) ? ga : 0.0;
+                        g[N + k] = finite_d(gd) ? gd : 0.0;
+                    }
                 }
             }
             __syncthreads();
@@ -809,13 +889,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                 __syncthreads();                          // every lane has read g
                 for (int i = lane; i < n2; i += 64) g[i] = (i < N || steer) ? -g[i] / scale : 0.0;
                 __syncthreads();
-                const double alpha = exp2(-(double)lane / 3.0);
-                double pa = S.a_prev, pd = S.df_prev;
-                for (int k = 0; k < N; ++k) {
-                    pa = clampd(clampd(u[k] + alpha * g[k], pa - P.rate_a, pa + P.rate_a), P.a_min, P.a_max);
-                    pd = clampd(clampd(u[N + k] + alpha * g[N + k], pd - P.rate_df, pd + P.rate_df), -P.df_max, P.df_max);
-                    slot[(size_t)k * 64 + lane] = pa;
-                    slot[(size_t)(N + k) * 64 + lane] = pd;
+                if (NEWTON) {                             // dN on the lower half of the lanes, the scaled -g on the upper
+                    const double alpha = exp2(-(double)(lane & 31) / 3.0);
+                    const double* dir = lane < 32 ? xl + 7 * (N + 1) : g;
+                    double pa = S.a_prev, pd = S.df_prev;
+                    for (int k = 0; k < N; ++k) {
+                        pa = clampd(clampd(u[k] + alpha * dir[k], pa - P.rate_a, pa + P.rate_a), P.a_min, P.a_max);
+                        pd = clampd(clampd(u[N + k] + alpha * dir[N + k], pd - P.rate_df, pd + P.rate_df), -P.df_max, P.df_max);
+                        slot[(size_t)k * 64 + lane] = pa;
+                        slot[(size_t)(N + k) * 64 + lane] = pd;
+                    }
+                } else {    // not shared with the branch above: one loop over `dir` reorders registers in the forward-difference
+                            // builds, which must stay the device code they were (profiles/polish_newton_identity.txt)
+                    const double alpha = exp2(-(double)lane / 3.0);
+                    double pa = S.a_prev, pd = S.df_prev;
+                    for (int k = 0; k < N; ++k) {
+                        pa = clampd(clampd(u[k] + alpha * g[k], pa - P.rate_a, pa + P.rate_a), P.a_min, P.a_max);
+                        pd = clampd(clampd(u[N + k] + alpha * g[N + k], pd - P.rate_df, pd + P.rate_df), -P.df_max, P.df_max);
+                        slot[(size_t)k * 64 + lane] = pa;
+                        slot[(size_t)(N + k) * 64 + lane] = pd;
+                    }
                 }
             }
             double J, sN, vN;
@@ -1290,6 +1383,7 @@ hipError_t prepare_emit_kernels() {
         for_each_family([&](auto cand) { opt_in(emit_seg_f64_kernel<cand(), hi(), nrk()>); });
         opt_in(polish_f64_kernel<hi(), nrk(), false>);
         opt_in(polish_f64_kernel<hi(), nrk(), true>);
+        opt_in(polish_f64_kernel<hi(), nrk(), true, true>);
     });
     opt_in(cost_gradient_f64_kernel<TERM_PROGRESS>);
     opt_in(cost_gradient_f64_kernel<TERM_LEAVE>);
@@ -1312,8 +1406,17 @@ hipError_t launch_emit<double>(const KP& P, int B, int W, const SolveArgs<double
 // polish_iters > 0: after emit, on the same stream (igt_api.hip solve_impl).  The kernel's LDS passes 64 KB from N = 63 on: it is
 // asked for once per handle (prepare_emit_kernels), like the emit in pieces'.
 // adjoint: the gradient of every iteration is the analytic one (igt_set_polish_gradient); the same grid, block and LDS.
-hipError_t launch_polish(const KP& P, int B, int iters, bool adjoint, const SolveArgs<double>& A, hipStream_t st) {
+// newton: the Newton build (igt_set_polish_step), analytic gradient whatever `adjoint` says; its LDS is 2 N doubles larger.
+hipError_t launch_polish(const KP& P, int B, int iters, bool adjoint, bool newton, const SolveArgs<double>& A, hipStream_t st) {
     if (P.dev & (DEV_EXACT64 | DEV_LITERAL)) return hipErrorNotSupported;      // the oracle-order developer kernels
+    if (newton) {
+        const size_t lds = polish_newton_lds_doubles(P.N) * 8;
+        return with_discretisation(P.hi_order, P.n_rk4, [&](auto hi, auto nrk) {
+            hipLaunchKernelGGL((polish_f64_kernel<hi(), nrk(), true, true>), dim3(B), dim3(64), lds, st, P, B, iters, A.x0, A.u_prev,
+                               A.kparams, A.flags, A.obs, A.cinf, A.status_out, A.cost_out, A.x_out, A.u_out);
+            return hipGetLastError();
+        });
+    }
     const size_t lds = polish_lds_doubles(P.N) * 8;
     return with_discretisation(P.hi_order, P.n_rk4, [&](auto hi, auto nrk) {
         return with_bool(adjoint, [&](auto adj) {

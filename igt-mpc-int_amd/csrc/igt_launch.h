@@ -117,7 +117,7 @@ hipError_t launch_value(const KP& P, int B, const DevNet<T>& net, const SolveArg
 hipError_t prepare_value_kernels(int n_hidden_mats);   // once per igt_set_value_net: dynamic-LDS function attributes
 hipError_t prepare_emit_kernels();                     // once per igt_create: the same for the float64 emit in pieces
 // polish_iters > 0 (float64, progress cost): projected-gradient steps on the emitted winners, in place in A's outputs
-hipError_t launch_polish(const KP& P, int B, int iters, bool adjoint, const SolveArgs<double>& A, hipStream_t st);
+hipError_t launch_polish(const KP& P, int B, int iters, bool adjoint, bool newton, const SolveArgs<double>& A, hipStream_t st);
 hipError_t launch_cost_gradient(const KP& P, int B, const double* x0, const double* kparams, const double* U, double* cost_out,
                                 double* grad_out, hipStream_t st);
 // igt_cost_gradient_vn_f64: the sweep before (leave: forward only, (s_N, v_N) into vn) and behind launch_terminal_value

@@ -14,6 +14,7 @@ IGT_COST_PROGRESS, IGT_COST_VALUE_NET = 0, 1
 IGT_FLAG_ABS_HEADING = 1
 IGT_FLAG_WARM = 2
 IGT_GRAD_FORWARD_DIFF, IGT_GRAD_ADJOINT = 0, 1
+IGT_POLISH_STEP_GRADIENT, IGT_POLISH_STEP_NEWTON = 0, 1
 VIOL_BITS = dict(box_v=1, box_u=2, rate=4, ey=8, terminal=16, collision=32, nonfinite=64)
 
 
@@ -73,6 +74,7 @@ SYMBOLS = {
     'igt_allgather_controls_f64': (_i, [_vp, _i32, _vp, _vp, _vp]),
     'igt_set_concurrency': (_i, [_vp, _i32]),
     'igt_set_polish_gradient': (_i, [_vp, _i]),
+    'igt_set_polish_step': (_i, [_vp, _i]),
     'igt_cost_gradient_f64': (_i, [_vp, _i32] + [_vp] * 6 + [_i, _vp]),
     'igt_terminal_value_f64': (_i, [_vp, _i32] + [_vp] * 5 + [_i, _vp]),
     'igt_cost_gradient_vn_f64': (_i, [_vp, _i32] + [_vp] * 8 + [_i, _vp]),
@@ -82,7 +84,8 @@ SYMBOLS = {
 }
 
 # added without a change of IGT_VERSION: a library of the same ABI from before them (IGT_LIB_PATH, tools/ab_lib.sh) lacks them
-OPTIONAL_SYMBOLS = ('igt_set_polish_gradient', 'igt_cost_gradient_f64', 'igt_terminal_value_f64', 'igt_cost_gradient_vn_f64')
+OPTIONAL_SYMBOLS = ('igt_set_polish_gradient', 'igt_cost_gradient_f64', 'igt_terminal_value_f64', 'igt_cost_gradient_vn_f64',
+                    'igt_set_polish_step')
 
 _libs = {}
 # IGT_DEV_FLAGS bits (csrc/igt_device.h DevFlag; the launch-time bits there are the library's own and not listed here)

@@ -69,7 +69,7 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
                     dtype='f64', rotation=None, cand_mode='track', refine_iters=0, verbose=False,
                     eval_mode='mpc', value_net=None, device_resident=False, warm_start=None, init=None,
                     terminal_set=True, feas_tol=None, limits=None, graph=False, a_min_policy=None, constant_speed=False,
-                    v0=0.0, polish_iters=0, num_agents=2, polish_grad='fd'):
+                    v0=0.0, polish_iters=0, num_agents=2, polish_grad='fd', polish_step='gradient'):
     """eval_mode 'mpc' (evaluate.py:370-639) or 'gt_mpc' (123-369: terminal value network in the cost;
     value_net = dict(layers=[(W,b),...][, Wn, mu_f, sigma_t, mu_t]), default: the network the reference ships for
     scenario sc -- its normalisation statistics are not shipped, identity unless given).  device_resident=True keeps every per-step array in HBM (torch tensors;
@@ -89,7 +89,8 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     constant_speed: the forecast holds the other agent's speed (mpc.yaml:13-14 prediction_type, evaluate.py:76-79);
     v0: initial speed (fourwayint.yaml:11) -- load_reference_configs reads all three from the reference's files.
     polish_iters (f64, eval_mode 'mpc'): projected-gradient steps on every solved problem's winner (igtmpc.h polish_iters);
-    polish_grad: their gradient, 'fd' forward differences (default) or 'adjoint' analytic (igtmpc.h igt_set_polish_gradient).
+    polish_grad: their gradient, 'fd' forward differences (default) or 'adjoint' analytic (igtmpc.h igt_set_polish_gradient);
+    polish_step: 'gradient' (default) or 'newton', half of the trials along the Gauss-Newton direction (igt_set_polish_step).
     num_agents = M in 2..4 (evaluate.py:46; four approach lanes): every step solves E M problems with n_obs = M - 1 -- each
     agent against the forecast / shared plan of every other one (Jacobi, evaluate.py:469-558).  Scenario `sc`'s route tuples for
     M > 2: routes.scene_routes; init = (x[E,M,7], route tuples of length M).  eval_mode 'mpc' only beyond two (the value
@@ -134,6 +135,7 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     solver = BatchSolver(N=N, dt=dt, n_rk4=n_rk4, C=C, n_obs=M - 1, device=device, dtype=dtype, cand_mode=cand_mode,
                          refine_iters=refine_iters if cand_mode in ('ramp_hold', 'track') else 0,
                          cost_mode='value_net' if gt else 'progress', polish_iters=polish_iters, polish_grad=polish_grad,
+                         polish_step=polish_step,
                          **dict({} if feas_tol is None else {'feas_tol': feas_tol}, **(limits or {})))
     if gt:
         solver.set_value_net(**value_net)
@@ -464,6 +466,8 @@ def main():
     ap.add_argument('--dtype', default='f64', choices=['f64', 'f32'])
     ap.add_argument('--polish_iters', type=int, default=0, help='f64, eval_mode mpc: projected-gradient steps on each winner (0..4)')
     ap.add_argument('--polish_grad', choices=('fd', 'adjoint'), default='fd', help='gradient of the polish: forward differences or analytic')
+    ap.add_argument('--polish_step', choices=('gradient', 'newton'), default='gradient',
+                    help='step of the polish: along the gradient, or half of the trials along the Gauss-Newton (LQ) direction')
     ap.add_argument('--save_dir', default=None, help='write the run directory the reference\'s driver writes (cl_traj.pkl, u_cl.pkl, '
                     'stats csv, mpc.yaml; evaluate.py:646) under <save_dir><eval_mode>_sc<sc>_seed2026_<time>/')
     a = ap.parse_args()
@@ -483,7 +487,8 @@ def main():
     a.N = kw['N']
     r = run_closed_loop(sc=a.sc, num_samples=a.num_samples, C=a.C, verbose=a.verbose, eval_mode=a.eval_mode,
                         value_net=net, device_resident=a.device_resident, cand_mode=a.cand_mode, dtype=a.dtype, graph=a.graph,
-                        polish_iters=a.polish_iters, polish_grad=a.polish_grad, num_agents=a.num_agents, **kw)
+                        polish_iters=a.polish_iters, polish_grad=a.polish_grad, polish_step=a.polish_step, num_agents=a.num_agents,
+                        **kw)
     if a.save_dir is not None:
         policy = {'type': 'MPC', 'N': a.N, 'dt': kw.get('dt', 0.1), 'a_min': -4, 'a_max': 3, 'v_min': -1.0, 'v_max': 5,      # mpc.yaml's keys
                   'prediction_type': 'constant_acceleration', 'collision_avoidance_type': 'circle', **policy_file, 'N': a.N,

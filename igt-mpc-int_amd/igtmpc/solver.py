@@ -22,7 +22,7 @@ def _is_torch(x):
 
 class BatchSolver:
     def __init__(self, N=20, dt=0.1, n_rk4=4, C=256, n_obs=1, device=0, dtype='f32',
-                 cand_mode='lattice', cost_mode='progress', polish_grad='fd', **limits):
+                 cand_mode='lattice', cost_mode='progress', polish_grad='fd', polish_step='gradient', **limits):
         self._h = None
         self.lib = L.load()          # the shipped library -- or libigtmpc_dev.so when IGT_DEV_FLAGS asks for developer kernels
         if dtype not in _DT:
@@ -50,6 +50,11 @@ class BatchSolver:
         if polish_grad not in ('fd', 'adjoint'):
             raise ValueError("polish_grad must be 'fd' or 'adjoint'")
         self.polish_grad = polish_grad
+        # step of the polish (igtmpc.h igt_set_polish_step): 'gradient' the trials along the scaled -gradient (the default), 'newton'
+        # half of them along the Gauss-Newton (LQ) direction, which takes the analytic gradient whatever polish_grad says
+        if polish_step not in ('gradient', 'newton'):
+            raise ValueError("polish_step must be 'gradient' or 'newton'")
+        self.polish_step = polish_step
         self.params = p
         self.device = device
         h = ct.c_void_p()
@@ -65,6 +70,8 @@ class BatchSolver:
         self._routes_set = False
         if polish_grad != 'fd':      # the default needs no call: a library from before the setter still serves it
             self._check(self.lib.igt_set_polish_gradient(self._h, L.IGT_GRAD_ADJOINT))
+        if polish_step != 'gradient':      # likewise
+            self._check(self.lib.igt_set_polish_step(self._h, L.IGT_POLISH_STEP_NEWTON))
 
     def _check(self, rc):
         L.check(rc, self.lib)

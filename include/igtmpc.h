@@ -355,6 +355,34 @@ int igt_set_concurrency(igt_handle* h, int32_t solves_in_flight);
 enum { IGT_GRAD_FORWARD_DIFF = 0, IGT_GRAD_ADJOINT = 1 };
 int igt_set_polish_gradient(igt_handle* h, int mode);
 
+/* Which step the polish of the winner tries (polish_iters > 0; default IGT_POLISH_STEP_GRADIENT: the 64 trials along the scaled
+ * negative gradient, the launch sequence and bits of a handle that never called this).  IGT_POLISH_STEP_NEWTON adds the
+ * Gauss-Newton (LQ, iLQR) direction from the Jacobians the analytic gradient is made of.  Per solved scenario and iteration, from
+ * the plan u [2, N] with node states x_k and cost J0:
+ *   1. T_k (3 x 5): rows (s, ey, epsi) of x_k+1 by (ey, epsi, v) of x_k and by (a_k, df_k), K(s) locally constant, and the
+ *      analytic gradient g by the costate recursion (non-finite entries 0) -- IGT_GRAD_ADJOINT's, whatever
+ *      igt_set_polish_gradient says; that setting is kept and applies again when the step is set back.
+ *   2. LQ model over z = (ey, epsi, v):  A_k = T_k rows 1-2, columns 0-2, over the row (0, 0, 1);  B_k = T_k rows 1-2, columns
+ *      3-4, over the row (dt, 0);  Q = diag(2, 2, 0),  R = 2 w_u I.  The s row enters the linear terms only (the costate of s
+ *      is -1 throughout):  q_k = (2 ey_k, 2 epsi_k, 0) - T_k[0, 0:3],  r_k = 2 w_u u_k - T_k[0, 3:5].  The cost is a sum of
+ *      squares plus a linear term, so the model is exact in the cost; only the curvature of the dynamics is dropped.
+ *   3. Riccati sweep from P_N = Q, p_N = (2 ey_N, 2 epsi_N, 0), k = N-1 .. 0:  Quu = R + B'PB,  Qux = B'PA,  Qu = r + B'p,
+ *      K = -Quu^-1 Qux,  kappa = -Quu^-1 Qu (the 2 x 2 inverse by the determinant formula),  P <- Q + A'PA + Qux'K,
+ *      symmetrised (the upper triangle mirrored),  p <- q + A'p + Qux'kappa.
+ *   4. Forward sweep:  dz_0 = 0,  dN_k = kappa_k + K_k dz_k,  dz_k+1 = A_k dz_k + B_k dN_k.  Non-finite entries of dN become 0;
+ *      a determinant that is non-finite or <= 0 makes the whole dN of that scenario and iteration 0; with steer_rate = 0 the
+ *      steering row is 0, as for the gradient direction.  dN is not rescaled: trial 0 is the full Newton step.
+ *   5. Trials: lane m < 32 is project(u + 2^(-m/3) dN), lane m >= 32 is project(u + 2^(-(m-32)/3) dG) with dG the scaled -g of
+ *      the gradient step (four rate limits on the longest trial).  Projection, verdicts, the cheapest feasible trial with ties
+ *      to the lowest m and acceptance only when strictly cheaper are the gradient step's.
+ * Everything the polish promises holds as written at igt_solve_batch_*: x_out is u_out's own table roll-out bit for bit, the
+ * cost never rises, argmin_out, status_out and unsolved scenarios are untouched, no workspace, capturable.  The refusals of
+ * polish_iters are unchanged (value-network cost, _f32, developer kernels).  A setter for the reason given above.
+ * IGT_E_INVALID for a null handle or a mode that is neither IGT_POLISH_STEP_ constant.  (Added without a change of
+ * IGT_VERSION; a caller that must run against an older library probes the symbol.) */
+enum { IGT_POLISH_STEP_GRADIENT = 0, IGT_POLISH_STEP_NEWTON = 1 };
+int igt_set_polish_step(igt_handle* h, int mode);
+
 /* dJ/du of the progress cost for one control sequence per scenario:
  *   J(u) = sum_{k<=N} (epsi_k^2 + ey_k^2) + w_u sum_{k<N} (a_k^2 + df_k^2) - (s_N - s_0)            (mpc.py:356-373)
  * over the RK4 Frenet roll-out from x0 with the handle's dt, n_rk4, l_r, l_f, differentiated by every a_k and df_k.  No

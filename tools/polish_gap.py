@@ -4,7 +4,9 @@
     python tools/polish_gap.py gap  [n_scenarios=256] [processes=16]     # gap to the NLP optimum
     python tools/polish_gap.py time [--parent-lib PATH] [--repeats 5]     # milliseconds per solve, one solve at a time
     python tools/polish_gap.py loop [episodes=512]                        # closed loop with polish_iters 0 and 2
-every mode takes  --grad fd|adjoint  (igtmpc.h igt_set_polish_gradient; default fd); time also  --N 20|40  and  --B 4096,65536
+every mode takes  --grad fd|adjoint  (igtmpc.h igt_set_polish_gradient; default fd)  and  --step gradient|newton  (igt_set_polish_step;
+default gradient; newton takes the analytic gradient whatever --grad says); time also  --N 20|40 ,  --B 4096,65536  and
+--families lattice,ramp-hold,tracking
 
 gap : the scenarios of tools/nlp_gap.py, solved by the device (float64) with the lattice, ramp-hold and tracking families x
       polish_iters 0, 1, 2, 4; gap = J - J_opt, J_opt the SLSQP optimum of oracle/nlp_quality.py started from the best answer
@@ -13,7 +15,8 @@ time: HIP events around solve(), B = 4096 and 65 536, N = 20, device tensors, on
       configuration is a fresh child process, this library and --parent-lib (a build of the parent commit, same ABI) taking
       turns, `repeats` rounds; per configuration the median of each child's medians and the spread over the rounds.
       polish_iters 0 / 1 / 2 for the three families, refine_iters = 2 beside them for the tracking family.  With --grad adjoint
-      the rows with polish_iters > 0 are measured in both gradient modes, side by side.
+      the rows with polish_iters > 0 are measured in both gradient modes, side by side.  With --step newton only the rows with
+      polish_iters 1 and 2 are measured: this library's adjoint and Newton modes and --parent-lib's adjoint mode, side by side.
 loop: igtmpc.evaluate.run_closed_loop, tracking default, N = 20 and N = 40, 64 episodes for each of the 8 scenarios."""
 import json
 import os
@@ -33,11 +36,20 @@ def _batch64(n, N=20):
     return {k: (np.asarray(v, dtype=np.float64) if v.dtype.kind == 'f' else v) for k, v in make_batch(n, N=N, dtype=np.float64).items()}
 
 
-def _grad_kw(grad):
-    """BatchSolver keyword of the gradient mode; none for the default, so that a library from before the setter still runs"""
+def _grad_kw(grad, step='gradient'):
+    """BatchSolver keywords of the gradient mode and the step; none for the defaults, so that a library from before the setters
+    still runs.  grad 'newton' (a row of the time table) is the Newton step."""
+    if grad == 'newton':
+        grad, step = 'adjoint', 'newton'
     if grad not in ('fd', 'adjoint'):
         sys.exit("--grad must be 'fd' or 'adjoint'")
-    return dict(polish_grad=grad) if grad != 'fd' else {}
+    if step not in ('gradient', 'newton'):
+        sys.exit("--step must be 'gradient' or 'newton'")
+    return dict(**(dict(polish_grad=grad) if grad != 'fd' else {}), **(dict(polish_step=step) if step != 'gradient' else {}))
+
+
+def _mode(grad, step):
+    return 'newton' if step == 'newton' else grad
 
 
 # ------------------------------------------------------------------------------------------------ gap
@@ -56,7 +68,7 @@ def _slsqp(job):
     return i, r['cost'], r['max_violation']
 
 
-def gap(n=256, procs=16, grad='fd'):
+def gap(n=256, procs=16, grad='fd', step='gradient'):
     import multiprocessing as mp
     import igtmpc
     import np_oracle as O
@@ -66,7 +78,7 @@ def gap(n=256, procs=16, grad='fd'):
     rows = {}
     for name, cand in FAMILIES:
         for k in (0, 1, 2, 4):
-            with igtmpc.BatchSolver(dtype='f64', cand_mode=cand, polish_iters=k, **_grad_kw(grad)) as s:
+            with igtmpc.BatchSolver(dtype='f64', cand_mode=cand, polish_iters=k, **_grad_kw(grad, step)) as s:
                 s.set_cinf(*cinf)
                 rows[(name, k)] = s.solve(b['x0'], b['u_prev'], b['kparams'], b['flags'], b['obs_xy'])
     J = np.stack([np.where(r['status'] == 0, r['cost'], np.inf) for r in rows.values()])
@@ -80,7 +92,7 @@ def gap(n=256, procs=16, grad='fd'):
         if viol < 1e-6:
             J_opt[i] = min(c, J[:, i].min())
     ok = np.isfinite(J_opt)
-    print(f'{n} scenarios of the benchmark generator, device solves (float64), polish gradient {grad}; {len(jobs)} solved by at least one row; optimum '
+    print(f'{n} scenarios of the benchmark generator, device solves (float64), polish {_mode(grad, step)}; {len(jobs)} solved by at least one row; optimum '
           f'(SLSQP, violation < 1e-6) for {ok.sum()}, mean J_opt {J_opt[ok].mean():.4f}')
     for (name, k), Jf in zip(rows, J):
         m = ok & np.isfinite(Jf)
@@ -118,22 +130,26 @@ def _time_child(cand, B, polish, refine, grad='fd', N=20, solves=30, warm=10):
     print(json.dumps(dict(ms=float(np.median(ms)), lo=float(np.min(ms)), hi=float(np.max(ms)))))
 
 
-def time_(parent_lib=None, repeats=5, grad='fd', N=20, Bs=(4096, 65536)):
-    _grad_kw(grad)
+def time_(parent_lib=None, repeats=5, grad='fd', N=20, Bs=(4096, 65536), step='gradient', families=None):
+    _grad_kw(grad, step)
+    newton = step == 'newton'
+    fams = [f for f in FAMILIES if families is None or f[0] in families]
     configs = []
     for B in Bs:
-        for name, cand in FAMILIES:
-            for k in (0, 1, 2):
-                for gm in (('fd', 'adjoint') if (k and grad == 'adjoint') else ('fd',)):
+        for name, cand in fams:
+            for k in ((1, 2) if newton else (0, 1, 2)):
+                for gm in (('adjoint', 'newton') if newton else ('fd', 'adjoint') if (k and grad == 'adjoint') else ('fd',)):
                     configs.append((name, cand, B, k, 0, gm))
-        configs.append(('tracking', 'track', B, 0, 2, 'fd'))
+        if not newton:
+            configs.append(('tracking', 'track', B, 0, 2, 'fd'))
     libs = [('this', None)] + ([('parent', parent_lib)] if parent_lib else [])
     got = {}
     for r in range(repeats):
         for name, cand, B, k, refine, gm in configs:
             for lib, path in libs:
-                if lib == 'parent' and (gm != 'fd' or (k and grad == 'fd')):
-                    continue           # the parent has no adjoint mode; its polished rows are asked for beside the adjoint ones
+                if lib == 'parent' and (gm != 'adjoint' if newton else (gm != 'fd' or (k and grad == 'fd'))):
+                    continue           # --grad: the parent has no adjoint mode, its polished rows are asked for beside the
+                                       # adjoint ones; --step newton: the parent's adjoint mode beside this library's two
                 env = dict(os.environ)
                 if path:
                     env['IGT_LIB_PATH'] = os.path.abspath(path)
@@ -142,6 +158,8 @@ def time_(parent_lib=None, repeats=5, grad='fd', N=20, Bs=(4096, 65536)):
                 if p.returncode != 0:          # a child that failed: nothing more is started on the device
                     sys.exit(f'{lib} {name} B={B} polish_iters={k} {gm}: exit {p.returncode}\n{p.stderr[-2000:]}')
                 got.setdefault((B, name, k, refine, gm, lib), []).append(json.loads(p.stdout.strip().splitlines()[-1])['ms'])
+                print(f'round {r + 1}: B = {B} {name} polish_iters {k} {gm} {lib}: {got[(B, name, k, refine, gm, lib)][-1]:.3f} ms',
+                      file=sys.stderr, flush=True)      # progress: the table comes at the end
     print(f'milliseconds per solve (HIP events, one solve at a time, N = {N}, float64); median of {repeats} child processes '
           f'[min .. max of their medians], libraries taking turns')
     for (B, name, k, refine, gm, lib), v in got.items():
@@ -150,17 +168,17 @@ def time_(parent_lib=None, repeats=5, grad='fd', N=20, Bs=(4096, 65536)):
 
 
 # ------------------------------------------------------------------------------------------------ loop
-def loop(episodes=512, grad='fd'):
+def loop(episodes=512, grad='fd', step='gradient'):
     """the protocol of DESIGN.md section 9's closed-loop table (tools/closed_loop_probe.py): episodes / 8 per scenario, 8 scenarios"""
     from igtmpc.evaluate import run_closed_loop
     for N in (20, 40):
         for k in (0, 2):
             inf, dl, fs, ms = [], [], [], []
             for sc in range(1, 9):
-                r = run_closed_loop(sc=sc, num_samples=episodes // 8, N=N, polish_iters=k, **_grad_kw(grad))
+                r = run_closed_loop(sc=sc, num_samples=episodes // 8, N=N, polish_iters=k, **_grad_kw(grad, step))
                 inf.append(r['infeasible_ratio'].mean()); dl.append(r['deadlock'].mean())
                 fs.append(r['x_data'][:, 2::7, -1].mean()); ms.append(r['solve_ms'][5:].mean())
-            print(f'closed loop, tracking default, N = {N}, {episodes // 8} episodes x 8 scenarios, polish_iters {k} ({grad}): infeasible steps '
+            print(f'closed loop, tracking default, N = {N}, {episodes // 8} episodes x 8 scenarios, polish_iters {k} ({_mode(grad, step)}): infeasible steps '
                   f'{np.mean(inf) * 100:.1f} %, deadlock flag {np.mean(dl) * 100:.1f} %, mean final s {np.mean(fs):.1f} m, '
                   f'{np.mean(ms):.3f} ms per step', flush=True)
 
@@ -169,6 +187,7 @@ if __name__ == '__main__':
     a = sys.argv[1:]
     opt = lambda name, default: a[a.index(name) + 1] if name in a else default
     grad = opt('--grad', 'fd')
+    step = opt('--step', 'gradient')
     pos = []                                   # positional arguments: what is left of the options and their values
     i = 1
     while i < len(a):
@@ -179,11 +198,12 @@ if __name__ == '__main__':
     if a and a[0] == '_child':
         _time_child(a[1], int(a[2]), int(a[3]), int(a[4]), *(a[5:6]), *(int(x) for x in a[6:7]))
     elif a and a[0] == 'gap':
-        gap(*(int(x) for x in pos[:2]), grad=grad)
+        gap(*(int(x) for x in pos[:2]), grad=grad, step=step)
     elif a and a[0] == 'time':
         time_(opt('--parent-lib', None), int(opt('--repeats', 5)), grad, int(opt('--N', 20)),
-              tuple(int(x) for x in opt('--B', '4096,65536').split(',')))
+              tuple(int(x) for x in opt('--B', '4096,65536').split(',')), step,
+              opt('--families', None) and opt('--families', None).split(','))
     elif a and a[0] == 'loop':
-        loop(*(int(x) for x in pos[:1]), grad=grad)
+        loop(*(int(x) for x in pos[:1]), grad=grad, step=step)
     else:
         sys.exit(__doc__)
