@@ -112,7 +112,7 @@ class MPC_Planner:
                  routes=None, ds_right=None, index=None, num_rk4_steps=7, solver='ipopt', ca_type='circle',
                  nn_config_dir=None, use_NN_cost2go=False, weights=(1, 1, 1),
                  C=256, device=0, dtype='f64', value_net=None, cand_mode='track', refine_iters=0, track_env=None,
-                 warm_start=None, polish_iters=0, polish_grad='fd', polish_step='gradient'):
+                 warm_start=None, polish_iters=0, polish_grad='fd', polish_step='gradient', value_polish_iters=0):
         assert agents is not None, 'Agents are not defined'           # mpc.py:155
         assert index is not None                                      # mpc.py:80
         if ca_type != 'circle':
@@ -167,12 +167,12 @@ class MPC_Planner:
             track_env = auto_track_env(N, dt)
         self.track_env = float(track_env)
         key = (N, dt, num_rk4_steps, C, self.num_obstacles, device, dtype, cost_mode, self.d_min, cand_mode, refine_iters,
-               self.track_env, _net_digest(value_net), polish_iters, polish_grad, polish_step)
+               self.track_env, _net_digest(value_net), polish_iters, polish_grad, polish_step, value_polish_iters)
         if key not in _SHARED:
             s = BatchSolver(N=N, dt=dt, n_rk4=num_rk4_steps, C=C, n_obs=self.num_obstacles, device=device,
                             dtype=dtype, cost_mode=cost_mode, d_min=self.d_min, cand_mode=cand_mode,
                             refine_iters=refine_iters, track_env=self.track_env, polish_iters=polish_iters,
-                            polish_grad=polish_grad, polish_step=polish_step)
+                            polish_grad=polish_grad, polish_step=polish_step, value_polish_iters=value_polish_iters)
             s.set_cinf(*self.C_inf)
             if use_NN_cost2go:
                 s.set_value_net(**value_net)

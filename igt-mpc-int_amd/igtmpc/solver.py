@@ -14,15 +14,27 @@ import numpy as np
 from . import _lib as L
 
 _DT = {'f32': np.float32, 'f64': np.float64}
+VALUE_POLISH_TRIALS = 64
 
 
 def _is_torch(x):
     return hasattr(x, 'data_ptr') and hasattr(x, 'is_cuda')
 
 
+def check_value_polish(iters, dtype, cost_mode):
+    """What BatchSolver(value_polish_iters=) / set_value_polish refuse, before any GPU call (the driver asks it too)."""
+    if isinstance(iters, bool) or int(iters) != iters or not 0 <= iters <= 4:
+        raise ValueError('value_polish_iters must be an integer in [0, 4]')
+    if iters > 0 and dtype != 'f64':
+        raise ValueError("value_polish_iters > 0 needs dtype='f64'")
+    if iters > 0 and cost_mode != 'value_net':
+        raise ValueError("value_polish_iters > 0 needs cost_mode='value_net' (the progress cost has polish_iters)")
+
+
 class BatchSolver:
     def __init__(self, N=20, dt=0.1, n_rk4=4, C=256, n_obs=1, device=0, dtype='f32',
-                 cand_mode='lattice', cost_mode='progress', polish_grad='fd', polish_step='gradient', **limits):
+                 cand_mode='lattice', cost_mode='progress', polish_grad='fd', polish_step='gradient',
+                 value_polish_iters=0, **limits):
         self._h = None
         self.lib = L.load()          # the shipped library -- or libigtmpc_dev.so when IGT_DEV_FLAGS asks for developer kernels
         if dtype not in _DT:
@@ -55,8 +67,14 @@ class BatchSolver:
         if polish_step not in ('gradient', 'newton'):
             raise ValueError("polish_step must be 'gradient' or 'newton'")
         self.polish_step = polish_step
+        # polish of the winner under the value-network cost (set_value_polish below): an explicit keyword, not a field of
+        # igt_params -- float64 and cost_mode='value_net' only, refused here, before any GPU call
+        check_value_polish(value_polish_iters, dtype, cost_mode)
+        self.value_polish_iters = int(value_polish_iters)
         self.params = p
         self.device = device
+        self.cost_mode = cost_mode
+        self._cinf_args = self._net_args = self._vp_table = None      # what value_polish's trial handle is set up from
         h = ct.c_void_p()
         self._check(self.lib.igt_create(ct.byref(p), device, ct.byref(h)))
         self._h = h
@@ -78,6 +96,7 @@ class BatchSolver:
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
+        self._drop_vp_table()
         if self._h is not None:
             self.lib.igt_destroy(self._h)
             self._h = None
@@ -102,6 +121,8 @@ class BatchSolver:
         if len(A) != len(b):
             raise ValueError('A and b disagree')
         self._check(self.lib.igt_set_cinf(self._h, A.ctypes.data, b.ctypes.data, len(b)))
+        self._cinf_args = (A.copy(), b.copy())
+        self._drop_vp_table()
 
     def set_candidate_table(self, U):
         U = np.ascontiguousarray(U, dtype=np.float64)
@@ -123,6 +144,8 @@ class BatchSolver:
         Wn_c, mu_c = np.ascontiguousarray(Wn), np.ascontiguousarray(mu_f)
         self._check(self.lib.igt_set_value_net(self._h, len(layers), dims_a.ctypes.data, flat.ctypes.data,
                                            Wn_c.ctypes.data, mu_c.ctypes.data, float(sigma_t), float(mu_t)))
+        self._net_args = (layers, Wn_c.copy(), mu_c.copy(), float(sigma_t), float(mu_t))
+        self._drop_vp_table()
 
     def set_concurrency(self, solves_in_flight):
         """Solves the caller keeps in flight on the device at a time, on other handles / streams (igtmpc.h igt_set_concurrency):
@@ -203,6 +226,9 @@ class BatchSolver:
         B = int(x0.shape[0])
         dt, N, no = self.np_dtype, self.N, self.n_obs
         torch_mode = _is_torch(x0)
+        if self.value_polish_iters and torch_mode:
+            raise TypeError('value_polish_iters > 0 is driven from the host: solve() takes numpy arrays then, not device tensors '
+                            '(and cannot be captured in a stream graph); set_value_polish(0) for the device-resident solve')
         if out is None:
             if torch_mode:
                 import torch
@@ -227,6 +253,8 @@ class BatchSolver:
                 if keep_is_copy(out[k], ptrs[i]):
                     raise ValueError(f'out[{k!r}] must be a contiguous array of the solver dtype')
         self._check(self._solve(self._h, B, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        if self.value_polish_iters:      # (host arrays: the solve above has synchronised)
+            self._value_polish_host(x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, out, self.value_polish_iters)
         return out
 
     def rollout_all(self, x0, u_prev, kparams, flags, obs_xy=None, tv_sv=None, enc=None, want_X=True, want_U=True,
@@ -248,6 +276,92 @@ class BatchSolver:
         mode, ptrs, keep = self._prep(arrs, shapes, dts)
         self._check(self._rollout(self._h, B, *ptrs, mode, self._stream_ptr(stream, False)))
         return dict(X=X, U=U, cost=cost, viol=viol)
+
+    # ------------------------------------------------------------------ polish under the value-network cost
+    def _drop_vp_table(self):
+        t, self._vp_table = getattr(self, '_vp_table', None), None
+        if t is not None:
+            t.close()
+
+    def _vp_trial_handle(self):
+        """A table handle (C = 64) with this solver's limits, terminal set and network: it rolls and judges the 64 trials.
+        Built from self.params as igt_create took them (the library reads them once; changing the struct later changes neither
+        handle) and dropped when set_cinf / set_value_net change what it mirrors.  A second copy of the network and a workspace
+        of its own: the price of driving the steps from the host."""
+        if self._vp_table is None:
+            own = ('N', 'dt', 'n_rk4', 'C', 'n_obs', 'cand_mode', 'cost_mode', 'polish_iters', 'refine_iters')
+            limits = {k: getattr(self.params, k) for k, _ in L.igt_params._fields_ if k not in own}
+            t = BatchSolver(N=self.N, dt=self.params.dt, n_rk4=self.params.n_rk4, C=VALUE_POLISH_TRIALS, n_obs=self.n_obs,
+                            device=self.device, dtype='f64', cand_mode='table', cost_mode='value_net', **limits)
+            if self._cinf_args is not None:
+                t.set_cinf(*self._cinf_args)
+            t.set_value_net(*self._net_args)
+            self._vp_table = t
+        return self._vp_table
+
+    def set_value_polish(self, k):
+        """Projected-gradient steps that solve() takes on every solved scenario's winner under the value-network cost (0..4;
+        0, the default: the solve as it is without this call, bit for bit).  float64 solvers with cost_mode='value_net';
+        polish_iters, the progress cost's polish, keeps refusing the value network.  Today the steps are driven from the host
+        (_value_polish_host): solve() takes them for host arrays and refuses device tensors -- and with them stream capture --
+        with a TypeError while k > 0."""
+        check_value_polish(k, self.dtype, self.cost_mode)
+        self.value_polish_iters = int(k)
+
+    def _value_polish_host(self, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, out, iters):
+        """Projected-gradient steps on every solved scenario's winner under the value-network cost (gt_mpc, mpc.py:356-369), driven
+        from the host through device entries that exist, in place in out = the solve's result for the same inputs (host
+        arrays).  Per solved scenario and iteration, from the plan u [2, N] and its cost J0 (iteration 1: the solve's):
+          1. g = dJ/du by igt_cost_gradient_vn_f64 at the plan (the costate seeded with the network's partials at the plan's own
+             (s_N, v_N)); non-finite entries become 0;
+          2. d = -g / scale, scale = max(max|g_a| / (4 dt jerk), max|g_df| / (4 dt steer_rate)) + 1e-30; steer_rate = 0: the
+             steering row of d is 0;
+          3. 64 trials u + 2^(-m/3) d, clamped step by step to the rate window around the clamped step before it, then to the box,
+             rolled, judged by every verdict and priced (stage terms - V_out of the trial's own terminal state) by
+             igt_rollout_batch_f64 on a table handle of 64 candidates with this solver's limits, terminal set and network;
+          4. the feasible trial of least cost, ties to the lowest m, accepted only if strictly cheaper than J0; else the scenario
+             stops for good.
+        x is the accepted trial's own table roll-out, cost never rises, argmin, status and unsolved rows are the solve's.  One gradient
+        launch per iteration for the whole batch, one table upload and roll-out per scenario and iteration: made for the
+        planner's one problem and for batches of some hundreds, with a host synchronisation per call (profiles/
+        value_polish_host_time.txt has the cost per scenario and iteration)."""
+        f8 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        x0, u_prev, kparams, obs_xy, tv_sv, enc = (f8(a) for a in (x0, u_prev, kparams, obs_xy, tv_sv, enc))
+        flags = np.ascontiguousarray(flags, dtype=np.uint32)
+        p, N = self.params, self.N
+        ra, rd = p.dt * p.jerk_limit, p.dt * p.steer_rate_limit
+        alpha = 2.0 ** (-np.arange(VALUE_POLISH_TRIALS) / 3.0)
+        table = self._vp_trial_handle()
+        alive = np.flatnonzero(out['status'] == 0)
+        for _ in range(iters):
+            if len(alive) == 0:
+                break
+            g = self.cost_gradient(x0[alive], kparams[alive], flags[alive], f8(out['u'][alive]), tv_sv=tv_sv[alive],
+                                   enc=enc[alive])['grad']
+            g = np.where(np.isfinite(g), g, 0.0)
+            ma, md = np.abs(g[:, 0]).max(axis=-1), np.abs(g[:, 1]).max(axis=-1)
+            scale = (np.maximum(ma / (4 * ra), md / (4 * rd)) if rd > 0 else ma / (4 * ra)) + 1e-30
+            d = -g / scale[:, None, None]
+            if not rd > 0:
+                d[:, 1] = 0.0
+            keep = []
+            for i, b in enumerate(alive):
+                U = out['u'][b][None] + alpha[:, None, None] * d[i][None]          # [64, 2, N]
+                pa = np.full(VALUE_POLISH_TRIALS, u_prev[b, 0])
+                pd = np.full(VALUE_POLISH_TRIALS, u_prev[b, 1])
+                for k in range(N):
+                    pa = np.clip(np.clip(U[:, 0, k], pa - ra, pa + ra), p.a_min, p.a_max)
+                    pd = np.clip(np.clip(U[:, 1, k], pd - rd, pd + rd), -p.df_max, p.df_max)
+                    U[:, 0, k], U[:, 1, k] = pa, pd
+                table.set_candidate_table(U)
+                r = table.rollout_all(x0[b:b + 1], u_prev[b:b + 1], kparams[b:b + 1], flags[b:b + 1], obs_xy[b:b + 1],
+                                      tv_sv[b:b + 1], enc[b:b + 1], want_U=False)
+                J = np.where((r['viol'][0] == 0) & np.isfinite(r['cost'][0]), r['cost'][0], np.inf)
+                m = int(J.argmin())                                                 # first minimum: the lowest m
+                if J[m] < out['cost'][b]:
+                    out['u'][b], out['x'][b], out['cost'][b] = U[m], r['X'][0, m], J[m]
+                    keep.append(b)
+            alive = np.asarray(keep, dtype=np.int64)
 
     def _entry(self, name):
         """An entry added without a change of IGT_VERSION: a library from before it (IGT_LIB_PATH) does not export it."""
