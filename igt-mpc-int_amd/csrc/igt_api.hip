@@ -62,6 +62,7 @@ struct igt_handle {
     int concurrency = 1;           // solves the caller keeps in flight on the device (igt_set_concurrency)
     int polish_grad = IGT_GRAD_FORWARD_DIFF;      // or IGT_GRAD_ADJOINT (igt_set_polish_gradient)
     int polish_step = IGT_POLISH_STEP_GRADIENT;   // or IGT_POLISH_STEP_NEWTON (igt_set_polish_step)
+    int value_polish = 0;          // iterations of the polish under the value-network cost (igt_set_value_polish)
     void* comm = nullptr;          // RCCL communicator of igt_comm_init (null: none)
     int comm_world = 1, comm_rank = 0;
     int32_t comm_B_local = 0;      // shard size of the communicator's first all-gather (0 = none yet); later calls must match
@@ -389,6 +390,18 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
         return fail(IGT_E_INVALID, "polish_iters > 0 needs the _f64 entry points (a forward difference of 1e-4 on a float cost is noise)");
     if (p.polish_iters > 0 && (h->kp.dev & (igt::DEV_EXACT64 | igt::DEV_LITERAL)))
         return fail(IGT_E_INVALID, "polish_iters > 0 is not available with the developer kernels of IGT_DEV_FLAGS 1024 / 2048");
+    // polish under the value-network cost (igt_set_value_polish): refused before anything is staged or enqueued
+    const int vp_iters = h->value_polish;
+    if (vp_iters > 0) {
+        if (sizeof(T) == 4) return fail(IGT_E_INVALID, "igt_set_value_polish > 0 needs the _f64 entry points");
+        if (h->kp.dev & (igt::DEV_EXACT64 | igt::DEV_LITERAL))
+            return fail(IGT_E_INVALID, "igt_set_value_polish > 0 is not available with the developer kernels of IGT_DEV_FLAGS 1024 / 2048");
+        if (B > igt::VALUE_POLISH_MAX_B) return fail(IGT_E_INVALID, "igt_set_value_polish > 0: B exceeds the 64 B trial records an int counts");
+        if (capturing(stream ? (hipStream_t)stream : h->stream))
+            return fail(IGT_E_STATE, "igt_set_value_polish > 0 cannot be recorded under stream capture: a solve replayed from a stream "
+                                     "graph with this polish faulted and the cause is not known; igt_set_value_polish(h, 0) for a "
+                                     "captured solve");
+    }
     const bool value = p.cost_mode == IGT_COST_VALUE_NET;
     const size_t n_x = (size_t)B * 7, n_u = (size_t)B * 2, n_k = (size_t)B * 3;
     const size_t n_obs = (size_t)B * p.n_obs * 2 * (p.N + 1);
@@ -439,6 +452,7 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     const bool trace = (h->kp.dev & igt::DEV_TRACE) != 0;      // developer trace: 32 B per unit behind the counters
     const size_t n_rec = value ? (size_t)B * p.C : 0;
     double* d_cpar = nullptr;
+    double* vp_work = nullptr;      // igt_value_polish_layout.h: the scratch of igt_set_value_polish's iterations
     const auto carve = [&](Arena& wa) {
         A.part_J = wa.take<double>(igt::PartJTail<T>(nullptr, B, (int)W, h->kp.G).doubles(ck_records));
         const igt::PartJTail<T> tail(A.part_J, B, (int)W, h->kp.G);
@@ -472,6 +486,7 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
                 A.live_idx = wa.take<unsigned>(n_rec);
             }
         }
+        if (vp_iters > 0) vp_work = wa.take<double>(igt::ValuePolishLayout::doubles(B, p.N));      // behind everything else
     };
     if (int rc = carve_work(h, st, carve)) return rc;
     A.n_cu = h->n_cu;
@@ -515,6 +530,23 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     if constexpr (sizeof(T) == 8) {      // the winners, polished in place in the outputs (igt_kernels_f64.hip polish_f64_kernel)
         if (p.polish_iters > 0) HIPCHK(igt::launch_polish(kp, B, p.polish_iters, h->polish_grad == IGT_GRAD_ADJOINT,
                                                        h->polish_step == IGT_POLISH_STEP_NEWTON, A, st));
+        // igt_set_value_polish: six launches an iteration, each sized by B (igt_kernels_f64.hip value_trials_f64_kernel) -- the
+        // gradient at the plan as igt_cost_gradient_vn_f64 takes it, the 64 trials per scenario, their values, the acceptance
+        if (vp_iters > 0) {
+            const igt::ValuePolishLayout VL(B, p.N);
+            double* grad = vp_work + VL.grad();
+            double* vn = vp_work + VL.vn();
+            const igt::VnScratch S(vn, B);
+            for (int it = 0; it < vp_iters; ++it) {
+                HIPCHK(igt::launch_cost_gradient_vn(kp, B, true, A.x0, A.kparams, A.u_out, vp_work + VL.grad_cost(), grad, vn, st));
+                HIPCHK(igt::launch_terminal_value(h->net_d, h->n_cu, B, S.sv(), A.tv_sv, A.enc, S.V(), S.dV(), st));
+                HIPCHK(igt::launch_cost_gradient_vn(kp, B, false, A.x0, A.kparams, A.u_out, vp_work + VL.grad_cost(), grad, vn, st));
+                HIPCHK(igt::launch_value_trials(kp, B, it == 0, A, vp_work, st));
+                HIPCHK(igt::launch_terminal_value(h->net_d, h->n_cu, B * igt::VALUE_POLISH_TRIALS, vp_work + VL.sv(),
+                                                  vp_work + VL.tv_sv(), vp_work + VL.enc(), vp_work + VL.V(), nullptr, st));
+                HIPCHK(igt::launch_value_accept(kp, B, A, vp_work, st));
+            }
+        }
     }
     if (h->prof) { HIPCHK(hipEventRecord(h->ev[2], st)); h->ev_recorded = true; }
 
@@ -1213,6 +1245,15 @@ int igt_set_polish_step(igt_handle* h, int mode) {
         return fail(IGT_E_INVALID, "mode must be IGT_POLISH_STEP_GRADIENT or IGT_POLISH_STEP_NEWTON");
     if (!h) return fail(IGT_E_INVALID, "null handle (igt_set_polish_step: IGT_POLISH_STEP_GRADIENT or IGT_POLISH_STEP_NEWTON)");
     h->polish_step = mode;
+    return IGT_OK;
+}
+
+int igt_set_value_polish(igt_handle* h, int iters) {
+    if (!h) return fail(IGT_E_INVALID, "null handle (igt_set_value_polish)");
+    if (iters < 0 || iters > igt::VALUE_POLISH_MAX_ITERS) return fail(IGT_E_INVALID, "igt_set_value_polish: iters must be in [0, 4]");
+    if (h->p.cost_mode != IGT_COST_VALUE_NET)
+        return fail(IGT_E_INVALID, "igt_set_value_polish needs a handle created with IGT_COST_VALUE_NET (the progress cost has polish_iters)");
+    h->value_polish = iters;
     return IGT_OK;
 }
 

@@ -6,6 +6,7 @@
 //   emit_gather_f64_kernel   small batches: the winner's trajectory copied out of the unit that rolled it
 //   rollout_all_f64_kernel   debug / parity: every candidate's trajectory, cost and verdict bits
 //   polish_f64_kernel     projected-gradient steps on the winner (forward-difference or adjoint gradient; Newton direction)
+//   value_trials_f64_kernel / value_accept_f64_kernel   the same under the value-network cost, around the network's kernels
 //   cost_gradient_f64_kernel   dJ/du of the progress cost for one control sequence per scenario (igt_adjoint64.h); templated on the
 //                         terminal term: the two sweeps of igt_cost_gradient_vn_f64 around the value network are instantiations
 //   search_kernel / emit_kernel / rollout_all_kernel<ExactStepper<double>>   the oracle's operation order (IGT_DEV_FLAGS=1024)
@@ -968,6 +969,147 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     if (lane == 0) cost_out[b] = J - (sN - S.x0[2]);
 }
 
+// ---- polish of the winner under the value-network cost (igt_set_value_polish; float64, gt_mpc) ----
+// J(u) = stage terms - V_out(s_N, v_N) (mpc.py:356-369): the terminal term is the network's, so an iteration cannot stay inside one
+// kernel as polish_f64_kernel's does -- the network's kernels stand between its parts.  Six launches on the solve's stream, each
+// sized by B alone (igt_api.hip solve_impl): the three of igt_cost_gradient_vn_f64 on u_out, value_trials_f64_kernel, the
+// values-alone terminal_value_f64_kernel over the 64 B trial records, value_accept_f64_kernel.  The scratch between them is the
+// solve's ValuePolishLayout (igt_value_polish_layout.h).  One wave per scenario in both kernels; a scenario is polished while
+// alive[b] is set: in iteration 1 where status_out[b] == 0, afterwards where the iteration before accepted a trial.
+// Trials: the gradient's non-finite entries become 0; scale, d, the 64 trials u + 2^(-m/3) d with their step-by-step clamps and
+// the [2 N][64] LDS columns are polish_f64_kernel's, and so is the roll-out: rollout_one on the table family with the lane's
+// column as its table (ROLL_POLISH), the sub-step variants voted across the wave, without the Cartesian rows where the obstacles
+// are out of reach.  Lane m leaves row b 64 + m of the records: stage cost (no terminal term), verdict bits (the rate verdict
+// included), (s_N, v_N) and a copy of the scenario's tv_sv and enc -- the network kernel takes one row per state and is not
+// taught another indexing.  A wave whose scenario is not alive writes NaN (s_N, v_N) and returns: the network launch reads
+// nothing this solve did not write, and a NaN value is never looked at.
+// Accept: J_m = stage_m - V_m where feasible and finite, the search's butterfly on (J, m), ties to the lowest m; accepted only if
+// strictly below cost_out[b].  The wave then lays trial m out again -- value_trial_column, the statements the trials kernel laid
+// it out with, every lane the same column --, rolls it with all rows, lane 0 keeps the states in LDS, and x_out[b], u_out[b],
+// cost_out[b] leave as whole rows.  alive[b] becomes the acceptance; argmin_out and status_out are never written.
+// LDS: the trial columns, plan and direction (value_trials_lds_doubles), the accept kernel the states as well
+// (polish_lds_doubles): above 64 KB from N = 63 on, asked for in prepare_emit_kernels.  Two waves per SIMD as the polish has: the
+// roll-out's registers are the search unit's (make resource-usage-polish prints both kernels').
+__host__ __device__ inline size_t value_trials_lds_doubles(int N) { return (size_t)2 * N * 64 + 4 * N; }
+// The plan u_out[b] into u, its gradient into g (non-finite entries 0), g <- d = -g / scale, and trial m into the calling lane's
+// column of slot.  Called by every lane of the scenario's wave.
+__device__ __forceinline__ void value_trial_column(const KP& P, const Scenario<double>& S, int b, int m, const double* u_out,
+                                                   const double* __restrict__ grad, double* slot, double* u, double* g) {
+    const int lane = threadIdx.x, N = P.N, n2 = 2 * N;
+    for (int i = lane; i < n2; i += 64) {
+        u[i] = u_out[(size_t)b * n2 + i];
+        const double gi = grad[(size_t)b * n2 + i];
+        g[i] = finite_d(gi) ? gi : 0.0;
+    }
+    __syncthreads();
+    // d = -g / scale: the longest trial moves some input by four rate limits
+    double ma = 0.0, md = 0.0;
+    for (int k = lane; k < N; k += 64) { ma = fmax(ma, fabs(g[k])); md = fmax(md, fabs(g[N + k])); }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        ma = fmax(ma, __shfl_xor(ma, off, 64));
+        md = fmax(md, __shfl_xor(md, off, 64));
+    }
+    const bool steer = P.rate_df > 0.0;
+    const double scale = (steer ? fmax(ma / (4.0 * P.rate_a), md / (4.0 * P.rate_df)) : ma / (4.0 * P.rate_a)) + 1e-30;
+    __syncthreads();                                      // every lane has read g
+    for (int i = lane; i < n2; i += 64) g[i] = (i < N || steer) ? -g[i] / scale : 0.0;
+    __syncthreads();
+    const double alpha = exp2(-(double)m / 3.0);
+    double pa = S.a_prev, pd = S.df_prev;
+    for (int k = 0; k < N; ++k) {
+        pa = clampd(clampd(u[k] + alpha * g[k], pa - P.rate_a, pa + P.rate_a), P.a_min, P.a_max);
+        pd = clampd(clampd(u[N + k] + alpha * g[N + k], pd - P.rate_df, pd + P.rate_df), -P.df_max, P.df_max);
+        slot[(size_t)k * 64 + lane] = pa;
+        slot[(size_t)(N + k) * 64 + lane] = pd;
+    }
+}
+template <bool HI, int NRK>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void value_trials_f64_kernel(
+        KP P, int B, int first, const double* __restrict__ x0, const double* __restrict__ u_prev, const double* __restrict__ kparams,
+        const uint32_t* __restrict__ flags, const double* __restrict__ obs, const double* __restrict__ cinf,
+        const double* __restrict__ tv_sv, const double* __restrict__ enc, const int32_t* __restrict__ status_out,
+        const double* __restrict__ u_out, double* work) {
+    extern __shared__ double value_lds[];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const ValuePolishLayout L(B, P.N);
+    int32_t* alive = reinterpret_cast<int32_t*>(work + L.alive());
+    const bool live = first ? status_out[b] == 0 : alive[b] != 0;
+    if (first && lane == 0) alive[b] = live ? 1 : 0;
+    const size_t row = (size_t)b * VALUE_POLISH_TRIALS + lane;
+    double2* sv = reinterpret_cast<double2*>(work + L.sv());
+    reinterpret_cast<double2*>(work + L.tv_sv())[row] = make_double2(tv_sv[(size_t)b * 2], tv_sv[(size_t)b * 2 + 1]);
+    reinterpret_cast<double2*>(work + L.enc())[row] = make_double2(enc[(size_t)b * 2], enc[(size_t)b * 2 + 1]);
+    double* stage = work + L.stage();
+    uint32_t* feas = reinterpret_cast<uint32_t*>(work + L.feas());
+    if (!live) {                                          // unsolved or stopped: defined words, nothing else
+        stage[row] = (double)NAN;
+        feas[row] = VIOL_NONFINITE;
+        sv[row] = make_double2((double)NAN, (double)NAN);
+        return;
+    }
+    const int n2 = 2 * P.N;
+    double* slot = value_lds;                             // [2 N][64] the lanes' control sequences
+    double* u = slot + (size_t)n2 * 64;                   // [2 N] the plan
+    double* g = u + n2;                                   // [2 N] gradient, then direction
+    Scenario<double> S;
+    load_scenario<double>(S, P, b, x0, u_prev, kparams, flags, obs);
+    const bool far = !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
+    value_trial_column(P, S, b, lane, u_out, work + L.grad(), slot, u, g);
+    NullSink none;
+    double J, sN, vN;
+    unsigned viol;
+    if (far) f64::rollout_one<CAND_TABLE, HI, ROLL_POLISH | ROLL_NO_XY, NRK>(P, S, 0, nullptr, cinf, none, J, viol, sN, vN, slot + lane, 64);
+    else f64::rollout_one<CAND_TABLE, HI, ROLL_POLISH, NRK>(P, S, 0, nullptr, cinf, none, J, viol, sN, vN, slot + lane, 64);
+    stage[row] = J;
+    feas[row] = viol;
+    sv[row] = make_double2(sN, vN);
+}
+template <bool HI, int NRK>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void value_accept_f64_kernel(
+        KP P, int B, const double* __restrict__ x0, const double* __restrict__ u_prev, const double* __restrict__ kparams,
+        const uint32_t* __restrict__ flags, const double* __restrict__ obs, const double* __restrict__ cinf,
+        double* __restrict__ cost_out, double* __restrict__ x_out, double* u_out, double* work) {
+    extern __shared__ double value_lds[];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const ValuePolishLayout L(B, P.N);
+    int32_t* alive = reinterpret_cast<int32_t*>(work + L.alive());
+    if (alive[b] == 0) return;                            // unsolved or stopped: neither read nor written
+    const size_t row = (size_t)b * VALUE_POLISH_TRIALS + lane;
+    const double Jm = (work + L.stage())[row] - (work + L.V())[row];          // mpc.py:369
+    double bestJ = Jm;
+    int bestM = (reinterpret_cast<const uint32_t*>(work + L.feas())[row] == 0 && finite_d(Jm)) ? lane : -1;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {             // the search's butterfly on (J, m), ties to the lowest m
+        const double oJ = __shfl_xor(bestJ, off, 64);
+        const int oM = __shfl_xor(bestM, off, 64);
+        const bool take = (oM >= 0) && (bestM < 0 || oJ < bestJ || (oJ == bestJ && oM < bestM));
+        if (take) { bestJ = oJ; bestM = oM; }
+    }
+    const bool accepted = bestM >= 0 && bestJ < cost_out[b];      // only when feasible and strictly cheaper
+    if (lane == 0) alive[b] = accepted ? 1 : 0;
+    if (!accepted) return;
+    const int N = P.N, n2 = 2 * N, nx = 7 * (N + 1);
+    double* slot = value_lds;
+    double* u = slot + (size_t)n2 * 64;
+    double* g = u + n2;
+    double* xl = g + n2;                                  // [7][N + 1] the accepted plan's states
+    Scenario<double> S;
+    load_scenario<double>(S, P, b, x0, u_prev, kparams, flags, obs);
+    value_trial_column(P, S, b, bestM, u_out, work + L.grad(), slot, u, g);
+    // the accepted trial with all rows: every lane rolls it (one wave's time either way), lane 0 keeps the states
+    StoreSink<double> keep{lane == 0 ? xl : nullptr, nullptr, N};
+    double J, sN, vN;
+    unsigned viol;
+    f64::rollout_one<CAND_TABLE, HI, ROLL_POLISH, NRK>(P, S, 0, nullptr, cinf, keep, J, viol, sN, vN, slot + lane, 64);
+    __syncthreads();
+    for (int i = lane; i < nx; i += 64) x_out[(size_t)b * nx + i] = xl[i];
+    for (int i = lane; i < n2; i += 64) u_out[(size_t)b * n2 + i] = slot[(size_t)i * 64 + lane];
+    if (lane == 0) cost_out[b] = bestJ;
+}
+
 // ---- dJ/du of the progress cost for one control sequence per scenario (igt_cost_gradient_f64) ----
 // 64 sequences per wave, one per lane.  Forward sweep: the roll-out of (s, ey, epsi) with the node states kept in LDS,
 // [3 (N + 1)][GRAD_STRIDE]; backward sweep: per step the Jacobian at the kept node (igt_adjoint64.h) and the costate update, v
@@ -1384,6 +1526,8 @@ hipError_t prepare_emit_kernels() {
         opt_in(polish_f64_kernel<hi(), nrk(), false>);
         opt_in(polish_f64_kernel<hi(), nrk(), true>);
         opt_in(polish_f64_kernel<hi(), nrk(), true, true>);
+        opt_in(value_trials_f64_kernel<hi(), nrk()>);
+        opt_in(value_accept_f64_kernel<hi(), nrk()>);
     });
     opt_in(cost_gradient_f64_kernel<TERM_PROGRESS>);
     opt_in(cost_gradient_f64_kernel<TERM_LEAVE>);
@@ -1424,6 +1568,26 @@ hipError_t launch_polish(const KP& P, int B, int iters, bool adjoint, bool newto
                                A.kparams, A.flags, A.obs, A.cinf, A.status_out, A.cost_out, A.x_out, A.u_out);
             return hipGetLastError();
         });
+    });
+}
+
+// igt_set_value_polish: launches 4 and 6 of an iteration (see value_trials_f64_kernel); grids of B, nothing read back
+hipError_t launch_value_trials(const KP& P, int B, bool first, const SolveArgs<double>& A, double* work, hipStream_t st) {
+    if (P.dev & (DEV_EXACT64 | DEV_LITERAL)) return hipErrorNotSupported;      // the oracle-order developer kernels
+    const size_t lds = value_trials_lds_doubles(P.N) * 8;
+    return with_discretisation(P.hi_order, P.n_rk4, [&](auto hi, auto nrk) {
+        hipLaunchKernelGGL((value_trials_f64_kernel<hi(), nrk()>), dim3(B), dim3(64), lds, st, P, B, first ? 1 : 0, A.x0, A.u_prev,
+                           A.kparams, A.flags, A.obs, A.cinf, A.tv_sv, A.enc, A.status_out, A.u_out, work);
+        return hipGetLastError();
+    });
+}
+hipError_t launch_value_accept(const KP& P, int B, const SolveArgs<double>& A, double* work, hipStream_t st) {
+    if (P.dev & (DEV_EXACT64 | DEV_LITERAL)) return hipErrorNotSupported;
+    const size_t lds = polish_lds_doubles(P.N) * 8;
+    return with_discretisation(P.hi_order, P.n_rk4, [&](auto hi, auto nrk) {
+        hipLaunchKernelGGL((value_accept_f64_kernel<hi(), nrk()>), dim3(B), dim3(64), lds, st, P, B, A.x0, A.u_prev, A.kparams,
+                           A.flags, A.obs, A.cinf, A.cost_out, A.x_out, A.u_out, work);
+        return hipGetLastError();
     });
 }
 

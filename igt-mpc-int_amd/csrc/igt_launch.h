@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "igt_device.h"
 #include "igt_value_net.h"
+#include "igt_value_polish_layout.h"
 
 namespace igt {
 
@@ -91,7 +92,7 @@ struct VnScratch {
     double* base;
     size_t B;
     __host__ __device__ VnScratch(double* base_, int B_) : base(base_), B((size_t)B_) {}
-    __host__ __device__ static size_t doubles(int B_) { return (size_t)5 * (size_t)B_; }
+    __host__ __device__ static size_t doubles(int B_) { return (size_t)VN_DOUBLES_PER_SCENARIO * (size_t)B_; }
     __host__ __device__ double* sv() const { return base; }
     __host__ __device__ double* V() const { return base + 2 * B; }
     __host__ __device__ double* dV() const { return base + 3 * B; }
@@ -126,6 +127,11 @@ hipError_t launch_cost_gradient_vn(const KP& P, int B, bool leave, const double*
 // igt_terminal_value_f64 (igt_value_net.h terminal_value_f64_kernel); dV_out null: the values alone
 hipError_t launch_terminal_value(const DevNet<double>& net, int n_cu, int n, const double* sv, const double* tv_sv,
                                  const double* enc, double* V_out, double* dV_out, hipStream_t st);
+// igt_set_value_polish (float64, value-network cost): launches 4 and 6 of one iteration on the emitted winners, in place in A's
+// outputs; work: the solve's ValuePolishLayout scratch (igt_value_polish_layout.h).  first: alive[b] is status_out[b] == 0.
+// Between them the caller runs launch_terminal_value over the 64 B trial records.
+hipError_t launch_value_trials(const KP& P, int B, bool first, const SolveArgs<double>& A, double* work, hipStream_t st);
+hipError_t launch_value_accept(const KP& P, int B, const SolveArgs<double>& A, double* work, hipStream_t st);
 template <typename T> hipError_t launch_reduce(int B, int W, const SolveArgs<T>& A, hipStream_t st);
 // ramp-hold refinement: winner of the pass just finished -> centre/span of the next pass (cpar[B,4])
 template <typename T>

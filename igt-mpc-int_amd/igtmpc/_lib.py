@@ -75,6 +75,7 @@ SYMBOLS = {
     'igt_set_concurrency': (_i, [_vp, _i32]),
     'igt_set_polish_gradient': (_i, [_vp, _i]),
     'igt_set_polish_step': (_i, [_vp, _i]),
+    'igt_set_value_polish': (_i, [_vp, _i]),
     'igt_cost_gradient_f64': (_i, [_vp, _i32] + [_vp] * 6 + [_i, _vp]),
     'igt_terminal_value_f64': (_i, [_vp, _i32] + [_vp] * 5 + [_i, _vp]),
     'igt_cost_gradient_vn_f64': (_i, [_vp, _i32] + [_vp] * 8 + [_i, _vp]),
@@ -85,7 +86,7 @@ SYMBOLS = {
 
 # added without a change of IGT_VERSION: a library of the same ABI from before them (IGT_LIB_PATH, tools/ab_lib.sh) lacks them
 OPTIONAL_SYMBOLS = ('igt_set_polish_gradient', 'igt_cost_gradient_f64', 'igt_terminal_value_f64', 'igt_cost_gradient_vn_f64',
-                    'igt_set_polish_step')
+                    'igt_set_polish_step', 'igt_set_value_polish')
 
 _libs = {}
 # IGT_DEV_FLAGS bits (csrc/igt_device.h DevFlag; the launch-time bits there are the library's own and not listed here)

@@ -26,7 +26,7 @@ import numpy as np
 from . import routes as R
 from .cinf import cinf_halfplanes
 from ._lib import IGT_FLAG_WARM
-from .solver import BatchSolver, check_value_polish
+from .solver import BatchSolver, check_value_polish, check_value_polish_driver
 from .value_nets import shipped_value_net
 
 A_MIN_POLICY = -4.0        # mpc.yaml:8, used by the brake fallback (evaluate.py:514)
@@ -69,7 +69,8 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
                     dtype='f64', rotation=None, cand_mode='track', refine_iters=0, verbose=False,
                     eval_mode='mpc', value_net=None, device_resident=False, warm_start=None, init=None,
                     terminal_set=True, feas_tol=None, limits=None, graph=False, a_min_policy=None, constant_speed=False,
-                    v0=0.0, polish_iters=0, num_agents=2, polish_grad='fd', polish_step='gradient', value_polish_iters=0):
+                    v0=0.0, polish_iters=0, num_agents=2, polish_grad='fd', polish_step='gradient', value_polish_iters=0,
+                    value_polish_driver='host'):
     """eval_mode 'mpc' (evaluate.py:370-639) or 'gt_mpc' (123-369: terminal value network in the cost;
     value_net = dict(layers=[(W,b),...][, Wn, mu_f, sigma_t, mu_t]), default: the network the reference ships for
     scenario sc -- its normalisation statistics are not shipped, identity unless given).  device_resident=True keeps every per-step array in HBM (torch tensors;
@@ -92,8 +93,10 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     polish_grad: their gradient, 'fd' forward differences (default) or 'adjoint' analytic (igtmpc.h igt_set_polish_gradient);
     polish_step: 'gradient' (default) or 'newton', half of the trials along the Gauss-Newton direction (igt_set_polish_step).
     value_polish_iters (0..4; f64, eval_mode 'gt_mpc'; 'mpc' checks its range and does not read it): the solver's polish under
-    the value-network cost (BatchSolver(value_polish_iters=)).  It is driven from the host today, so device_resident=True (and
-    graph=True) refuse it with a ValueError; polish_iters keeps raising with gt_mpc.
+    the value-network cost (BatchSolver(value_polish_iters=)).  value_polish_driver 'host' (default): driven from numpy, so
+    device_resident=True (and graph=True) refuse it with a ValueError; 'device': the library takes the steps inside the solve
+    (igtmpc.h igt_set_value_polish), device_resident=True runs, graph=True is refused with a ValueError -- the library refuses such
+    a solve under stream capture.  polish_iters keeps raising with gt_mpc.
     num_agents = M in 2..4 (evaluate.py:46; four approach lanes): every step solves E M problems with n_obs = M - 1 -- each
     agent against the forecast / shared plan of every other one (Jacobi, evaluate.py:469-558).  Scenario `sc`'s route tuples for
     M > 2: routes.scene_routes; init = (x[E,M,7], route tuples of length M).  eval_mode 'mpc' only beyond two (the value
@@ -107,8 +110,12 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     a_min_policy = A_MIN_POLICY if a_min_policy is None else float(a_min_policy)
     gt = eval_mode == 'gt_mpc'
     check_value_polish(value_polish_iters, dtype if gt else 'f64', 'value_net')      # the range in every mode; the dtype where it is read
+    check_value_polish_driver(value_polish_driver)
     vp_iters = value_polish_iters if gt else 0
-    if vp_iters and device_resident:
+    if vp_iters and value_polish_driver == 'device' and graph:
+        raise ValueError("value_polish_iters > 0 with value_polish_driver='device' is refused under stream capture (igtmpc.h "
+                         'igt_set_value_polish): not with graph=True')
+    if vp_iters and value_polish_driver == 'host' and device_resident:
         raise ValueError('value_polish_iters > 0 is driven from the host today: not with device_resident=True / graph=True')
     if gt and value_net is None:
         if init is not None:
@@ -143,6 +150,7 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
                          refine_iters=refine_iters if cand_mode in ('ramp_hold', 'track') else 0,
                          cost_mode='value_net' if gt else 'progress', polish_iters=polish_iters, polish_grad=polish_grad,
                          polish_step=polish_step, value_polish_iters=vp_iters,
+                         value_polish_driver=value_polish_driver if gt else 'host',
                          **dict({} if feas_tol is None else {'feas_tol': feas_tol}, **(limits or {})))
     if gt:
         solver.set_value_net(**value_net)
@@ -473,8 +481,11 @@ def main():
     ap.add_argument('--dtype', default='f64', choices=['f64', 'f32'])
     ap.add_argument('--polish_iters', type=int, default=0, help='f64, eval_mode mpc: projected-gradient steps on each winner (0..4)')
     ap.add_argument('--value_polish_iters', type=int, default=0,
-                    help='f64, eval_mode gt_mpc: projected-gradient steps on each winner under the value-network cost (0..4); driven from '
-                         'the host, refused with --device_resident and --graph')
+                    help='f64, eval_mode gt_mpc: projected-gradient steps on each winner under the value-network cost (0..4); with the '
+                         "'host' driver refused with --device_resident and --graph")
+    ap.add_argument('--value_polish_driver', choices=('host', 'device'), default='host',
+                    help='who takes those steps: numpy on the host (default) or the library inside the solve (runs with '
+                         '--device_resident; --graph is refused: stream capture)')
     ap.add_argument('--polish_grad', choices=('fd', 'adjoint'), default='fd', help='gradient of the polish: forward differences or analytic')
     ap.add_argument('--polish_step', choices=('gradient', 'newton'), default='gradient',
                     help='step of the polish: along the gradient, or half of the trials along the Gauss-Newton (LQ) direction')
@@ -498,7 +509,8 @@ def main():
     r = run_closed_loop(sc=a.sc, num_samples=a.num_samples, C=a.C, verbose=a.verbose, eval_mode=a.eval_mode,
                         value_net=net, device_resident=a.device_resident, cand_mode=a.cand_mode, dtype=a.dtype, graph=a.graph,
                         polish_iters=a.polish_iters, polish_grad=a.polish_grad, polish_step=a.polish_step,
-                        value_polish_iters=a.value_polish_iters, num_agents=a.num_agents,
+                        value_polish_iters=a.value_polish_iters, value_polish_driver=a.value_polish_driver,
+                        num_agents=a.num_agents,
                         **kw)
     if a.save_dir is not None:
         policy = {'type': 'MPC', 'N': a.N, 'dt': kw.get('dt', 0.1), 'a_min': -4, 'a_max': 3, 'v_min': -1.0, 'v_max': 5,      # mpc.yaml's keys

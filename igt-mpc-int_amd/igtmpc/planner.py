@@ -18,7 +18,7 @@ import numpy as np
 
 from .cinf import cinf_halfplanes
 from ._lib import IGT_FLAG_WARM
-from .solver import BatchSolver
+from .solver import BatchSolver, check_value_polish_driver
 from .value_nets import shipped_value_net
 from .vehicle import Curvature, VehicleAction, VehicleReference  # noqa: F401  (re-exported for drivers)
 
@@ -112,7 +112,8 @@ class MPC_Planner:
                  routes=None, ds_right=None, index=None, num_rk4_steps=7, solver='ipopt', ca_type='circle',
                  nn_config_dir=None, use_NN_cost2go=False, weights=(1, 1, 1),
                  C=256, device=0, dtype='f64', value_net=None, cand_mode='track', refine_iters=0, track_env=None,
-                 warm_start=None, polish_iters=0, polish_grad='fd', polish_step='gradient', value_polish_iters=0):
+                 warm_start=None, polish_iters=0, polish_grad='fd', polish_step='gradient', value_polish_iters=0,
+                 value_polish_driver='host'):
         assert agents is not None, 'Agents are not defined'           # mpc.py:155
         assert index is not None                                      # mpc.py:80
         if ca_type != 'circle':
@@ -166,13 +167,16 @@ class MPC_Planner:
             from .evaluate import auto_track_env
             track_env = auto_track_env(N, dt)
         self.track_env = float(track_env)
+        check_value_polish_driver(value_polish_driver)
         key = (N, dt, num_rk4_steps, C, self.num_obstacles, device, dtype, cost_mode, self.d_min, cand_mode, refine_iters,
                self.track_env, _net_digest(value_net), polish_iters, polish_grad, polish_step, value_polish_iters)
+        key += (value_polish_driver,)      # a handle's igt_set_value_polish field is the driver's: one handle per driver
         if key not in _SHARED:
             s = BatchSolver(N=N, dt=dt, n_rk4=num_rk4_steps, C=C, n_obs=self.num_obstacles, device=device,
                             dtype=dtype, cost_mode=cost_mode, d_min=self.d_min, cand_mode=cand_mode,
                             refine_iters=refine_iters, track_env=self.track_env, polish_iters=polish_iters,
-                            polish_grad=polish_grad, polish_step=polish_step, value_polish_iters=value_polish_iters)
+                            polish_grad=polish_grad, polish_step=polish_step, value_polish_iters=value_polish_iters,
+                            value_polish_driver=value_polish_driver)
             s.set_cinf(*self.C_inf)
             if use_NN_cost2go:
                 s.set_value_net(**value_net)

@@ -15,6 +15,7 @@ from . import _lib as L
 
 _DT = {'f32': np.float32, 'f64': np.float64}
 VALUE_POLISH_TRIALS = 64
+VALUE_POLISH_DRIVERS = ('host', 'device')
 
 
 def _is_torch(x):
@@ -31,10 +32,17 @@ def check_value_polish(iters, dtype, cost_mode):
         raise ValueError("value_polish_iters > 0 needs cost_mode='value_net' (the progress cost has polish_iters)")
 
 
+def check_value_polish_driver(driver):
+    """The name of who drives the polish under the value-network cost: 'host' (numpy, _value_polish_host) or 'device' (igtmpc.h
+    igt_set_value_polish).  Refused before any GPU call."""
+    if driver not in VALUE_POLISH_DRIVERS:
+        raise ValueError(f"value_polish_driver must be 'host' or 'device', not {driver!r}")
+
+
 class BatchSolver:
     def __init__(self, N=20, dt=0.1, n_rk4=4, C=256, n_obs=1, device=0, dtype='f32',
                  cand_mode='lattice', cost_mode='progress', polish_grad='fd', polish_step='gradient',
-                 value_polish_iters=0, **limits):
+                 value_polish_iters=0, value_polish_driver='host', **limits):
         self._h = None
         self.lib = L.load()          # the shipped library -- or libigtmpc_dev.so when IGT_DEV_FLAGS asks for developer kernels
         if dtype not in _DT:
@@ -71,6 +79,9 @@ class BatchSolver:
         # igt_params -- float64 and cost_mode='value_net' only, refused here, before any GPU call
         check_value_polish(value_polish_iters, dtype, cost_mode)
         self.value_polish_iters = int(value_polish_iters)
+        # ... and who takes its steps: 'host' (the default) this class from numpy, 'device' the library inside the solve
+        check_value_polish_driver(value_polish_driver)
+        self.value_polish_driver = value_polish_driver
         self.params = p
         self.device = device
         self.cost_mode = cost_mode
@@ -90,6 +101,8 @@ class BatchSolver:
             self._check(self.lib.igt_set_polish_gradient(self._h, L.IGT_GRAD_ADJOINT))
         if polish_step != 'gradient':      # likewise
             self._check(self.lib.igt_set_polish_step(self._h, L.IGT_POLISH_STEP_NEWTON))
+        self._vp_field = 0      # the handle's igt_set_value_polish field: the iterations under 'device', 0 under 'host'
+        self._set_value_polish(self.value_polish_iters, value_polish_driver)      # likewise: no call while the field stays 0
 
     def _check(self, rc):
         L.check(rc, self.lib)
@@ -226,7 +239,8 @@ class BatchSolver:
         B = int(x0.shape[0])
         dt, N, no = self.np_dtype, self.N, self.n_obs
         torch_mode = _is_torch(x0)
-        if self.value_polish_iters and torch_mode:
+        host_polish = self.value_polish_iters if self.value_polish_driver == 'host' else 0
+        if host_polish and torch_mode:
             raise TypeError('value_polish_iters > 0 is driven from the host: solve() takes numpy arrays then, not device tensors '
                             '(and cannot be captured in a stream graph); set_value_polish(0) for the device-resident solve')
         if out is None:
@@ -253,8 +267,8 @@ class BatchSolver:
                 if keep_is_copy(out[k], ptrs[i]):
                     raise ValueError(f'out[{k!r}] must be a contiguous array of the solver dtype')
         self._check(self._solve(self._h, B, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
-        if self.value_polish_iters:      # (host arrays: the solve above has synchronised)
-            self._value_polish_host(x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, out, self.value_polish_iters)
+        if host_polish:      # (host arrays: the solve above has synchronised)
+            self._value_polish_host(x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, out, host_polish)
         return out
 
     def rollout_all(self, x0, u_prev, kparams, flags, obs_xy=None, tv_sv=None, enc=None, want_X=True, want_U=True,
@@ -302,11 +316,26 @@ class BatchSolver:
     def set_value_polish(self, k):
         """Projected-gradient steps that solve() takes on every solved scenario's winner under the value-network cost (0..4;
         0, the default: the solve as it is without this call, bit for bit).  float64 solvers with cost_mode='value_net';
-        polish_iters, the progress cost's polish, keeps refusing the value network.  Today the steps are driven from the host
-        (_value_polish_host): solve() takes them for host arrays and refuses device tensors -- and with them stream capture --
-        with a TypeError while k > 0."""
+        polish_iters, the progress cost's polish, keeps refusing the value network.  Who takes the steps is the solver's
+        value_polish_driver (the keyword, or set_value_polish_driver): under 'host', the default, they are driven from numpy
+        (_value_polish_host) -- solve() takes them for host arrays and refuses device tensors, and with them stream capture,
+        with a TypeError while k > 0; under 'device' the library takes them inside the solve (igtmpc.h igt_set_value_polish: six
+        launches an iteration on the solve's stream) for host arrays and device tensors alike -- a solve on a capturing stream is
+        then refused by the library (IgtError, 'stream capture')."""
+        self._set_value_polish(k, self.value_polish_driver)
+
+    def set_value_polish_driver(self, driver):
+        """'host' or 'device' (see set_value_polish); the number of iterations stays as it is."""
+        self._set_value_polish(self.value_polish_iters, driver)
+
+    def _set_value_polish(self, k, driver):
         check_value_polish(k, self.dtype, self.cost_mode)
-        self.value_polish_iters = int(k)
+        check_value_polish_driver(driver)
+        field = int(k) if driver == 'device' else 0
+        if field != self._vp_field:      # (a library from before the entry serves the 'host' driver and k = 0)
+            self._check(self._entry('igt_set_value_polish')(self._h, field))
+            self._vp_field = field
+        self.value_polish_iters, self.value_polish_driver = int(k), driver
 
     def _value_polish_host(self, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, out, iters):
         """Projected-gradient steps on every solved scenario's winner under the value-network cost (gt_mpc, mpc.py:356-369), driven

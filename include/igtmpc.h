@@ -383,6 +383,30 @@ int igt_set_polish_gradient(igt_handle* h, int mode);
 enum { IGT_POLISH_STEP_GRADIENT = 0, IGT_POLISH_STEP_NEWTON = 1 };
 int igt_set_polish_step(igt_handle* h, int mode);
 
+/* Polish of the winner under the value-network cost (IGT_COST_VALUE_NET, the _f64 solve entries; default 0: the launch sequence and
+ * bits of a handle that never called this).  With iters = k in 1..4 a solve enqueues, behind the emit pass and on its own
+ * stream, k iterations on every solved scenario's plan u [2, N] with cost J0 = stage terms - V_out(s_N, v_N) (mpc.py:356-369):
+ *   1. g = dJ/du at the plan, as igt_cost_gradient_vn_f64 returns it; non-finite entries become 0;
+ *   2. d = -g / scale, scale = max(max|g_a| / (4 dt jerk), max|g_df| / (4 dt steer_rate)) + 1e-30 (steer_rate = 0: the steering
+ *      row of d is 0 and its term is left out);
+ *   3. 64 trials u + 2^(-m/3) d, clamped step by step to the rate window around the clamped step before it, then to the box;
+ *      each is rolled and judged by every verdict (the rate verdict included) and priced stage terms - V_out of its own
+ *      terminal state;
+ *   4. the feasible trial of least cost, ties to the lowest m, is accepted only if strictly cheaper than J0; else the scenario
+ *      stops for good.
+ * x_out is u_out's own table roll-out bit for bit, cost_out never rises, argmin_out, status_out and unsolved scenarios are
+ * untouched.  Six launches an iteration whatever the batch, none sized by a count read from the device, no host
+ * synchronisation; IGT_MEM_HOST and IGT_MEM_DEVICE alike.  The scratch (64 trial records per scenario) is part of the solve's
+ * workspace, which therefore grows on the first eager solve after the call.
+ * Stream capture is refused while iters > 0: a solve on a capturing stream returns IGT_E_STATE ("stream capture") before it
+ * stages or enqueues anything.  An earlier build of this loop ended in an illegal memory access when replayed from a stream
+ * graph and the cause was not found; until it is, capture a solve with iters = 0.
+ * polish_iters, the progress cost's polish, keeps refusing the value network.  The _f32 solve entries and the developer kernels
+ * of IGT_DEV_FLAGS 1024 / 2048 refuse a handle with iters > 0 (IGT_E_INVALID).
+ * IGT_E_INVALID for a null handle, iters outside 0..4, or a handle whose cost is not IGT_COST_VALUE_NET.  (Added without a change
+ * of IGT_VERSION; a caller that must run against an older library probes the symbol.) */
+int igt_set_value_polish(igt_handle* h, int iters);
+
 /* dJ/du of the progress cost for one control sequence per scenario:
  *   J(u) = sum_{k<=N} (epsi_k^2 + ey_k^2) + w_u sum_{k<N} (a_k^2 + df_k^2) - (s_N - s_0)            (mpc.py:356-373)
  * over the RK4 Frenet roll-out from x0 with the handle's dt, n_rk4, l_r, l_f, differentiated by every a_k and df_k.  No
