@@ -70,6 +70,7 @@ struct igt_handle {
     size_t u0_bytes = 0;
     int dev_ckpt = -1;             // IGT_DEV_CKPT / IGT_DEV_TRAJ_MAX (threshold sweeps), read once at igt_create; -1: not set
     int dev_traj_max = -1;
+    int dev_reserve_pool = -1, dev_reserve_units = -1;      // IGT_DEV_RESERVE / IGT_DEV_RESERVE_UNITS (developer library only); -1: not set
 };
 
 namespace {
@@ -491,6 +492,8 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     if (int rc = carve_work(h, st, carve)) return rc;
     A.n_cu = h->n_cu;
     A.waves_per_simd = h->concurrency >= 3 ? 1 : 2;      // two solves in flight do not overlap on this runtime (igtmpc.h)
+    A.reserve_pool = h->dev_reserve_pool;
+    A.reserve_units = h->dev_reserve_units;
     A.ck_parts = ck_parts;
     if (h->prof) HIPCHK(hipEventRecord(h->ev[0], st));
     igt::KP kp = h->kp;
@@ -872,6 +875,11 @@ int igt_create(const igt_params* p, int device, igt_handle** out) {
     // developer sweeps: the environment is read here, not on every solve
     if (const char* e = std::getenv("IGT_DEV_CKPT")) h->dev_ckpt = std::max(std::atoi(e), 0);
     if (const char* e = std::getenv("IGT_DEV_TRAJ_MAX")) h->dev_traj_max = std::max(std::atoi(e), 0);
+#if IGT_DEV_KERNELS
+    // sweeps of the slot reserve (igt_launch.h search64_grid): waves per 8 compute units a float64 search leaves alone
+    if (const char* e = std::getenv("IGT_DEV_RESERVE")) h->dev_reserve_pool = std::max(std::atoi(e), 0);
+    if (const char* e = std::getenv("IGT_DEV_RESERVE_UNITS")) h->dev_reserve_units = std::max(std::atoi(e), 0);
+#endif
     { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0) h->n_cu = v; }
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete h; return fail(IGT_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }

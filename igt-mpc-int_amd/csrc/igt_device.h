@@ -53,6 +53,7 @@ enum DevFlag : int {
     DEV_NO_SEG_EMIT = 16777216,        // float64 emit rolls the winner in one piece, not from the search's checkpoints
     DEV_SEPARATE_QUEUES = 33554432,    // float64: the queues are sorted by build_queues_kernel, not inside accel_rows_kernel
     DEV_NO_REFILL = 1 << 26,           // float64 lattice: 64-candidate units, not one pool per scenario whose lanes refill
+    DEV_NO_RESERVE = 1 << 27,          // float64, three or more solves in flight: the search takes every wave slot (igt_launch.h search64_grid)
     // launch-time bits: what the search kernels find behind the partials (igt_launch.h PartJTail)
     DEV_LAUNCH_INCUMBENTS = 1 << 28,   // float: the [B] incumbents
     DEV_LAUNCH_CKPT = 1 << 29,         // float64: the checkpoint records for emit_seg_f64_kernel

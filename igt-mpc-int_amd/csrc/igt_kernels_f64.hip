@@ -1425,8 +1425,10 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
     // 2 waves per SIMD (232 VGPRs, no spill); the 3-per-SIMD build spills 244 B/lane and is 3-8 % behind at every batch
     // size (DEV_WAVES3 selects it for A/B runs)
     const bool o3 = IGT_DEV_KERNELS && (P.dev & DEV_WAVES3) != 0;
-    const size_t slots = (size_t)A.n_cu * 4 * (o3 ? 3 : (A.waves_per_simd == 1 ? 1 : 2));
-    const size_t grid = total < slots ? total : slots;
+    // the slots bound the pools' batch; the waves launched leave a reserve when solves overlap (igt_launch.h search64_grid)
+    const size_t slots = search64_slots(A.n_cu, A.waves_per_simd, P.dev);
+    const size_t waves = search64_grid(A.n_cu, A.waves_per_simd, Search64::UNITS, P.dev, A.reserve_units);
+    const size_t grid = total < waves ? total : waves;
     const unsigned* order = nullptr;
     // lattice on live rows: one item per scenario, its candidates rolled as one pool by a wave whose lanes refill (search_pool64).
     // An item is about four units long, and with fewer than four per wave the longest items make the span (one solve at a time,
@@ -1465,7 +1467,8 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
     if (!HI && captures_trajectories(P, A))
         return launch_search_kernel(search_f64_kernel_cap<CAND, VALUE>, grid, P, B, W, 8, order, order_stride, A, st, A.traj);
     if constexpr (CAND == CAND_LATTICE && !VALUE) if (pools) {
-        const size_t pgrid = (size_t)B < slots ? (size_t)B : slots;
+        const size_t pwaves = search64_grid(A.n_cu, A.waves_per_simd, Search64::POOL, P.dev, A.reserve_pool);
+        const size_t pgrid = (size_t)B < pwaves ? (size_t)B : pwaves;
         // with checkpoint records to leave (emit in pieces) the build that carries the slots; else the one without them
         return with_bool((Pr.dev & DEV_LAUNCH_CKPT) != 0, [&](auto ckpt) {
             return launch_search_kernel(search_f64_kernel_pool<CAND, HI, VALUE, NRK, ckpt()>, pgrid, Pr, B, W, 8, order,

@@ -43,6 +43,7 @@ struct SolveArgs {   // all device pointers
     unsigned* work_counter;         // the search's 8 unit counters, 256 B apart (zeroed before every launch); unit_trace behind them
     int n_cu;                       // compute units (sizes the persistent search grid)
     int waves_per_simd;             // of the persistent search grid: 2, or 1 when solves overlap (igt_set_concurrency); 0 = 2
+    int reserve_pool = -1, reserve_units = -1;   // developer sweeps: search64_grid's reserve_per_8cu by kernel family (-1: the shipped values)
     double* ckpt;                   // [ck_parts-1][B*Wk] horizon checkpoints of the search pass for emit (null: none)
     int ck_parts;                   // pieces the horizon is emitted in (igt_device.h Seg / Ckpt)
     unsigned* queue_order;          // [8][ceil(B/8) W] longest-first unit order of the search queues (null: index order)
@@ -102,6 +103,39 @@ struct VnScratch {
 constexpr size_t WORK_COUNTER_WORDS = 1024;
 __host__ __device__ inline unsigned long long* unit_trace(unsigned* work_counter) {
     return reinterpret_cast<unsigned long long*>(work_counter + WORK_COUNTER_WORDS);
+}
+
+// ---- the grid of the persistent float64 search (launch_search64) ----
+// The wave slots a search may take: two waves per SIMD (three: the developer builds of DEV_WAVES3), or one where the caller has
+// announced three or more solves in flight (SolveArgs::waves_per_simd == 1), so that two searches are resident side by side.
+// The pools' batch bound (B >= 4 * slots) is stated in these, reserve or not: which kernel runs does not depend on the reserve.
+inline size_t search64_slots(int n_cu, int waves_per_simd, int dev) {
+    const bool o3 = IGT_DEV_KERNELS && (dev & DEV_WAVES3) != 0;
+    return (size_t)n_cu * 4 * (o3 ? 3 : (waves_per_simd == 1 ? 1 : 2));
+}
+// The persistent waves a search launches.  With one wave per SIMD two resident searches take every slot of the chip between
+// them (the pool kernel's registers leave room for two waves per SIMD and no third).  From three solves in flight on a search
+// leaves `reserve` slots alone.  The waves dequeue their items, so a smaller grid gives each wave more items and nothing else
+// changes -- the same answers, bit for bit.  Measured with four solves in flight (profiles/slot_reserve_ab.txt, DESIGN section
+// 3): +4 % on the step rate with 32 of 1024 waves held back, less with 64 and 128, nothing with 256 -- though the other lanes'
+// emit and row passes, for which the reserve was meant, take as long as before: the search enqueued behind the two resident
+// ones takes the free slots and starts its longest items early.  With three in flight it costs 1.3 %.
+// reserve = n_cu * (waves per 8 compute units) / 8, by kernel family; the grid never goes below one wave per queue
+// (SEARCH64_QUEUES, one per XCD) while the chip has that many slots and never above the slots.  With one or two solves in
+// flight, with DEV_NO_RESERVE and for the DEV_WAVES3 builds: the slots.
+// reserve_per_8cu >= 0: the developer library's override for sweeps (IGT_DEV_RESERVE, IGT_DEV_RESERVE_UNITS; igt_api.hip).
+enum class Search64 { UNITS, POOL };       // search_f64_kernel_o2 / _o2w on 64-candidate units; search_f64_kernel_pool
+constexpr int SEARCH64_QUEUES = 8;
+constexpr int SEARCH64_RESERVE_PER_8CU_POOL = 1;       // 32 of 1024 waves at 256 compute units: the value that won the headline's sweep
+constexpr int SEARCH64_RESERVE_PER_8CU_UNITS = 0;      // the tracking family's gain (+3 %) stayed under three times its spread: the slots
+inline size_t search64_grid(int n_cu, int waves_per_simd, Search64 family, int dev, int reserve_per_8cu = -1) {
+    const size_t slots = search64_slots(n_cu, waves_per_simd, dev);
+    if (waves_per_simd != 1 || (dev & DEV_NO_RESERVE) || (IGT_DEV_KERNELS && (dev & DEV_WAVES3))) return slots;
+    const int per8 = reserve_per_8cu >= 0 ? reserve_per_8cu
+                                          : (family == Search64::POOL ? SEARCH64_RESERVE_PER_8CU_POOL : SEARCH64_RESERVE_PER_8CU_UNITS);
+    const size_t reserve = (size_t)n_cu * (size_t)per8 / 8;
+    const size_t floor = slots < (size_t)SEARCH64_QUEUES ? slots : (size_t)SEARCH64_QUEUES;
+    return slots > reserve + floor ? slots - reserve : floor;
 }
 
 bool search_builds_queues(const KP& P, int B, const SolveArgs<float>& A);   // then no memset of the counters is needed

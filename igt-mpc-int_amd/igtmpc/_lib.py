@@ -111,6 +111,7 @@ DEV_NO_BOUND = 8388608
 DEV_NO_SEG_EMIT = 16777216
 DEV_SEPARATE_QUEUES = 33554432
 DEV_NO_REFILL = 1 << 26
+DEV_NO_RESERVE = 1 << 27
 DEV_KERNEL_FLAGS = DEV_WAVES3 | DEV_EXACT64 | DEV_LITERAL      # the kernels only libigtmpc_dev.so carries
 LIB_PATH_DEV = os.path.join(os.path.dirname(LIB_PATH), 'libigtmpc_dev.so')
 
