@@ -372,11 +372,10 @@ int check_batch(const igt_handle* h, int32_t B, const void* x0, const void* u_pr
     return IGT_OK;
 }
 
-// the queue builder of small float batches zeroes the search kernel's unit counters itself
-template <typename T>
-inline bool counters_by_builder(const igt::KP& kp, int B, const igt::SolveArgs<T>& A) {
-    return igt::search_is_static(kp, B, A) || igt::search_builds_queues(kp, B, A);      // ... or the search uses none
-}
+// Whether the host zeroes the search kernel's unit counters: not where a queue builder does it or the search uses none.  The
+// double path reads its plan; the overloads exist only because the float path has no plan and asks its launcher's predicate.
+inline bool host_zeroes_counters(const igt::KP& kp, int B, const igt::SolveArgs<float>& A) { return !igt::search_builds_queues(kp, B, A); }
+inline bool host_zeroes_counters(const igt::KP&, int, const igt::SolveArgs<double>& A) { return A.plan.memset_counters; }
 
 template <typename T>
 int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* kparams, const uint32_t* flags,
@@ -440,38 +439,36 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
         if (sizeof(T) == 4 && v >= 1 && v <= igt::SEG_MAX_PARTS && p.N % v == 0 && p.N >= 2 * v) ck_parts = v;
     }
     const bool use_ckpt = ck_parts > 1;
-    // small double batches -- no more units than the chip has SIMDs, B <= 256 at 256 candidates -- : the search pass keeps
-    // every trajectory and emit copies the winner's (igt_kernels_common.h CaptureSink; 97 KB of stores per unit at N = 20,
-    // hidden behind a lone wave's dependent chains; with several units per SIMD they are not: a closed loop of 512
-    // problems per step ran 0.32 ms per step with them against 0.30 without, 0.43 against 0.36 at 1024)
-    size_t traj_max_units = (size_t)h->n_cu * 4;
-    if (h->dev_traj_max >= 0) traj_max_units = (size_t)std::min(h->dev_traj_max, 8192) * Wk;   // sweeps: a batch size
-    const bool capture = sizeof(T) == 8 && !exact64 && (size_t)B * Wk <= traj_max_units && (p.C % 64) == 0;
-    const size_t traj_doubles = capture ? (size_t)B * Wk * igt::traj_unit_doubles(p.N) : 0;
-    // double path, progress cost: the unit winners' horizon checkpoints for the emit in pieces (records behind the partials)
-    const bool ck_records = sizeof(T) == 8 && !value && !exact64 && p.N >= 8;
+    // double path: which kernels search and emit run, and with them the trajectories, checkpoint records and queue order to carve
+    // (igt_launch.h plan_search64).  One plan for the solve: a refinement pass changes nothing it reads.
+    A.n_cu = h->n_cu;
+    A.waves_per_simd = h->concurrency >= 3 ? 1 : 2;      // two solves in flight do not overlap on this runtime (igtmpc.h)
+    if constexpr (sizeof(T) == 8)
+        A.plan = igt::plan_search64(h->kp, B, value, igt::Search64Env{A.n_cu, A.waves_per_simd, h->dev_reserve_pool,
+                                                                       h->dev_reserve_units, h->dev_traj_max});
+    const igt::Search64Plan& plan = A.plan;
+    // float path, small batches: the search queues are sorted longest unit first (build_queues_kernel)
+    const size_t queue_order_words = sizeof(T) == 8 ? plan.queue_order_words : (B <= 6144 ? (size_t)((B + 7) / 8) * 8 * Wk : 0);
     const bool trace = (h->kp.dev & igt::DEV_TRACE) != 0;      // developer trace: 32 B per unit behind the counters
     const size_t n_rec = value ? (size_t)B * p.C : 0;
     double* d_cpar = nullptr;
     double* vp_work = nullptr;      // igt_value_polish_layout.h: the scratch of igt_set_value_polish's iterations
     const auto carve = [&](Arena& wa) {
-        A.part_J = wa.take<double>(igt::PartJTail<T>(nullptr, B, (int)W, h->kp.G).doubles(ck_records));
+        A.part_J = wa.take<double>(igt::PartJTail<T>(nullptr, B, (int)W, h->kp.G).doubles(plan.ck_records != 0));
         const igt::PartJTail<T> tail(A.part_J, B, (int)W, h->kp.G);
         A.incumbents = tail.incumbents();
         if constexpr (sizeof(T) == 8) {
             A.row_mask = tail.masks();
             A.row_rems = tail.row_rems();
-            A.ck_records = ck_records ? tail.ck_records() : nullptr;
+            A.ck_records = plan.ck_records ? tail.ck_records() : nullptr;
         }
         A.part_c = wa.take<int32_t>((size_t)B * W);
         d_cpar = wa.take<double>((size_t)B * 4);
         A.work_counter = wa.take<unsigned>(igt::WORK_COUNTER_WORDS + (trace ? (size_t)((B + 7) / 8) * 8 * Wk * 8 : 0));
         // small batches: the search pass leaves horizon checkpoints, emit rolls the winner's four quarters at once
         A.ckpt = use_ckpt ? wa.take<double>((size_t)(ck_parts - 1) * B * Wk * igt::SEG_UNIT_DOUBLES) : nullptr;
-        // small batches: the search queues are sorted longest unit first (build_queues_kernel; 3-5 % up to B = 4096,
-        // nothing from 8192 on)
-        A.queue_order = B <= 6144 ? wa.take<unsigned>((size_t)((B + 7) / 8) * 8 * Wk) : nullptr;
-        if constexpr (sizeof(T) == 8) A.traj = capture ? wa.take<double>(traj_doubles) : nullptr;
+        A.queue_order = queue_order_words ? wa.take<unsigned>(queue_order_words) : nullptr;
+        if constexpr (sizeof(T) == 8) A.traj = plan.traj_doubles ? wa.take<double>(plan.traj_doubles) : nullptr;
         if (value) {
             A.rec_J = wa.take<double>(n_rec);
             A.rec_sN = wa.take<T>(n_rec);
@@ -490,10 +487,6 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
         if (vp_iters > 0) vp_work = wa.take<double>(igt::ValuePolishLayout::doubles(B, p.N));      // behind everything else
     };
     if (int rc = carve_work(h, st, carve)) return rc;
-    A.n_cu = h->n_cu;
-    A.waves_per_simd = h->concurrency >= 3 ? 1 : 2;      // two solves in flight do not overlap on this runtime (igtmpc.h)
-    A.reserve_pool = h->dev_reserve_pool;
-    A.reserve_units = h->dev_reserve_units;
     A.ck_parts = ck_parts;
     if (h->prof) HIPCHK(hipEventRecord(h->ev[0], st));
     igt::KP kp = h->kp;
@@ -502,19 +495,19 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
         A.cpar = it == 0 ? nullptr : d_cpar;
         if (value) {
             if (compact) {
-                if (!counters_by_builder(kp, B, A)) HIPCHK(hipMemsetAsync(A.work_counter, 0, 8 * 256, st));
+                if (host_zeroes_counters(kp, B, A)) HIPCHK(hipMemsetAsync(A.work_counter, 0, 8 * 256, st));
                 HIPCHK(hipMemsetAsync(A.rec_count, 0, 256, st));
                 HIPCHK(hipMemsetAsync(A.best_key, 0xff, (size_t)B * 8, st));
             }
             else if (!exact64) {      // double path: compact list of feasible candidates as well
-                if (!counters_by_builder(kp, B, A)) HIPCHK(hipMemsetAsync(A.work_counter, 0, 8 * 256, st));
+                if (host_zeroes_counters(kp, B, A)) HIPCHK(hipMemsetAsync(A.work_counter, 0, 8 * 256, st));
                 HIPCHK(hipMemsetAsync(A.rec_count, 0, 256, st));
             }
             HIPCHK(igt::launch_search_records<T>(kp, B, A, st));
             HIPCHK(igt::launch_value<T>(kp, B, net_of<T>(h), A, nullptr, nullptr, st));
             if (exact64) HIPCHK(igt::launch_reduce<T>(B, (int)W, A, st));
         } else {
-            if (!exact64 && !counters_by_builder(kp, B, A)) HIPCHK(hipMemsetAsync(A.work_counter, 0, 8 * 256, st));
+            if (host_zeroes_counters(kp, B, A)) HIPCHK(hipMemsetAsync(A.work_counter, 0, 8 * 256, st));
             HIPCHK(igt::launch_search<T>(kp, B, A, h->nc, st));
         }
         if (it < p.refine_iters) {   // winner of this pass -> centre / span of the next one

@@ -199,7 +199,7 @@ __device__ __forceinline__ int units_of_live_rows(const KP& P, int W, unsigned l
 // One workgroup per queue sorts its units into QC cost classes, most expensive first, keeping the scenario order
 // inside a class (a stable counting sort, so the order is a function of the inputs alone).
 // order[q][k] = (scenario ordinal in the queue) * 256 + slice.
-constexpr int QC = 8, QB_THREADS = 1024, QB_TRIPS = 2;     // up to 2048 units per queue (B <= 8192 at W = 2)
+constexpr int QC = 8;     // QB_THREADS, QB_TRIPS (igt_launch.h): up to 2048 units per queue (B <= 8192 at W = 2)
 // The body for one queue q, run by one workgroup of QB_THREADS_ threads in QB_TRIPS_ trips (QB_THREADS_ * QB_TRIPS_ = 2048): the
 // stand-alone kernel below takes 1024 x 2; the float64 prelude (igt_kernels_f64.hip accel_rows_kernel, whose first eight
 // workgroups sort the queues while the others roll the acceleration rows) 256 x 8.

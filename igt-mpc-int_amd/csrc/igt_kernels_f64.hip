@@ -495,15 +495,6 @@ __device__ __forceinline__ void search_pool64(const KP& P, int W, int b, const d
         ck_all[(size_t)(b * W) * CK_RECORD + q * f64::CK_FIELDS + f] = rec[lane];
     }
 }
-// Whether the search rolls pools of candidates (search_pool64) instead of 64-candidate units: the lattice family, progress cost,
-// units of live rows, the steering table of all G columns fits.  Every developer switch that changes the units' layout keeps
-// the units (the A/B comparisons of the units stay what they were), and so does DEV_NO_REFILL; so do the queues sorted by
-// build_queues_kernel (DEV_SEPARATE_QUEUES), which knows only units.
-__host__ __device__ inline bool search_pools(const KP& P, int cand, bool value, bool live_rows) {
-    return cand == CAND_LATTICE && !value && live_rows && P.G * P.N <= STEER_TABLE_MAX_ENTRIES &&
-           !(P.dev & (DEV_NO_SLICES | DEV_NO_EARLY_EXIT | DEV_NO_STEER_TABLE | DEV_ALL_ROWS | DEV_WHOLE_COLUMNS | DEV_NO_REFILL |
-                      DEV_SEPARATE_QUEUES | DEV_WAVES3));
-}
 template <int CAND, bool HI, bool VALUE, int NRK, bool CKPT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_f64_kernel_pool(IGT_SEARCH64_ARGS) {
     if constexpr (CAND == CAND_LATTICE && !VALUE) {
@@ -634,7 +625,6 @@ struct SegSink {
         if (k == 0) { X[0] = st[0]; X[N1] = st[1]; X[6 * N1] = st[6]; }
     }
 };
-__host__ __device__ inline int seg_doubles_per_scenario(int N) { return 7 * (N + 1) + 4 * N; }
 
 struct LdsControls {         // tracking family: the controls of step k as the Frenet pieces left them in LDS
     const double* A; const double* SB; const double* CB;
@@ -1252,7 +1242,7 @@ struct LdsSink {
         for (int i = 0; i < 7; ++i) x[i * (N + 1) + k] = st[i];
     }
 };
-constexpr int LIT_WAVES = 16, LIT_MAX_N = 40;
+constexpr int LIT_WAVES = 16;      // LIT_MAX_N: igt_launch.h
 template <int CAND, bool HI>
 __global__ __launch_bounds__(64 * LIT_WAVES) void search_literal_f64_kernel(
     KP P, int B, int W, const double* __restrict__ x0, const double* __restrict__ u_prev, const double* __restrict__ kparams,
@@ -1329,7 +1319,7 @@ __global__ __launch_bounds__(64 * LIT_WAVES) void search_literal_f64_kernel(
 template <bool VALUE>
 static hipError_t launch_search_exact(const KP& P, int B, const SolveArgs<double>& A, hipStream_t st) {
     typedef ExactStepper<double> St;
-    const dim3 grid((B + 3) / 4), block(256);
+    const dim3 grid(A.plan.grid), block(256);
     with_bool(P.cand_mode != CAND_TABLE, [&](auto shared_df) {
         hipLaunchKernelGGL((search_kernel<St, double, 1, shared_df(), VALUE>), grid, block, 0, st, P, B, A.x0, A.u_prev,
                            A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.cost_out, A.argmin_out, A.status_out,
@@ -1339,59 +1329,6 @@ static hipError_t launch_search_exact(const KP& P, int B, const SolveArgs<double
 }
 
 #endif
-bool search_builds_queues(const KP& P, int B, const SolveArgs<double>& A) {
-    const int W = P.C / 64;
-    return A.queue_order && W <= 256 && ((B + 7) / 8) * W <= QB_THREADS * QB_TRIPS && !(P.dev & DEV_NO_QUEUE_ORDER) &&
-           !(P.dev & (DEV_EXACT64 | DEV_LITERAL));
-}
-
-// Small batches keep the trajectories of the search pass (CaptureSink) when the kernel built for the reference's
-// discretisation runs; DEV_NO_CAPTURE switches it off for A/B runs.
-static bool captures_trajectories(const KP& P, const SolveArgs<double>& A) {
-    return A.traj && !P.hi_order && P.n_rk4 == 4 && !(P.dev & (DEV_WAVES3 | DEV_EXACT64 | DEV_LITERAL | DEV_NO_CAPTURE));
-}
-
-// ... and such a batch has no more units than the chip has SIMDs (the kernel that keeps trajectories holds one wave per
-// SIMD), so every unit is given its own wave: the queue builder (6.6 us and a launch) would only order units that all start
-// at once.  Measured, search + emit, tracking family: 67 us against 84 at B = 1, 91 against 101 at B = 32.
-// DEV_KEEP_QUEUES keeps the queues for A/B runs; the unit trace (DEV_TRACE) needs them.
-bool search_is_static(const KP& P, int B, const SolveArgs<double>& A) {
-    return captures_trajectories(P, A) && (size_t)B * (P.C / 64) <= (size_t)A.n_cu * 4 && !(P.dev & (DEV_TRACE | DEV_KEEP_QUEUES));
-}
-
-// Whether emit rolls the winner in four pieces from the search pass's checkpoints (emit_seg_f64_kernel): progress cost (with the
-// value network the winner is only known after the network has run), batches that do not keep trajectories, horizons of at
-// least 8 steps, workspace taken for the records (A.ck_records).  The search launcher and the emit launcher both ask this.
-// scenarios per workgroup: a full wave's 64 when their staging fits a compute unit's LDS (116 KB at N = 20; 160 KB per CU,
-// the kernel asks for more than the default 64 KB: seg_lds_opt_in), else the largest power of two that does
-constexpr size_t SEG_LDS_MAX = 150 * 1024;
-static int seg_scenarios_per_block(const KP& P) {
-    int S = 64;
-    while (S > 0 && (size_t)S * seg_doubles_per_scenario(P.N) * 8 > SEG_LDS_MAX) S >>= 1;
-    return S;
-}
-template <class K>
-static hipError_t seg_lds_opt_in(K kernel) {      // once per instantiation and device (a function attribute)
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEG_LDS_MAX);
-}
-// Not when the caller overlaps solves (igt_set_concurrency >= 3): there the emit pass of one solve runs under the search pass of
-// another, its latency is hidden, and what matters is that it gets on the chip between two persistent search kernels -- one
-// 64-thread wave without LDS does, a 320-thread workgroup with 116 KB of LDS waits for a compute unit to drain (measured on one
-// box, three runs each: 20.3 against 20.9 M solves/s with four solves in flight).
-static bool emits_in_pieces(const KP& P, const SolveArgs<double>& A) {
-    return A.ck_records && P.cost_mode == 0 && P.N >= 8 && !captures_trajectories(P, A) && seg_scenarios_per_block(P) >= 4 &&
-           A.waves_per_simd != 1 && !(P.dev & (DEV_WAVES3 | DEV_EXACT64 | DEV_LITERAL | DEV_NO_SEG_EMIT));
-}
-
-// Whether the search runs on units made of live acceleration rows only (accel_rows_kernel; unit_layout).  Only for batches of
-// more than two rounds of units (B > 1024 at 256 candidates): below that the solve lasts as long as its longest unit, fewer
-// units do not shorten it, and the extra launch costs 8 us (a closed loop of 512 problems per step: 0.30 against 0.28 ms).
-static bool packs_live_rows(const KP& P, int B, const SolveArgs<double>& A) {
-    const int W = P.C / 64;
-    return A.row_mask && P.cand_mode != CAND_TABLE && P.G <= 64 && P.G * P.G == P.C && W * 64 == P.C && P.G % W == 0 &&
-           !(P.dev & (DEV_NO_SLICES | DEV_EXACT64 | DEV_LITERAL | DEV_ALL_ROWS)) && !captures_trajectories(P, A) && (size_t)B * W > (size_t)A.n_cu * 16;
-}
-
 // The arguments every float64 search kernel takes (IGT_SEARCH64_ARGS), out of SolveArgs; more: what one kernel takes behind
 // them (search_f64_kernel_cap: the trajectories)
 template <class Kernel, class... More>
@@ -1410,84 +1347,64 @@ static hipError_t with_build(const KP& P, F&& f) {
     });
 }
 
-// float64 search: persistent waves on the per-XCD queues, one 64-candidate unit at a time
+// float64 search: the prelude and the kernel that A.plan names (igt_launch.h plan_search64, where the rules and their
+// measurements are) -- persistent waves on the per-XCD queues, one 64-candidate unit, or one scenario's pool, at a time
 template <int CAND, bool HI, int NRK, bool VALUE>
 static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A, hipStream_t st) {
-    const int W = P.C / 64;
-#if IGT_DEV_KERNELS
-    if ((P.dev & DEV_LITERAL) && !VALUE && P.N <= LIT_MAX_N) {       // measurement variant: the literal wave-per-trajectory mapping
-        hipLaunchKernelGGL((search_literal_f64_kernel<CAND, HI>), dim3(B), dim3(64 * LIT_WAVES), 0, st, P, B, W, A.x0, A.u_prev,
-                           A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c);
-        return hipGetLastError();
-    }
-#endif
-    const size_t total = (size_t)B * W;
-    // 2 waves per SIMD (232 VGPRs, no spill); the 3-per-SIMD build spills 244 B/lane and is 3-8 % behind at every batch
-    // size (DEV_WAVES3 selects it for A/B runs)
-    const bool o3 = IGT_DEV_KERNELS && (P.dev & DEV_WAVES3) != 0;
-    // the slots bound the pools' batch; the waves launched leave a reserve when solves overlap (igt_launch.h search64_grid)
-    const size_t slots = search64_slots(A.n_cu, A.waves_per_simd, P.dev);
-    const size_t waves = search64_grid(A.n_cu, A.waves_per_simd, Search64::UNITS, P.dev, A.reserve_units);
-    const size_t grid = total < waves ? total : waves;
-    const unsigned* order = nullptr;
-    // lattice on live rows: one item per scenario, its candidates rolled as one pool by a wave whose lanes refill (search_pool64).
-    // An item is about four units long, and with fewer than four per wave the longest items make the span (one solve at a time,
-    // B = 4096: 2 per wave, search 0.208 -> 0.230 ms; four solves in flight, one wave per SIMD: 4 per wave, 23.6 -> 27.0 M solves/s)
-    const bool pools = !o3 && search_pools(P, CAND, VALUE, packs_live_rows(P, B, A)) && (size_t)B >= 4 * slots;
-    const int order_stride = ((B + 7) / 8) * (pools ? 1 : W);
-    if (!HI && search_is_static(P, B, A))
-        return launch_search_kernel(search_f64_kernel_cap<CAND, VALUE>, total, P, B, W, 0, order, order_stride, A, st, A.traj);
-    // the live-row masks and the checkpoint records live behind the partials (PartJTail): no further kernel argument -- the
-    // search kernels spill scalar registers as it is, and every one more shows up as v_readlane in the control-step loop
+    const Search64Plan& plan = A.plan;
+    const int W = plan.W;
+    const bool pools = plan.search_kernel == SearchKernel64::POOL;
     KP Pr = P;
-    if (!VALUE && emits_in_pieces(P, A)) Pr.dev |= DEV_LAUNCH_CKPT;
-    const unsigned long long* rows = nullptr;
-    bool queues_built = false;
+    Pr.dev |= plan.launch_dev_bits;      // what the kernel finds behind the partials (PartJTail)
     if constexpr (CAND != CAND_TABLE) {
-        if (packs_live_rows(P, B, A)) {
-            rows = A.row_mask;
+        if (plan.live_rows) {
             const int per_block = (ROWS_THREADS / 64) * (64 / P.G);    // scenarios per workgroup
             const int n_groups = (B + per_block - 1) / per_block;
-            // small batches: the same launch sorts the queues (longest units first)
-            queues_built = search_builds_queues(P, B, A) && !(P.dev & DEV_SEPARATE_QUEUES);
-            with_bool(queues_built, [&](auto queues) {
+            with_bool(plan.rows_build_queues, [&](auto queues) {
                 hipLaunchKernelGGL((accel_rows_kernel<CAND, queues()>), dim3(n_groups + (queues() ? 8 : 0)), dim3(ROWS_THREADS), 0, st,
                                    P, B, A.x0, A.u_prev, A.flags, A.cinf, A.centre(), A.row_mask, A.row_rems, W, A.kparams,
-                                   A.queue_order, order_stride, A.work_counter, pools ? W : 0);
+                                   A.queue_order, plan.order_stride, A.work_counter, pools ? W : 0);
             });
-            if (queues_built) order = A.queue_order;
-            Pr.dev |= DEV_LAUNCH_LIVE_ROWS;
         }
     }
-    if (!queues_built && search_builds_queues(P, B, A)) {    // small batches: longest units first
-        hipLaunchKernelGGL(build_queues_kernel<double>, dim3(8), dim3(QB_THREADS), 0, st, P, B, W, A.x0, A.kparams,
-                           A.queue_order, order_stride, A.work_counter, rows);
-        order = A.queue_order;
-    }
-    if (!HI && captures_trajectories(P, A))
-        return launch_search_kernel(search_f64_kernel_cap<CAND, VALUE>, grid, P, B, W, 8, order, order_stride, A, st, A.traj);
-    if constexpr (CAND == CAND_LATTICE && !VALUE) if (pools) {
-        const size_t pwaves = search64_grid(A.n_cu, A.waves_per_simd, Search64::POOL, P.dev, A.reserve_pool);
-        const size_t pgrid = (size_t)B < pwaves ? (size_t)B : pwaves;
+    if (plan.separate_queue_builder)
+        hipLaunchKernelGGL(build_queues_kernel<double>, dim3(8), dim3(QB_THREADS), 0, st, P, B, W, A.x0, A.kparams, A.queue_order,
+                           plan.order_stride, A.work_counter, plan.live_rows ? A.row_mask : nullptr);
+    const unsigned* order = plan.sorts_queues() ? A.queue_order : nullptr;
+    const auto search = [&](auto kernel, auto... more) {
+        return launch_search_kernel(kernel, plan.grid, Pr, B, W, plan.queues, order, plan.order_stride, A, st, more...);
+    };
+    switch (plan.search_kernel) {
+    case SearchKernel64::CAPTURE_STATIC:
+    case SearchKernel64::CAPTURE_QUEUES:
+        return search(search_f64_kernel_cap<CAND, VALUE>, A.traj);
+    case SearchKernel64::POOL:
         // with checkpoint records to leave (emit in pieces) the build that carries the slots; else the one without them
-        return with_bool((Pr.dev & DEV_LAUNCH_CKPT) != 0, [&](auto ckpt) {
-            return launch_search_kernel(search_f64_kernel_pool<CAND, HI, VALUE, NRK, ckpt()>, pgrid, Pr, B, W, 8, order,
-                                        order_stride, A, st);
-        });
-    }
+        if constexpr (CAND == CAND_LATTICE && !VALUE)
+            return with_bool((plan.launch_dev_bits & DEV_LAUNCH_CKPT) != 0,
+                             [&](auto ckpt) { return search(search_f64_kernel_pool<CAND, HI, VALUE, NRK, ckpt()>); });
+        break;
+    case SearchKernel64::UNITS:
+        // NRK = 4: the reference's discretisation (4 sub-steps, short polynomials) has its own build of the kernel
+        if constexpr (CAND == CAND_TRACK) return search(search_f64_kernel_o2w<CAND, HI, VALUE, NRK>);
+        else return search(search_f64_kernel_o2<CAND, HI, VALUE, NRK>);
 #if IGT_DEV_KERNELS
-    if (o3) return launch_search_kernel(search_f64_kernel_o3<CAND, HI, VALUE>, grid, Pr, B, W, 8, order, order_stride, A, st);
+    case SearchKernel64::UNITS_WAVES3:
+        return search(search_f64_kernel_o3<CAND, HI, VALUE>);
+    case SearchKernel64::LITERAL:
+        hipLaunchKernelGGL((search_literal_f64_kernel<CAND, HI>), dim3(plan.grid), dim3(64 * LIT_WAVES), 0, st, P, B, W, A.x0, A.u_prev,
+                           A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c);
+        return hipGetLastError();
 #endif
-    // NRK = 4: the reference's discretisation (4 sub-steps, short polynomials) has its own build of the kernel
-    if constexpr (CAND == CAND_TRACK)
-        return launch_search_kernel(search_f64_kernel_o2w<CAND, HI, VALUE, NRK>, grid, Pr, B, W, 8, order, order_stride, A, st);
-    else
-        return launch_search_kernel(search_f64_kernel_o2<CAND, HI, VALUE, NRK>, grid, Pr, B, W, 8, order, order_stride, A, st);
+    default:
+        break;
+    }
+    return hipErrorInvalidValue;      // a plan made for another family, cost or library
 }
 template <bool VALUE>
 static hipError_t dispatch_search64(const KP& P, int B, const SolveArgs<double>& A, hipStream_t st) {
 #if IGT_DEV_KERNELS
-    if (P.dev & DEV_EXACT64) return launch_search_exact<VALUE>(P, B, A, st);     // developer switch: oracle-order kernels
+    if (A.plan.search_kernel == SearchKernel64::ORACLE) return launch_search_exact<VALUE>(P, B, A, st);     // developer switch
 #endif
     return with_build(P, [&](auto cand, auto hi, auto nrk) { return launch_search64<cand(), hi(), nrk(), VALUE>(P, B, A, st); });
 }
@@ -1500,23 +1417,34 @@ hipError_t launch_search_records<double>(const KP& P, int B, const SolveArgs<dou
     return dispatch_search64<true>(P, B, A, st);
 }
 
+// emit: the kernel that A.plan names -- the same plan as the search pass's, which left the trajectories or the records it reads
 template <int CAND, bool HI, int NRK>
 static hipError_t launch_emit64(const KP& P, int B, int W, const SolveArgs<double>& A, hipStream_t st) {
-    if (!HI && captures_trajectories(P, A)) {
+    switch (A.plan.emit_kernel) {
+    case EmitKernel64::GATHER:
         hipLaunchKernelGGL((emit_gather_f64_kernel<CAND>), dim3(B), dim3(64), 0, st, P, B, W, A.part_J, A.part_c, A.traj, A.cost_out,
                            A.argmin_out, A.status_out, A.x_out, A.u_out);
-    } else if (emits_in_pieces(P, A)) {
-        const int S = seg_scenarios_per_block(P);
-        const size_t lds = (size_t)S * seg_doubles_per_scenario(P.N) * 8;
-        hipLaunchKernelGGL((emit_seg_f64_kernel<CAND, HI, NRK>), dim3((B + S - 1) / S), dim3(SEG_THREADS), lds, st, P, B, W, S, A.x0,
-                           A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.ck_records,
-                           A.cost_out, A.argmin_out, A.status_out, A.x_out, A.u_out);
-    } else {
+        break;
+    case EmitKernel64::PIECES: {
+        const int S = A.plan.seg_scenarios;
+        hipLaunchKernelGGL((emit_seg_f64_kernel<CAND, HI, NRK>), dim3((B + S - 1) / S), dim3(SEG_THREADS), A.plan.seg_lds_bytes, st, P,
+                           B, W, S, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c,
+                           A.ck_records, A.cost_out, A.argmin_out, A.status_out, A.x_out, A.u_out);
+        break;
+    }
+    case EmitKernel64::ONE_PIECE:
         hipLaunchKernelGGL((emit_f64_kernel<CAND, HI, NRK>), dim3((B + 63) / 64), dim3(64), 0, st, P, B, W, A.x0, A.u_prev, A.kparams,
                            A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.cost_out, A.argmin_out, A.status_out,
                            A.x_out, A.u_out);
+        break;
+    case EmitKernel64::ORACLE:      // launch_emit<double> has taken it
+        return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+template <class K>
+static hipError_t seg_lds_opt_in(K kernel) {      // once per instantiation and device (a function attribute)
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEG_LDS_MAX);
 }
 // dynamic LDS above 64 KB has to be asked for, per kernel and device: once per handle at igt_create -- not on the launch path,
 // which must stay a pure sequence of stream operations (stream capture).  The emit in pieces and the polish kernel: every build
@@ -1541,7 +1469,7 @@ hipError_t prepare_emit_kernels() {
 template <>
 hipError_t launch_emit<double>(const KP& P, int B, int W, const SolveArgs<double>& A, hipStream_t st) {
 #if IGT_DEV_KERNELS
-    if (P.dev & DEV_EXACT64) {     // developer switch: oracle-order kernels (argmin_out is already final there)
+    if (A.plan.emit_kernel == EmitKernel64::ORACLE) {     // developer switch: oracle-order kernels (argmin_out is already final there)
         hipLaunchKernelGGL((emit_kernel<ExactStepper<double>, double>), dim3((B + 63) / 64), dim3(64), 0, st, P, B, A.x0,
                            A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.argmin_out, A.x_out, A.u_out);
         return hipGetLastError();

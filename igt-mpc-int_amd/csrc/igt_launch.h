@@ -11,6 +11,210 @@ namespace igt {
 // trajectories kept by the search pass of a small double batch (igt_kernels_common.h CaptureSink)
 constexpr int TRAJ_FIELDS = 9;                    // the 7 states, then a and delta_f
 __host__ __device__ inline size_t traj_unit_doubles(int N) { return (size_t)TRAJ_FIELDS * (N + 1) * 64; }
+constexpr int CK_RECORD_DOUBLES = 24;             // igt_fast64.h (CK_PARTS - 1) * CK_FIELDS
+constexpr int QB_THREADS = 1024, QB_TRIPS = 2;    // build_queues_kernel: up to 2048 units per queue (B <= 8192 at W = 2)
+constexpr int LIT_MAX_N = 40;                     // search_literal_f64_kernel's LDS holds horizons up to this
+// emit_seg_f64_kernel stages this much per scenario in LDS; scenarios per workgroup: a full wave's 64 when their staging fits a
+// compute unit's LDS (116 KB at N = 20; 160 KB per CU, the kernel asks for more than the default 64 KB: seg_lds_opt_in), else
+// the largest power of two that does
+__host__ __device__ inline int seg_doubles_per_scenario(int N) { return 7 * (N + 1) + 4 * N; }
+constexpr size_t SEG_LDS_MAX = 150 * 1024;
+inline int seg_scenarios_per_block(int N) {
+    int S = 64;
+    while (S > 0 && (size_t)S * seg_doubles_per_scenario(N) * 8 > SEG_LDS_MAX) S >>= 1;
+    return S;
+}
+
+// ---- the grid of the persistent float64 search (plan_search64) ----
+// The wave slots a search may take: two waves per SIMD (three: the developer builds of DEV_WAVES3), or one where the caller has
+// announced three or more solves in flight (Search64Env::waves_per_simd == 1), so that two searches are resident side by side.
+// The pools' batch bound (B >= 4 * slots) is stated in these, reserve or not: which kernel runs does not depend on the reserve.
+inline size_t search64_slots(int n_cu, int waves_per_simd, int dev, bool dev_kernels = IGT_DEV_KERNELS) {
+    const bool o3 = dev_kernels && (dev & DEV_WAVES3) != 0;
+    return (size_t)n_cu * 4 * (o3 ? 3 : (waves_per_simd == 1 ? 1 : 2));
+}
+// The persistent waves a search launches.  With one wave per SIMD two resident searches take every slot of the chip between
+// them (the pool kernel's registers leave room for two waves per SIMD and no third).  From three solves in flight on a search
+// leaves `reserve` slots alone.  The waves dequeue their items, so a smaller grid gives each wave more items and nothing else
+// changes -- the same answers, bit for bit.  Measured with four solves in flight (profiles/slot_reserve_ab.txt, DESIGN section
+// 3): +4 % on the step rate with 32 of 1024 waves held back, less with 64 and 128, nothing with 256 -- though the other lanes'
+// emit and row passes, for which the reserve was meant, take as long as before: the search enqueued behind the two resident
+// ones takes the free slots and starts its longest items early.  With three in flight it costs 1.3 %.
+// reserve = n_cu * (waves per 8 compute units) / 8, by kernel family; the grid never goes below one wave per queue
+// (SEARCH64_QUEUES, one per XCD) while the chip has that many slots and never above the slots.  With one or two solves in
+// flight, with DEV_NO_RESERVE and for the DEV_WAVES3 builds: the slots.
+// reserve_per_8cu >= 0: the developer library's override for sweeps (IGT_DEV_RESERVE, IGT_DEV_RESERVE_UNITS; igt_api.hip).
+enum class Search64 { UNITS, POOL };       // search_f64_kernel_o2 / _o2w on 64-candidate units; search_f64_kernel_pool
+constexpr int SEARCH64_QUEUES = 8;
+constexpr int SEARCH64_RESERVE_PER_8CU_POOL = 1;       // 32 of 1024 waves at 256 compute units: the value that won the headline's sweep
+constexpr int SEARCH64_RESERVE_PER_8CU_UNITS = 0;      // the tracking family's gain (+3 %) stayed under three times its spread: the slots
+inline size_t search64_grid(int n_cu, int waves_per_simd, Search64 family, int dev, int reserve_per_8cu = -1,
+                            bool dev_kernels = IGT_DEV_KERNELS) {
+    const size_t slots = search64_slots(n_cu, waves_per_simd, dev, dev_kernels);
+    if (waves_per_simd != 1 || (dev & DEV_NO_RESERVE) || (dev_kernels && (dev & DEV_WAVES3))) return slots;
+    const int per8 = reserve_per_8cu >= 0 ? reserve_per_8cu
+                                          : (family == Search64::POOL ? SEARCH64_RESERVE_PER_8CU_POOL : SEARCH64_RESERVE_PER_8CU_UNITS);
+    const size_t reserve = (size_t)n_cu * (size_t)per8 / 8;
+    const size_t floor = slots < (size_t)SEARCH64_QUEUES ? slots : (size_t)SEARCH64_QUEUES;
+    return slots > reserve + floor ? slots - reserve : floor;
+}
+
+// ---- the plan of one float64 solve: what it runs, decided once on the host ----
+// plan_search64 states the search kernel, its prelude, the launch-time bits, the emit kernel, the workspace and the counter memset.
+// igt_api.hip solve_impl carves its workspace from the plan; launch_search64 / launch_emit64 (igt_kernels_f64.hip) switch on it.
+// Host code over KP and plain numbers, no pointers: tests/search_plan.cpp checks it without a GPU.
+enum class SearchKernel64 {
+    ORACLE,           // search_kernel<ExactStepper>: the oracle-order developer kernel (DEV_EXACT64)
+    LITERAL,          // search_literal_f64_kernel: the literal wave-per-trajectory mapping (DEV_LITERAL), a measurement variant
+    CAPTURE_STATIC,   // search_f64_kernel_cap, one wave per unit: no queues, no counters
+    CAPTURE_QUEUES,   // search_f64_kernel_cap on the queues
+    POOL,             // search_f64_kernel_pool: one item per scenario
+    UNITS_WAVES3,     // search_f64_kernel_o3: the 3-waves-per-SIMD developer builds (DEV_WAVES3)
+    UNITS,            // search_f64_kernel_o2 / _o2w (tracking family) on 64-candidate units
+};
+enum class EmitKernel64 {
+    ORACLE,           // emit_kernel<ExactStepper>
+    GATHER,           // emit_gather_f64_kernel: copies the winner out of the trajectories the search kept
+    PIECES,           // emit_seg_f64_kernel: rolls the winner in four pieces from the search's checkpoint records
+    ONE_PIECE,        // emit_f64_kernel
+};
+struct Search64Env {      // what the plan reads besides KP, the batch size and the cost
+    int n_cu;
+    int waves_per_simd;   // of the persistent search grid: 2, or 1 when solves overlap (igt_set_concurrency >= 3)
+    int reserve_pool = -1, reserve_units = -1;   // developer sweeps: search64_grid's reserve_per_8cu by kernel family (-1: the shipped values)
+    int dev_traj_max = -1;                       // developer sweeps (IGT_DEV_TRAJ_MAX): the batch size up to which trajectories are kept
+    bool dev_kernels = IGT_DEV_KERNELS;          // the library carries the developer kernels; without them igt_create refuses their flags
+};
+struct Search64Plan {
+    int W;                            // 64-candidate units per scenario
+    SearchKernel64 search_kernel;
+    size_t grid;                      // workgroups of the search kernel
+    int queues;                       // 8, or 0: every unit has a wave of its own
+    int order_stride;                 // entries per queue of the unit order (the pools' items are scenarios)
+    bool live_rows;                   // accel_rows_kernel runs: units of live acceleration rows only
+    bool rows_build_queues;           // ... and sorts the queues in the same launch
+    bool separate_queue_builder;      // build_queues_kernel runs
+    int launch_dev_bits;              // OR-ed into the search kernel's KP::dev (DEV_LAUNCH_CKPT, DEV_LAUNCH_LIVE_ROWS)
+    EmitKernel64 emit_kernel;
+    int seg_scenarios;                // PIECES: scenarios per workgroup ...
+    size_t seg_lds_bytes;             // ... and their dynamic LDS
+    // workspace to carve; 0: not taken.  Trajectories and queue order exactly where the chosen kernels touch them.
+    size_t traj_doubles;              // [B W][9][N+1][64] trajectories (the capture kinds -> GATHER)
+    size_t ck_records;                // [B W] checkpoint records of CK_RECORD_DOUBLES behind the partials (PIECES reads them)
+    size_t queue_order_words;         // [8][ceil(B/8) W] unit order of the queues (either queue builder)
+    bool memset_counters;             // the host zeroes the unit counters: queues that no builder zeroes
+    bool sorts_queues() const { return rows_build_queues || separate_queue_builder; }
+};
+
+// value: the pass writes per-candidate records for the value network (launch_search_records), else the progress cost.
+// P.refine_it is not read: one plan serves every refinement pass of a solve.
+inline Search64Plan plan_search64(const KP& P, int B, bool value, const Search64Env& env) {
+    Search64Plan p{};
+    const int W = p.W = P.C / 64;
+    const size_t total = (size_t)B * W;
+    p.order_stride = ((B + 7) / 8) * W;
+    if (env.dev_kernels && (P.dev & DEV_EXACT64)) {      // developer switch: oracle-order kernels, four scenarios per workgroup
+        p.search_kernel = SearchKernel64::ORACLE;
+        p.emit_kernel = EmitKernel64::ORACLE;
+        p.grid = ((size_t)B + 3) / 4;
+        return p;
+    }
+    if (env.dev_kernels && (P.dev & DEV_LITERAL) && !value && P.N <= LIT_MAX_N) {
+        p.search_kernel = SearchKernel64::LITERAL;
+        p.emit_kernel = EmitKernel64::ONE_PIECE;
+        p.grid = (size_t)B;
+        return p;
+    }
+    // 2 waves per SIMD (232 VGPRs, no spill); the 3-per-SIMD build spills 244 B/lane and is 3-8 % behind at every batch
+    // size (DEV_WAVES3 selects it for A/B runs)
+    const bool o3 = env.dev_kernels && (P.dev & DEV_WAVES3) != 0;
+
+    // Small batches -- no more units than the chip has SIMDs, B <= 256 at 256 candidates -- keep the trajectories of the search
+    // pass and emit copies the winner's (igt_kernels_common.h CaptureSink; 97 KB of stores per unit at N = 20, hidden behind a
+    // lone wave's dependent chains; with several units per SIMD they are not: a closed loop of 512 problems per step ran 0.32 ms
+    // per step with them against 0.30 without, 0.43 against 0.36 at 1024), when the kernel built for the reference's
+    // discretisation runs; DEV_NO_CAPTURE switches it off for A/B runs.
+    const size_t traj_max_units = env.dev_traj_max >= 0 ? (size_t)(env.dev_traj_max < 8192 ? env.dev_traj_max : 8192) * W   // sweeps: a batch size
+                                                        : (size_t)env.n_cu * 4;
+    const bool captures_trajectories = total <= traj_max_units && P.C % 64 == 0 && !P.hi_order && P.n_rk4 == 4 &&
+                                       !(P.dev & (DEV_WAVES3 | DEV_EXACT64 | DEV_LITERAL | DEV_NO_CAPTURE));
+    // ... and such a batch has no more units than the chip has SIMDs (the kernel that keeps trajectories holds one wave per
+    // SIMD), so every unit is given its own wave: the queue builder (6.6 us and a launch) would only order units that all start
+    // at once.  Measured, search + emit, tracking family: 67 us against 84 at B = 1, 91 against 101 at B = 32.
+    // DEV_KEEP_QUEUES keeps the queues for A/B runs; the unit trace (DEV_TRACE) needs them.
+    const bool search_is_static = captures_trajectories && total <= (size_t)env.n_cu * 4 && !(P.dev & (DEV_TRACE | DEV_KEEP_QUEUES));
+
+    // Small batches: the search queues are sorted longest unit first (build_queues_kernel, or inside accel_rows_kernel; 3-5 % up
+    // to B = 4096, nothing from 8192 on); the builder also zeroes the unit counters.
+    const bool search_builds_queues = !search_is_static && B <= 6144 && W <= 256 && ((B + 7) / 8) * W <= QB_THREADS * QB_TRIPS &&
+                                      !(P.dev & (DEV_NO_QUEUE_ORDER | DEV_EXACT64 | DEV_LITERAL));
+
+    // Emit rolls the winner in four pieces from the search pass's checkpoints (emit_seg_f64_kernel): progress cost (with the
+    // value network the winner is only known after the network has run), batches that do not keep trajectories, horizons of at
+    // least 8 steps.  Not when the caller overlaps solves (igt_set_concurrency >= 3): there the emit pass of one solve runs under
+    // the search pass of another, its latency is hidden, and what matters is that it gets on the chip between two persistent
+    // search kernels -- one 64-thread wave without LDS does, a 320-thread workgroup with 116 KB of LDS waits for a compute unit
+    // to drain (measured on one box, three runs each: 20.3 against 20.9 M solves/s with four solves in flight).
+    const int S = seg_scenarios_per_block(P.N);
+    const bool emits_in_pieces = !value && P.N >= 8 && !captures_trajectories && S >= 4 && env.waves_per_simd != 1 &&
+                                 !(P.dev & (DEV_WAVES3 | DEV_EXACT64 | DEV_LITERAL | DEV_NO_SEG_EMIT));
+
+    // The search runs on units made of live acceleration rows only (accel_rows_kernel; unit_layout).  Only for batches of more
+    // than two rounds of units (B > 1024 at 256 candidates): below that the solve lasts as long as its longest unit, fewer units
+    // do not shorten it, and the extra launch costs 8 us (a closed loop of 512 problems per step: 0.30 against 0.28 ms).
+    const bool packs_live_rows = P.cand_mode != CAND_TABLE && P.G <= 64 && P.G * P.G == P.C && W * 64 == P.C && P.G % W == 0 &&
+                                 !(P.dev & (DEV_NO_SLICES | DEV_EXACT64 | DEV_LITERAL | DEV_ALL_ROWS)) && !captures_trajectories &&
+                                 total > (size_t)env.n_cu * 16;
+
+    // Lattice on live rows: one item per scenario, its candidates rolled as one pool by a wave whose lanes refill (search_pool64):
+    // progress cost, the steering table of all G columns fits.  Every developer switch that changes the units' layout keeps the
+    // units (the A/B comparisons of the units stay what they were), and so does DEV_NO_REFILL; so do the queues sorted by
+    // build_queues_kernel (DEV_SEPARATE_QUEUES), which knows only units.
+    // An item is about four units long, and with fewer than four per wave the longest items make the span (one solve at a time,
+    // B = 4096: 2 per wave, search 0.208 -> 0.230 ms; four solves in flight, one wave per SIMD: 4 per wave, 23.6 -> 27.0 M solves/s).
+    // The slots bound the pools' batch; the waves launched leave a reserve when solves overlap (search64_grid).
+    const bool search_pools = !o3 && P.cand_mode == CAND_LATTICE && !value && packs_live_rows &&
+                              P.G * P.N <= STEER_TABLE_MAX_ENTRIES &&
+                              !(P.dev & (DEV_NO_SLICES | DEV_NO_EARLY_EXIT | DEV_NO_STEER_TABLE | DEV_ALL_ROWS | DEV_WHOLE_COLUMNS |
+                                         DEV_NO_REFILL | DEV_SEPARATE_QUEUES | DEV_WAVES3)) &&
+                              (size_t)B >= 4 * search64_slots(env.n_cu, env.waves_per_simd, P.dev, env.dev_kernels);
+
+    p.search_kernel = search_is_static        ? SearchKernel64::CAPTURE_STATIC
+                      : captures_trajectories ? SearchKernel64::CAPTURE_QUEUES
+                      : search_pools          ? SearchKernel64::POOL
+                      : o3                    ? SearchKernel64::UNITS_WAVES3
+                                              : SearchKernel64::UNITS;
+    p.emit_kernel = captures_trajectories ? EmitKernel64::GATHER : emits_in_pieces ? EmitKernel64::PIECES : EmitKernel64::ONE_PIECE;
+    if (search_is_static) {
+        p.grid = total;
+    } else {
+        const size_t items = search_pools ? (size_t)B : total;
+        const size_t waves = search64_grid(env.n_cu, env.waves_per_simd, search_pools ? Search64::POOL : Search64::UNITS, P.dev,
+                                           search_pools ? env.reserve_pool : env.reserve_units, env.dev_kernels);
+        p.grid = items < waves ? items : waves;
+        p.queues = SEARCH64_QUEUES;
+    }
+    if (search_pools) p.order_stride = (B + 7) / 8;
+    p.live_rows = packs_live_rows;
+    p.rows_build_queues = packs_live_rows && search_builds_queues && !(P.dev & DEV_SEPARATE_QUEUES);
+    p.separate_queue_builder = search_builds_queues && !p.rows_build_queues;
+    // the live-row masks and the checkpoint records live behind the partials (PartJTail): no further kernel argument -- the
+    // search kernels spill scalar registers as it is, and every one more shows up as v_readlane in the control-step loop
+    p.launch_dev_bits = (emits_in_pieces ? DEV_LAUNCH_CKPT : 0) | (packs_live_rows ? DEV_LAUNCH_LIVE_ROWS : 0);
+    if (emits_in_pieces) {
+        p.seg_scenarios = S;
+        p.seg_lds_bytes = (size_t)S * seg_doubles_per_scenario(P.N) * 8;
+    }
+    // The records are taken for every progress-cost solve of 8 steps or more, also where emit rolls in one piece and nothing
+    // touches them: behind the partials they set where part_c, the unit counters and the queue order lie, and without their
+    // 3 MB the headline (B = 4096, four solves in flight, emit in one piece) ran 0.1294 against 0.1272 ms per step, same device
+    // code (profiles/search_plan_identity.txt, section 4).
+    if (!value && P.N >= 8) p.ck_records = total;
+    if (captures_trajectories) p.traj_doubles = total * traj_unit_doubles(P.N);
+    if (search_builds_queues) p.queue_order_words = (size_t)((B + 7) / 8) * 8 * W;
+    p.memset_counters = !search_is_static && !search_builds_queues;
+    return p;
+}
 
 template <typename T>
 struct SolveArgs {   // all device pointers
@@ -43,7 +247,7 @@ struct SolveArgs {   // all device pointers
     unsigned* work_counter;         // the search's 8 unit counters, 256 B apart (zeroed before every launch); unit_trace behind them
     int n_cu;                       // compute units (sizes the persistent search grid)
     int waves_per_simd;             // of the persistent search grid: 2, or 1 when solves overlap (igt_set_concurrency); 0 = 2
-    int reserve_pool = -1, reserve_units = -1;   // developer sweeps: search64_grid's reserve_per_8cu by kernel family (-1: the shipped values)
+    Search64Plan plan;              // double path: what the search and emit launchers run (plan_search64)
     double* ckpt;                   // [ck_parts-1][B*Wk] horizon checkpoints of the search pass for emit (null: none)
     int ck_parts;                   // pieces the horizon is emitted in (igt_device.h Seg / Ckpt)
     unsigned* queue_order;          // [8][ceil(B/8) W] longest-first unit order of the search queues (null: index order)
@@ -60,7 +264,6 @@ struct SolveArgs {   // all device pointers
     double* row_rems;               // double path: [B G] the acceleration rows' travel sums (accel_rows_kernel)
     double* ck_records;             // double path: [B W][CK_RECORD_DOUBLES] unit winners' checkpoints for emit (null: none)
 };
-constexpr int CK_RECORD_DOUBLES = 24;   // igt_fast64.h (CK_PARTS - 1) * CK_FIELDS
 
 // What part_J holds behind its [B, W] partials:
 //   double path: [B] live-row masks, [B] incumbents, [B G] row travel sums, [B W][CK_RECORD_DOUBLES] checkpoint records
@@ -105,43 +308,7 @@ __host__ __device__ inline unsigned long long* unit_trace(unsigned* work_counter
     return reinterpret_cast<unsigned long long*>(work_counter + WORK_COUNTER_WORDS);
 }
 
-// ---- the grid of the persistent float64 search (launch_search64) ----
-// The wave slots a search may take: two waves per SIMD (three: the developer builds of DEV_WAVES3), or one where the caller has
-// announced three or more solves in flight (SolveArgs::waves_per_simd == 1), so that two searches are resident side by side.
-// The pools' batch bound (B >= 4 * slots) is stated in these, reserve or not: which kernel runs does not depend on the reserve.
-inline size_t search64_slots(int n_cu, int waves_per_simd, int dev) {
-    const bool o3 = IGT_DEV_KERNELS && (dev & DEV_WAVES3) != 0;
-    return (size_t)n_cu * 4 * (o3 ? 3 : (waves_per_simd == 1 ? 1 : 2));
-}
-// The persistent waves a search launches.  With one wave per SIMD two resident searches take every slot of the chip between
-// them (the pool kernel's registers leave room for two waves per SIMD and no third).  From three solves in flight on a search
-// leaves `reserve` slots alone.  The waves dequeue their items, so a smaller grid gives each wave more items and nothing else
-// changes -- the same answers, bit for bit.  Measured with four solves in flight (profiles/slot_reserve_ab.txt, DESIGN section
-// 3): +4 % on the step rate with 32 of 1024 waves held back, less with 64 and 128, nothing with 256 -- though the other lanes'
-// emit and row passes, for which the reserve was meant, take as long as before: the search enqueued behind the two resident
-// ones takes the free slots and starts its longest items early.  With three in flight it costs 1.3 %.
-// reserve = n_cu * (waves per 8 compute units) / 8, by kernel family; the grid never goes below one wave per queue
-// (SEARCH64_QUEUES, one per XCD) while the chip has that many slots and never above the slots.  With one or two solves in
-// flight, with DEV_NO_RESERVE and for the DEV_WAVES3 builds: the slots.
-// reserve_per_8cu >= 0: the developer library's override for sweeps (IGT_DEV_RESERVE, IGT_DEV_RESERVE_UNITS; igt_api.hip).
-enum class Search64 { UNITS, POOL };       // search_f64_kernel_o2 / _o2w on 64-candidate units; search_f64_kernel_pool
-constexpr int SEARCH64_QUEUES = 8;
-constexpr int SEARCH64_RESERVE_PER_8CU_POOL = 1;       // 32 of 1024 waves at 256 compute units: the value that won the headline's sweep
-constexpr int SEARCH64_RESERVE_PER_8CU_UNITS = 0;      // the tracking family's gain (+3 %) stayed under three times its spread: the slots
-inline size_t search64_grid(int n_cu, int waves_per_simd, Search64 family, int dev, int reserve_per_8cu = -1) {
-    const size_t slots = search64_slots(n_cu, waves_per_simd, dev);
-    if (waves_per_simd != 1 || (dev & DEV_NO_RESERVE) || (IGT_DEV_KERNELS && (dev & DEV_WAVES3))) return slots;
-    const int per8 = reserve_per_8cu >= 0 ? reserve_per_8cu
-                                          : (family == Search64::POOL ? SEARCH64_RESERVE_PER_8CU_POOL : SEARCH64_RESERVE_PER_8CU_UNITS);
-    const size_t reserve = (size_t)n_cu * (size_t)per8 / 8;
-    const size_t floor = slots < (size_t)SEARCH64_QUEUES ? slots : (size_t)SEARCH64_QUEUES;
-    return slots > reserve + floor ? slots - reserve : floor;
-}
-
 bool search_builds_queues(const KP& P, int B, const SolveArgs<float>& A);   // then no memset of the counters is needed
-bool search_builds_queues(const KP& P, int B, const SolveArgs<double>& A);
-bool search_is_static(const KP& P, int B, const SolveArgs<double>& A);      // one wave per unit: no queues, no counters
-inline bool search_is_static(const KP&, int, const SolveArgs<float>&) { return false; }
 template <typename T> hipError_t launch_search(const KP& P, int B, const SolveArgs<T>& A, int nc, hipStream_t st);
 template <typename T> hipError_t launch_emit(const KP& P, int B, int W, const SolveArgs<T>& A, hipStream_t st);
 // value-net cost: search pass that writes per-candidate records, then prep + MLP + per-chunk arg-min

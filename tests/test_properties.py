@@ -55,19 +55,28 @@ def test_argmin_does_not_depend_on_the_order_of_the_candidates(seed, order_seed)
        shift=st.floats(-20, 20))
 def test_filter_preds_depends_on_the_relative_pose_only(x, y, h, ox, oy, shift):
     """utils.py:365-388: the verdict is the sign of (p_obs - p_ego) . (cos psi, sin psi): translating both vehicles by the
-    same vector changes nothing, and an obstacle mirrored through the ego lands on the other side."""
+    same vector changes nothing, and an obstacle mirrored through the ego lands on the other side.
+    Whether the filter moved the obstacle is read at step 1 of the horizon, which every scene here holds at 7: the verdict reads
+    the current position alone and moves the whole horizon, and a drawn coordinate may itself be -20 (ox = -20 in front of the
+    ego used to count as moved)."""
     from igtmpc import routes as R
-    obs = np.zeros((1, 1, 2, 5)); obs[0, 0, 0] = ox; obs[0, 0, 1] = oy
+    def scene(px, py):
+        o = np.full((1, 1, 2, 5), 7.0); o[0, 0, 0, 0] = px; o[0, 0, 1, 0] = py
+        return o
+    moved = lambda out: out[0, 0, 0, 1] == -20.0 and (out[0, 0] == -20.0).all()
+    kept = lambda out, inp: np.array_equal(out, inp)
+    obs = scene(ox, oy)
     a = R.filter_preds(np.array([[x, y]]), np.array([h]), obs)
-    sh = obs + shift
+    sh = scene(ox + shift, oy + shift)
     b2 = R.filter_preds(np.array([[x + shift, y + shift]]), np.array([h]), sh)
+    assert moved(a) != kept(a, obs) and moved(b2) != kept(b2, sh)  # all of the horizon moved, or nothing touched
     dot = (ox - x) * np.cos(h) + (oy - y) * np.sin(h)
     if abs(dot) > 1e-6:                                           # away from the boundary the shifted scene decides alike
-        assert (a[0, 0, 0, 0] == -20.0) == (b2[0, 0, 0, 0] == -20.0)
-        mirrored = np.zeros_like(obs); mirrored[0, 0, 0] = 2 * x - ox; mirrored[0, 0, 1] = 2 * y - oy
+        assert moved(a) == moved(b2)
+        mirrored = scene(2 * x - ox, 2 * y - oy)
         c = R.filter_preds(np.array([[x, y]]), np.array([h]), mirrored)
-        assert (a[0, 0, 0, 0] == -20.0) != (c[0, 0, 0, 0] == -20.0)
-        assert (a[0, 0, 0, 0] == -20.0) == (dot < 0)
+        assert moved(a) != moved(c)
+        assert moved(a) == (dot < 0)
 
 
 @SET

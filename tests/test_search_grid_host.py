@@ -5,7 +5,6 @@ under the address and undefined-behaviour sanitizers and run: n_cu in {1, 8, 256
 (DEV_NO_RESERVE) on and off, both kernel families, every reserve of a sweep -- the grid never 0, never above the slots, the slots
 themselves below three in flight, and the pools' batch bound (B >= 4 * slots) untouched.  No GPU."""
 import os
-import re
 import shutil
 import subprocess
 
@@ -30,19 +29,6 @@ def test_search_grid_keeps_its_bounds(tmp_path):
     assert r.returncode == 0, r.stderr
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.strip() == 'search grid ok', r.stdout + r.stderr
-
-
-def test_both_launch_sites_take_their_grid_from_the_one_function():
-    """launch_search64 forms no grid of its own: the unit kernels' and the pool kernel's come from search64_grid, the pools' batch
-    bound from search64_slots (the unreserved slots), and nothing else in the float64 launchers multiplies n_cu out again."""
-    src = open(os.path.join(CSRC, 'igt_kernels_f64.hip')).read()
-    body = src[src.index('static hipError_t launch_search64('):src.index('static hipError_t dispatch_search64(')]
-    assert body.count('search64_grid(') == 2
-    assert 'search64_grid(A.n_cu, A.waves_per_simd, Search64::UNITS, P.dev' in body
-    assert 'search64_grid(A.n_cu, A.waves_per_simd, Search64::POOL, P.dev' in body
-    assert re.search(r'const size_t slots = search64_slots\(A\.n_cu, A\.waves_per_simd, P\.dev\);', body)
-    assert re.search(r'const bool pools = .*\(size_t\)B >= 4 \* slots;', body)
-    assert 'n_cu*4' not in body.replace(' ', '')
 
 
 def test_the_switch_is_the_next_free_bit_and_is_documented():
