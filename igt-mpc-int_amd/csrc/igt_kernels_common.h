@@ -202,7 +202,7 @@ __device__ __forceinline__ int units_of_live_rows(const KP& P, int W, unsigned l
 constexpr int QC = 8;     // QB_THREADS, QB_TRIPS (igt_launch.h): up to 2048 units per queue (B <= 8192 at W = 2)
 // The body for one queue q, run by one workgroup of QB_THREADS_ threads in QB_TRIPS_ trips (QB_THREADS_ * QB_TRIPS_ = 2048): the
 // stand-alone kernel below takes 1024 x 2; the float64 prelude (igt_kernels_f64.hip accel_rows_kernel, whose first eight
-// workgroups sort the queues while the others roll the acceleration rows) 256 x 8.
+// workgroups sort the queues while the others roll the acceleration rows) 256 x 8, or 64 x 32 where its workgroups are one wave.
 // row_mask: the scenarios' live acceleration rows when they are known at this point (a slice beyond the live rows' units is
 // a hole and sorts last); null: not known -- such slices are sorted as if they held candidates and the search skips them
 // when it gets there.  by_rows: the tracking family's units are cut along the acceleration axis (unit-rank-major order).
@@ -214,13 +214,14 @@ __device__ __forceinline__ void build_queue(const KP& P, int B, int W, int q, co
                                             unsigned* __restrict__ work_counter,
                                             const unsigned long long* __restrict__ row_mask, bool by_rows, int pool_units = 0) {
     constexpr int QB_THREADS = QB_THREADS_, QB_TRIPS = QB_TRIPS_;
+    constexpr int CLS_UNROLL = QB_THREADS <= 64 ? 4 : 2;      // one wave: more scenarios' loads in flight per trip of step 1
     __shared__ int cnt[QB_TRIPS][QB_THREADS / 64][QC];   // [trip][wave][class] counts, then exclusive offsets
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (tid == 0) work_counter[q * 64] = 0u;             // this queue's unit counter (saves the memset node)
     const int n_scen = (B + 7) / 8, n = n_scen * W;
     // 1. the classes, one thread per scenario (its W units share what is read of it): cls_s[j W + p]
     __shared__ unsigned char cls_s[QB_THREADS * QB_TRIPS];
-#pragma unroll 2
+#pragma unroll CLS_UNROLL
     for (int j = tid; j < n_scen; j += QB_THREADS) {
         const int b = queue_scenario(q, j);
         int nu = 0;                                      // a hole of the last block of 8: sorts last, skipped by the search
@@ -257,13 +258,16 @@ __device__ __forceinline__ void build_queue(const KP& P, int B, int W, int q, co
     }
     __syncthreads();
     // 2. an item's class and its rank among its wave's items of that class: in registers over two trips; over more (the
-    // prelude's 256 threads) in LDS, the trips not unrolled
+    // prelude's 256 or 64 threads) in LDS, the trips not unrolled
     constexpr bool IN_LDS = QB_TRIPS > 2;
     constexpr int UNROLL = IN_LDS ? 1 : QB_TRIPS;
+    // the trips that hold items: all of them in registers (unrolled); in LDS those below n (a pool queue of B = 4096 holds 512
+    // items -- 8 trips of one wave, not 32)
+    const int n_trips = IN_LDS ? min((n + QB_THREADS - 1) / QB_THREADS, QB_TRIPS) : QB_TRIPS;
     __shared__ unsigned short cls_rank[IN_LDS ? QB_THREADS * QB_TRIPS : 1];
     int cls[IN_LDS ? 1 : QB_TRIPS], rank[IN_LDS ? 1 : QB_TRIPS];
 #pragma unroll UNROLL
-    for (int t = 0; t < QB_TRIPS; ++t) {
+    for (int t = 0; t < n_trips; ++t) {
         const int i = t * QB_THREADS + tid;
         const int c = i < n ? (int)cls_s[i] : -1;
         int r = 0;
@@ -280,13 +284,13 @@ __device__ __forceinline__ void build_queue(const KP& P, int B, int W, int q, co
     __shared__ int total[QC];
     if (tid < QC) {          // per class: exclusive offsets in index order (trip, wave), and the class total
         int run = 0;
-        for (int t = 0; t < QB_TRIPS; ++t)
+        for (int t = 0; t < n_trips; ++t)
             for (int w2 = 0; w2 < QB_THREADS / 64; ++w2) { const int v = cnt[t][w2][tid]; cnt[t][w2][tid] = run; run += v; }
         total[tid] = run;
     }
     __syncthreads();
 #pragma unroll UNROLL
-    for (int t = 0; t < QB_TRIPS; ++t) {
+    for (int t = 0; t < n_trips; ++t) {
         int c, r;
         if constexpr (IN_LDS) { const int cr = cls_rank[t * QB_THREADS + tid]; c = (cr >> 8) == 15 ? -1 : (cr >> 8); r = cr & 255; }
         else { c = cls[t]; r = rank[t]; }

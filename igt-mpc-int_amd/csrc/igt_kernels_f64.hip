@@ -188,9 +188,13 @@ __global__ __launch_bounds__(256) void rollout_all_kernel(KP P, int B, const T* 
 // its class and the search wave that takes it finds it empty and moves on.  (Sorting them last needs the masks first: as
 // a second launch that is the 7 us; inside this one it was built with tickets and a device-scope fence per workgroup and
 // cost 20 us, profiles/r04_ab_fused_prelude.txt.)
-constexpr int ROWS_THREADS = 256, ROWS_QB_TRIPS = QB_THREADS * QB_TRIPS / ROWS_THREADS;
-template <int CAND, bool QUEUES>
-__global__ __launch_bounds__(ROWS_THREADS) void accel_rows_kernel(KP P, int B, const double* __restrict__ x0,
+//
+// THREADS: the workgroup.  ROWS_THREADS_WIDE (four waves; the queue builders take up to eight trips of 256 threads), or -- where
+// solves overlap, igt_launch.h plan_search64 rows_threads -- ROWS_THREADS_NARROW: one wave, which starts wherever a single wave
+// slot is free beside the resident searches (the builders then take up to 32 trips of 64 threads: the same stable sort, the
+// same order table).  The lane mapping is the same either way.
+template <int CAND, bool QUEUES, int THREADS>
+__global__ __launch_bounds__(THREADS) void accel_rows_kernel(KP P, int B, const double* __restrict__ x0,
                                                          const double* __restrict__ u_prev, const uint32_t* __restrict__ flags,
                                                          const double* __restrict__ cinf, Centre<double> cpar,
                                                          unsigned long long* __restrict__ row_mask, double* __restrict__ row_rem,
@@ -198,14 +202,14 @@ __global__ __launch_bounds__(ROWS_THREADS) void accel_rows_kernel(KP P, int B, c
                                                          int order_stride, unsigned* __restrict__ work_counter, int pool_units) {
     if constexpr (QUEUES) {
         if (blockIdx.x < 8) {      // pool_units > 0: one item per scenario (search_pool64)
-            build_queue<double, ROWS_THREADS, ROWS_QB_TRIPS>(P, B, pool_units > 0 ? 1 : W, (int)blockIdx.x, x0, kparams, order,
-                                                             order_stride, work_counter, nullptr, true, pool_units);
+            build_queue<double, THREADS, QB_THREADS * QB_TRIPS / THREADS>(P, B, pool_units > 0 ? 1 : W, (int)blockIdx.x, x0, kparams,
+                                                                         order, order_stride, work_counter, nullptr, true, pool_units);
             return;
         }
     }
     const int lane = threadIdx.x & 63, lg = __ffs(P.G) - 1;                  // G is a power of two (igt_api.hip)
     const int per_wave = 64 >> lg;                                           // scenarios per wave
-    const int wave = ((int)blockIdx.x - (QUEUES ? 8 : 0)) * (ROWS_THREADS / 64) + (int)(threadIdx.x >> 6);
+    const int wave = ((int)blockIdx.x - (QUEUES ? 8 : 0)) * (THREADS / 64) + (int)(threadIdx.x >> 6);
     const int b = wave * per_wave + (lane >> lg), i = lane & (P.G - 1);
     bool live = false;
     if (b < B) {
@@ -1358,13 +1362,16 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
     Pr.dev |= plan.launch_dev_bits;      // what the kernel finds behind the partials (PartJTail)
     if constexpr (CAND != CAND_TABLE) {
         if (plan.live_rows) {
-            const int per_block = (ROWS_THREADS / 64) * (64 / P.G);    // scenarios per workgroup
-            const int n_groups = (B + per_block - 1) / per_block;
-            with_bool(plan.rows_build_queues, [&](auto queues) {
-                hipLaunchKernelGGL((accel_rows_kernel<CAND, queues()>), dim3(n_groups + (queues() ? 8 : 0)), dim3(ROWS_THREADS), 0, st,
-                                   P, B, A.x0, A.u_prev, A.flags, A.cinf, A.centre(), A.row_mask, A.row_rems, W, A.kparams,
-                                   A.queue_order, plan.order_stride, A.work_counter, pools ? W : 0);
-            });
+            const int n_groups = rows_groups(B, plan.rows_threads, P.G);
+            const auto rows = [&](auto threads) {
+                with_bool(plan.rows_build_queues, [&](auto queues) {
+                    hipLaunchKernelGGL((accel_rows_kernel<CAND, queues(), threads()>), dim3(n_groups + (queues() ? 8 : 0)), dim3(threads()),
+                                       0, st, P, B, A.x0, A.u_prev, A.flags, A.cinf, A.centre(), A.row_mask, A.row_rems, W, A.kparams,
+                                       A.queue_order, plan.order_stride, A.work_counter, pools ? W : 0);
+                });
+            };
+            if (plan.rows_threads == ROWS_THREADS_NARROW) rows(std::integral_constant<int, ROWS_THREADS_NARROW>{});
+            else rows(std::integral_constant<int, ROWS_THREADS_WIDE>{});
         }
     }
     if (plan.separate_queue_builder)

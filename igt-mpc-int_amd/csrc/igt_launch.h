@@ -59,6 +59,16 @@ inline size_t search64_grid(int n_cu, int waves_per_simd, Search64 family, int d
     return slots > reserve + floor ? slots - reserve : floor;
 }
 
+// ---- the workgroups of the acceleration-row pass (igt_kernels_f64.hip accel_rows_kernel) ----
+// One lane per (scenario, row), 64 / G scenarios per wave; workgroups of ROWS_THREADS_WIDE threads, or -- plan_search64
+// rows_threads -- of one wave.  What the launcher and the kernel both count with:
+constexpr int ROWS_THREADS_WIDE = 256, ROWS_THREADS_NARROW = 64;
+inline int rows_scenarios_per_block(int threads, int G) { return (threads / 64) * (64 / G); }
+inline int rows_groups(int B, int threads, int G) {      // row workgroups (the queue builders come on top)
+    const int per_block = rows_scenarios_per_block(threads, G);
+    return (B + per_block - 1) / per_block;
+}
+
 // ---- the plan of one float64 solve: what it runs, decided once on the host ----
 // plan_search64 states the search kernel, its prelude, the launch-time bits, the emit kernel, the workspace and the counter memset.
 // igt_api.hip solve_impl carves its workspace from the plan; launch_search64 / launch_emit64 (igt_kernels_f64.hip) switch on it.
@@ -93,6 +103,7 @@ struct Search64Plan {
     int order_stride;                 // entries per queue of the unit order (the pools' items are scenarios)
     bool live_rows;                   // accel_rows_kernel runs: units of live acceleration rows only
     bool rows_build_queues;           // ... and sorts the queues in the same launch
+    int rows_threads = ROWS_THREADS_WIDE;   // ... in workgroups of this many threads: ROWS_THREADS_WIDE, or ROWS_THREADS_NARROW when solves overlap
     bool separate_queue_builder;      // build_queues_kernel runs
     int launch_dev_bits;              // OR-ed into the search kernel's KP::dev (DEV_LAUNCH_CKPT, DEV_LAUNCH_LIVE_ROWS)
     EmitKernel64 emit_kernel;
@@ -198,6 +209,11 @@ inline Search64Plan plan_search64(const KP& P, int B, bool value, const Search64
     p.live_rows = packs_live_rows;
     p.rows_build_queues = packs_live_rows && search_builds_queues && !(P.dev & DEV_SEPARATE_QUEUES);
     p.separate_queue_builder = search_builds_queues && !p.rows_build_queues;
+    // Solves that overlap (igt_set_concurrency >= 3): the row pass runs beside two resident searches that hold nearly every wave
+    // slot, and a workgroup starts only where ONE compute unit has all its waves' slots free at once.  One-wave workgroups: row
+    // pass 106 -> 50 us under overlap, headline +7.3 % with the builder's empty trips gone, tracking family +6.2 %
+    // (profiles/rows_shape_ab.txt); DEV_WIDE_ROWS keeps the 256 threads for A/B runs.
+    p.rows_threads = packs_live_rows && env.waves_per_simd == 1 && !(P.dev & DEV_WIDE_ROWS) ? ROWS_THREADS_NARROW : ROWS_THREADS_WIDE;
     // the live-row masks and the checkpoint records live behind the partials (PartJTail): no further kernel argument -- the
     // search kernels spill scalar registers as it is, and every one more shows up as v_readlane in the control-step loop
     p.launch_dev_bits = (emits_in_pieces ? DEV_LAUNCH_CKPT : 0) | (packs_live_rows ? DEV_LAUNCH_LIVE_ROWS : 0);
