@@ -38,6 +38,7 @@ enum DevFlag : int {
     DEV_NO_QUEUE_ORDER = 16,           // the search queues in index order, not longest unit first
     DEV_WAVES3 = 32,                   // developer kernels: the 3-waves-per-SIMD builds of the search
     DEV_WIDE_ROWS = 64,                // float64, three or more solves in flight: accel_rows_kernel keeps its 256-thread workgroups (plan_search64 rows_threads)
+    DEV_EMIT_PRIO0 = 128,              // float64 pool search, three or more solves in flight: emit_f64_kernel stays at wave priority 0 (plan_search64 emit_priority)
     DEV_TRACE = 256,                   // unit trace (written to $IGT_DEV_TRACE; unit_trace)
     DEV_NO_STEAL = 512,                // a wave takes units from its own queue only
     DEV_EXACT64 = 1024,                // developer kernels: the oracle-order float64 kernels

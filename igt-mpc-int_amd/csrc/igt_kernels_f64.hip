@@ -569,7 +569,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 
 // one lane per scenario: final arg-min over the W partials, then the winner re-rolled with the same arithmetic
 // (general sub-step variant: the lanes of the wave belong to different scenarios) -> x*[7,N+1], u*[2,N]
-template <int CAND, bool HI, int NRK>
+// PRIO > 0 (igt_launch.h plan_search64 emit_priority): beside resident search waves this wave is the youngest on its SIMD and gets
+// the issue slots they leave; it raises its priority once, before anything else, and keeps it.  A build of its own, not a
+// run-time condition: s_setprio ignores EXEC and must not sit under a branch the compiler cannot prove wave-uniform, and the
+// PRIO = 0 build stays the code it was.
+template <int CAND, bool HI, int NRK, int PRIO = 0>
 __global__ __launch_bounds__(64) void emit_f64_kernel(KP P, int B, int W, const double* __restrict__ x0,
                                                       const double* __restrict__ u_prev,
                                                       const double* __restrict__ kparams,
@@ -579,6 +583,7 @@ __global__ __launch_bounds__(64) void emit_f64_kernel(KP P, int B, int W, const 
                                                       const int32_t* __restrict__ part_c, double* __restrict__ cost_out,
                                                       int32_t* __restrict__ argmin_out, int32_t* __restrict__ status_out,
                                                       double* __restrict__ x_out, double* __restrict__ u_out) {
+    if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(PRIO);
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     double bestJ = 0.0;
@@ -1439,11 +1444,18 @@ static hipError_t launch_emit64(const KP& P, int B, int W, const SolveArgs<doubl
                            A.ck_records, A.cost_out, A.argmin_out, A.status_out, A.x_out, A.u_out);
         break;
     }
-    case EmitKernel64::ONE_PIECE:
-        hipLaunchKernelGGL((emit_f64_kernel<CAND, HI, NRK>), dim3((B + 63) / 64), dim3(64), 0, st, P, B, W, A.x0, A.u_prev, A.kparams,
-                           A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.cost_out, A.argmin_out, A.status_out,
-                           A.x_out, A.u_out);
-        break;
+    case EmitKernel64::ONE_PIECE: {
+        const auto emit = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((B + 63) / 64), dim3(64), 0, st, P, B, W, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table,
+                               A.cinf, A.centre(), A.part_J, A.part_c, A.cost_out, A.argmin_out, A.status_out, A.x_out, A.u_out);
+        };
+        // the build that raises its wave priority: asked for behind the pool search alone (plan_search64 emit_priority), so the
+        // lattice's emit alone has it.  No per-kernel setup depends on the build (prepare_emit_kernels: emit in pieces and polish).
+        if (A.plan.emit_priority == 0) { emit(emit_f64_kernel<CAND, HI, NRK>); break; }
+        if constexpr (CAND == CAND_LATTICE)
+            if (A.plan.emit_priority == EMIT_PRIORITY_OVERLAP) { emit(emit_f64_kernel<CAND, HI, NRK, EMIT_PRIORITY_OVERLAP>); break; }
+        return hipErrorInvalidValue;      // a plan made for another family or library
+    }
     case EmitKernel64::ORACLE:      // launch_emit<double> has taken it
         return hipErrorInvalidValue;
     }

@@ -95,6 +95,7 @@ struct Search64Env {      // what the plan reads besides KP, the batch size and 
     int dev_traj_max = -1;                       // developer sweeps (IGT_DEV_TRAJ_MAX): the batch size up to which trajectories are kept
     bool dev_kernels = IGT_DEV_KERNELS;          // the library carries the developer kernels; without them igt_create refuses their flags
 };
+constexpr int EMIT_PRIORITY_OVERLAP = 3;         // s_setprio level of the one-piece emit beside resident searches (plan_search64 emit_priority)
 struct Search64Plan {
     int W;                            // 64-candidate units per scenario
     SearchKernel64 search_kernel;
@@ -114,6 +115,7 @@ struct Search64Plan {
     size_t ck_records;                // [B W] checkpoint records of CK_RECORD_DOUBLES behind the partials (PIECES reads them)
     size_t queue_order_words;         // [8][ceil(B/8) W] unit order of the queues (either queue builder)
     bool memset_counters;             // the host zeroes the unit counters: queues that no builder zeroes
+    int emit_priority;                // ONE_PIECE: the wave priority emit_f64_kernel sets at its top (0: none)
     bool sorts_queues() const { return rows_build_queues || separate_queue_builder; }
 };
 
@@ -214,6 +216,20 @@ inline Search64Plan plan_search64(const KP& P, int B, bool value, const Search64
     // pass 106 -> 50 us under overlap, headline +7.3 % with the builder's empty trips gone, tracking family +6.2 %
     // (profiles/rows_shape_ab.txt); DEV_WIDE_ROWS keeps the 256 threads for A/B runs.
     p.rows_threads = packs_live_rows && env.waves_per_simd == 1 && !(P.dev & DEV_WIDE_ROWS) ? ROWS_THREADS_NARROW : ROWS_THREADS_WIDE;
+    // The one-piece emit of overlapping solves: one wave per 64 scenarios, each a single dependent chain of some 27 000
+    // instructions, and always the youngest wave on a SIMD that holds one or two persistent search waves -- VALU issue goes by
+    // priority, then age, so it gets the slots the searches leave: 49 us alone on the chip, 162 us beside them.  Behind the pool
+    // search the wave raises its priority once at its top (s_setprio, never lowered; emit_f64_kernel PRIO): the chain issues
+    // every few cycles at the most, the searches keep the rest, the work done is the same.
+    // Measured (profiles/rows_in_search_ab.txt; five alternating runs a side): headline 34.75 -> 35.77 M solves/s
+    // (+2.9 %, every run above every parent run, parent spread 0.33 %), three in flight 30.51 -> 34.39 (+12.7 %); emit under
+    // overlap 160 -> 109 us, pool search 269 -> 285, row pass 50 -> 80 (sum 480 -> 474).  Levels 1, 2 and 3 gave one figure --
+    // the searches stay at 0 -- so it is 3.  Pool search only: the tracking family's emit fell as well (281 -> 267 us) but its
+    // unit search paid more than that, -0.9 % on the step, so the 64-candidate units keep priority 0 and only the lattice's
+    // emit has the raised build.
+    // DEV_EMIT_PRIO0 keeps priority 0 for A/B runs.
+    p.emit_priority = search_pools && p.emit_kernel == EmitKernel64::ONE_PIECE && env.waves_per_simd == 1 && !(P.dev & DEV_EMIT_PRIO0)
+                          ? EMIT_PRIORITY_OVERLAP : 0;
     // the live-row masks and the checkpoint records live behind the partials (PartJTail): no further kernel argument -- the
     // search kernels spill scalar registers as it is, and every one more shows up as v_readlane in the control-step loop
     p.launch_dev_bits = (emits_in_pieces ? DEV_LAUNCH_CKPT : 0) | (packs_live_rows ? DEV_LAUNCH_LIVE_ROWS : 0);

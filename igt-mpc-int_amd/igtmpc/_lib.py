@@ -96,6 +96,7 @@ DEV_NO_STEER_TABLE = 4
 DEV_NO_QUEUE_ORDER = 16
 DEV_WAVES3 = 32
 DEV_WIDE_ROWS = 64
+DEV_EMIT_PRIO0 = 128
 DEV_TRACE = 256
 DEV_NO_STEAL = 512
 DEV_EXACT64 = 1024
