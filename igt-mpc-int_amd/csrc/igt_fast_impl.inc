@@ -55,13 +55,14 @@ __device__ __forceinline__ void rotate2(f2& s, f2& c, f2 sd, f2 cd) {
 template <bool HI_ORDER>
 struct FastPair {
     // per-scenario constants
-    float h, hh, h6, kv, inv_lr, lr_ratio, big;
+    float h, hh, h6, kv, kvz, inv_lr, lr_ratio, big;
     double b0, b1, dt;
     int n_rk4;
 
     __device__ __forceinline__ void init(const KP& P, double b0_, double b1_, double kv_) {
         h = (float)P.h; hh = (float)(P.h / 2); h6 = (float)(P.h / 6);
         kv = (float)kv_; inv_lr = (float)(1.0 / P.l_r); lr_ratio = (float)P.lr_ratio;
+        kvz = fabsf(kv) < INFINITY ? kv : 0.0f;      // kv where the arc's share is 0 (arc_curv): kv itself unless it is non-finite
         big = 1.2676506e30f;      // 2^100
         b0 = b0_; b1 = b1_; dt = P.dt; n_rk4 = P.n_rk4;
     }
@@ -72,6 +73,15 @@ struct FastPair {
     static __device__ __forceinline__ void ssc_half(f2 d, f2& sd, f2& cd) {
         if (HI_ORDER) small_sincos2(d, sd, cd); else tiny_sincos2(d, sd, cd);
     }
+    // K = kv [s >= b0] - kv [s >= b1] from the share d = [s >= b0] - [s >= b1] of the arc (0, 1, or a fraction within 2^-100 of a
+    // break-point).  d kv as it stands would make 0 * kv = NaN of a non-finite kv BEFORE its arc, where pw_const (mpc.py:199)
+    // and the whole-step variant say K = 0; with d = 0 the factor is kvz.  A finite kv has kvz = kv: the product's own bits.
+    __device__ __forceinline__ f2 arc_curv(f2 d) const {
+        f2 K;
+#pragma unroll
+        for (int q = 0; q < NV; ++q) K[q] = d[q] * (d[q] == 0.0f ? kvz : kv);
+        return K;
+    }
     // curvature of both candidates at break-point-relative arguments e + o*2^100
     __device__ __forceinline__ f2 curv(f2 e0, f2 e1, f2 o) const {
         // scalar v_fma_f32 ... clamp (the packed form cannot carry the clamp the compiler folds in)
@@ -81,7 +91,7 @@ struct FastPair {
             c0[q] = __builtin_amdgcn_fmed3f(fmaf(o[q], big, e0[q]), 0.0f, 1.0f);
             c1[q] = __builtin_amdgcn_fmed3f(fmaf(o[q], big, e1[q]), 0.0f, 1.0f);
         }
-        return (c0 - c1) * splat(kv);
+        return arc_curv(c0 - c1);
     }
 
     // One RK4 sub-step, general curvature.  In/out: base pairs (s1,c1)=(sin,cos)(beta+epsi),
@@ -136,7 +146,7 @@ struct FastPair {
             const f2 ey = w.ey;
             f2 sdA, cdA, sdB, cdB, sa, ca;
             // ---- stage 1
-            f2 K = KC ? splat(kv) : (clamp01(e0) - clamp01(e1)) * splat(kv);
+            f2 K = KC ? splat(kv) : arc_curv(clamp01(e0) - clamp01(e1));
             const f2 g1 = v1 * rcp2(fma2(-K, ey, ONE));
             const f2 ds1 = g1 * c1;
             const f2 de1 = v1 * s1;

@@ -297,6 +297,7 @@ __global__ __launch_bounds__(64) void emit_fast_kernel(KP P, int B, int W, const
         const double Jw = part_J[(size_t)b * W + w];
         if (cw >= 0 && (c < 0 || Jw < bestJ || (Jw == bestJ && cw < c))) { bestJ = Jw; c = cw; }
     }
+    if (c >= 0 && inputs_refused<float>(P, b, x0, u_prev, flags, cpar)) c = -1;
     cost_out[b] = c >= 0 ? (float)bestJ : INFINITY;
     argmin_out[b] = c;
     status_out[b] = c >= 0 ? 0 : 1;
@@ -345,6 +346,7 @@ __global__ __launch_bounds__(64) void emit_seg_kernel(KP P, int B, int W, int Wk
         const double Jw = part_J[(size_t)b * W + w];
         if (cw >= 0 && (c < 0 || Jw < bestJ || (Jw == bestJ && cw < c))) { bestJ = Jw; c = cw; }
     }
+    if (c >= 0 && inputs_refused<float>(P, b, x0, u_prev, flags, cpar)) c = -1;
     float* xo = x_out + (size_t)b * 7 * (P.N + 1);
     float* uo = u_out + (size_t)b * 2 * P.N;
     if (g == 0) {

@@ -21,6 +21,15 @@ __device__ __forceinline__ void load_scenario(Scenario<T>& S, const KP& P, int b
     S.b0 = (double)kparams[(size_t)b * 3 + 0];
     S.b1 = (double)kparams[(size_t)b * 3 + 1];
     S.kv = (double)kparams[(size_t)b * 3 + 2];
+    // K(s) = kv [s >= b0] - kv [s >= b1] (mpc.py:199 pw_const) whatever the two break-points are; the roll-outs' whole-step
+    // shortcuts ("clear of the arc": before b0 or behind b1) read them as an arc [b0, b1) with b0 <= b1.  Anything else is
+    // restated as such an arc here, once per scenario, with the same K at every s: a NaN break-point is never reached (+inf);
+    // b1 < b0 is -kv on [b1, b0); and a non-finite kv leaves kv - kv = NaN behind the arc as well, so its arc never ends.
+    // Ordered finite inputs and the straight route's (inf, inf, 0) pass through untouched.
+    if (!(S.b0 == S.b0)) S.b0 = (double)INFINITY;
+    if (!(S.b1 == S.b1)) S.b1 = (double)INFINITY;
+    if (S.b1 < S.b0) { const double t = S.b0; S.b0 = S.b1; S.b1 = t; S.kv = -S.kv; }
+    if (!(fabs(S.kv) < 1.79e308)) S.b1 = (double)INFINITY;
     S.obs = obs + (size_t)b * P.n_obs * 2 * (P.N + 1);
     // ramp-hold targets = base sequence + offset.  Base: the warm start u_ws[b] (the previous solution shifted by one
     // step, utils.py:354-363 augment_prev_sol) when the scenario carries one (IGT_FLAG_WARM), else u_prev held.
@@ -35,6 +44,32 @@ __device__ __forceinline__ void load_scenario(Scenario<T>& S, const KP& P, int b
 }
 
 __device__ __forceinline__ bool finite_d(double x) { return fabs(x) < 1.79e308; }
+
+// What an emit wave refuses whatever the search found (status 1, NaN rows): inputs whose poison the search cannot see.
+//   * |psi_0| or |epsi_0| beyond ANGLE_DOMAIN (include/igtmpc.h), NaN and inf included: sincos_reduced (igt_math64.h) is written
+//     for |x| up to about 1e6, and a search unit whose obstacles are out of reach never rolls x, y, psi (ROLL_NO_XY) -- it
+//     found a winner whose Cartesian rows the emit then rolled to NaN;
+//   * a NaN in the warm start the scenario's candidates are centred on: the control recurrences clamp with fmin / fmax, which
+//     drop a NaN, so every candidate was rolled towards a box limit instead of being non-finite (the tracking family reads the
+//     accelerations only; an infinite entry is clamped to the box on both sides and stays);
+//   * a NaN in u_prev, which the generated families' recurrences start from: the same clamps.
+// One lane per scenario reads 4 + at most 2 N numbers; nothing of it is in a search kernel.
+constexpr double ANGLE_DOMAIN = 1.0e6;
+template <typename T>
+__device__ __forceinline__ bool inputs_refused(const KP& P, int b, const T* __restrict__ x0, const T* __restrict__ u_prev,
+                                               const uint32_t* __restrict__ flags, Centre<T> cpar) {
+    bool bad = !(fabs((double)x0[(size_t)b * 7 + 4]) <= ANGLE_DOMAIN) || !(fabs((double)x0[(size_t)b * 7 + 6]) <= ANGLE_DOMAIN);
+    if (P.cand_mode != CAND_TABLE) {
+        const T a = u_prev[(size_t)b * 2 + 0], df = u_prev[(size_t)b * 2 + 1];
+        bad |= !(a == a) || !(df == df);
+    }
+    if (cpar.ws && (flags[b] & 2u) && (P.cand_mode == CAND_RAMP_HOLD || P.cand_mode == CAND_TRACK)) {
+        const T* ws = cpar.ws + (size_t)b * 2 * P.N;
+        const int n = P.cand_mode == CAND_TRACK ? P.N : 2 * P.N;
+        for (int k = 0; k < n; ++k) bad |= !(ws[k] == ws[k]);
+    }
+    return bad;
+}
 
 template <typename T>
 struct StoreSink {

@@ -525,7 +525,10 @@ __global__ __launch_bounds__(64) void search_f64_kernel_cap(IGT_SEARCH64_ARGS, d
 // one 64-thread block per scenario: final arg-min over the W partials, then the winner's trajectory copied out of the unit
 // that rolled it.  Which lane that was is asked of unit_candidate itself, so the two cannot drift apart.
 template <int CAND>
-__global__ __launch_bounds__(64) void emit_gather_f64_kernel(KP P, int B, int W, const double* __restrict__ part_J,
+__global__ __launch_bounds__(64) void emit_gather_f64_kernel(KP P, int B, int W, const double* __restrict__ x0,
+                                                             const double* __restrict__ u_prev,
+                                                             const uint32_t* __restrict__ flags, Centre<double> cpar,
+                                                             const double* __restrict__ part_J,
                                                              const int32_t* __restrict__ part_c,
                                                              const double* __restrict__ traj, double* __restrict__ cost_out,
                                                              int32_t* __restrict__ argmin_out, int32_t* __restrict__ status_out,
@@ -538,6 +541,7 @@ __global__ __launch_bounds__(64) void emit_gather_f64_kernel(KP P, int B, int W,
         const double Jw = part_J[(size_t)b * W + w];
         if (cw >= 0 && (c < 0 || Jw < bestJ || (Jw == bestJ && cw < c))) { bestJ = Jw; c = cw; pw = w; }
     }
+    if (c >= 0 && inputs_refused<double>(P, b, x0, u_prev, flags, cpar)) c = -1;
     if (lane == 0) {
         cost_out[b] = c >= 0 ? bestJ : (double)INFINITY;
         argmin_out[b] = c;
@@ -593,6 +597,7 @@ __global__ __launch_bounds__(64) void emit_f64_kernel(KP P, int B, int W, const 
         const double Jw = part_J[(size_t)b * W + w];
         if (cw >= 0 && (c < 0 || Jw < bestJ || (Jw == bestJ && cw < c))) { bestJ = Jw; c = cw; }
     }
+    if (c >= 0 && inputs_refused<double>(P, b, x0, u_prev, flags, cpar)) c = -1;
     cost_out[b] = c >= 0 ? bestJ : (double)INFINITY;
     argmin_out[b] = c;
     status_out[b] = c >= 0 ? 0 : 1;
@@ -666,6 +671,7 @@ __global__ __launch_bounds__(SEG_THREADS) void emit_seg_f64_kernel(KP P, int B, 
             const double Jw = part_J[(size_t)b * W + w];
             if (cw >= 0 && (c < 0 || Jw < bestJ || (Jw == bestJ && cw < c))) { bestJ = Jw; c = cw; pw = w; }
         }
+        if (c >= 0 && inputs_refused<double>(P, b, x0, u_prev, flags, cpar)) c = -1;
         if (wave == 0) {
             cost_out[b] = c >= 0 ? bestJ : (double)INFINITY;
             argmin_out[b] = c;
@@ -1434,7 +1440,9 @@ template <int CAND, bool HI, int NRK>
 static hipError_t launch_emit64(const KP& P, int B, int W, const SolveArgs<double>& A, hipStream_t st) {
     switch (A.plan.emit_kernel) {
     case EmitKernel64::GATHER:
-        hipLaunchKernelGGL((emit_gather_f64_kernel<CAND>), dim3(B), dim3(64), 0, st, P, B, W, A.part_J, A.part_c, A.traj, A.cost_out,
+        hipLaunchKernelGGL((emit_gather_f64_kernel<CAND>), dim3(B), dim3(64), 0, st, P, B, W, A.x0, A.u_prev, A.flags, A.centre(), A.part_J, A.part_c,
+                           A.traj,
+                           A.cost_out,
                            A.argmin_out, A.status_out, A.x_out, A.u_out);
         break;
     case EmitKernel64::PIECES: {

@@ -301,6 +301,12 @@ __device__ __forceinline__ void compact_features(const CompactRecs& R, unsigned 
     const float e_ego = enc[(size_t)b * 2 + 0], e_tv = enc[(size_t)b * 2 + 1];
     // x_N = [s_tv, v_tv, e_tv, s_N - s_tv, v_N - v_tv, e_ego - e_tv]   (mpc.py:326-338)
     g[0] = s_tv; g[1] = v_tv; g[2] = e_tv; g[3] = sN - s_tv; g[4] = vN - v_tv; g[5] = e_ego - e_tv;
+    // a non-finite feature gives a NaN cost (compact_finish then keeps the entry out of the arg-min): an infinite one
+    // saturates the hardware tanh to +-1 and the entry would win with a finite value
+    bool fin = true;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) fin &= fabsf(g[k]) < INFINITY;
+    if (!fin) J = (double)NAN;
 }
 
 __device__ __forceinline__ float layer1(const DevNet<float>& net, int i, const float (&g)[6]) {
@@ -553,7 +559,13 @@ __global__ __launch_bounds__(512) void value_mfma_f64_kernel(DevNet<double> net,
             }
         v += __shfl_xor(v, 16, 64);
         v += __shfl_xor(v, 32, 64);
-        if (live && g == 0) rec_J[e] = rec_J[e] - ((v + net.bout) * net.sigma_t + net.mu_t);      // mpc.py:369
+        if (live && g == 0) {
+            // a non-finite (s_N, v_N, tv_sv, enc) gives a NaN cost, as terminal_value_f64_kernel gives a NaN value: tanh_d clamps
+            // its argument and would hide it -- the entry would win with the value of a saturated network
+            const double chk = ((sN + vN) + (s_tv + v_tv)) + (e_ego + e_tv);
+            const bool fin = fabs(chk) < 1.79e308;
+            rec_J[e] = fin ? rec_J[e] - ((v + net.bout) * net.sigma_t + net.mu_t) : (double)NAN;      // mpc.py:369
+        }
     }
 }
 

@@ -82,7 +82,7 @@ enum {
 #define IGT_VIOL_EY 8u         /* mpc.py:296-299  k = 0..N   */
 #define IGT_VIOL_TERMINAL 16u  /* mpc.py:177-180  C_inf * [v_{N-1}; a_{N-1}] <= b */
 #define IGT_VIOL_COLLISION 32u /* mpc.py:223-226  k = 1..N   */
-#define IGT_VIOL_NONFINITE 64u
+#define IGT_VIOL_NONFINITE 64u /* a non-finite state (|.| >= 1e300 counts) or a non-finite cost */
 
 #define IGT_MAX_N 64
 #define IGT_MAX_CINF 256
@@ -163,12 +163,20 @@ int igt_set_value_net(igt_handle* h, int32_t n_layers, const int32_t* dims, cons
  * return the feasible arg-min (ties -> lowest candidate index).
  *
  *   x0      [B,7]              initial state                       (mpc.py:280-292)
+ *                              Angles: psi_0 = x0[6] and epsi_0 = x0[4] are reduced by the library's own two-term
+ *                              Cody-Waite reduction; the solve is accurate (the bars below) for |psi_0|, |epsi_0| <= 1e6,
+ *                              any multiple of 2 pi included.  Beyond 1e6 -- NaN and inf included -- the scenario is
+ *                              answered status 1, never status 0 with non-finite rows.
  *   u_prev  [B,2]              previously applied (a, df)          (mpc.py:286)
- *   kparams [B,3]              curvature (b0, b1, Kv): K(s)=Kv on [b0,b1) else 0;
- *                              straight routes pass (inf, inf, 0)  (mpc.py:183-200)
+ *   kparams [B,3]              curvature (b0, b1, Kv): K(s) = Kv [s >= b0] - Kv [s >= b1] (mpc.py:183-200 pw_const), i.e.
+ *                              Kv on [b0,b1) else 0 for b0 <= b1; straight routes pass (inf, inf, 0).  Any other values
+ *                              mean what the formula says: a NaN break-point is never reached, b1 < b0 gives -Kv on
+ *                              [b1,b0), and a non-finite Kv makes every state from b0 on non-finite.
  *   flags   [B]                IGT_FLAG_*
  *   obs_xy  [B,n_obs,2,N+1]    obstacle x / y predictions, already passed through
- *                              filter_preds (utils.py:365-388); k = 1..N are read
+ *                              filter_preds (utils.py:365-388); k = 1..N are read, obs_xy[..., 0] is not.  A non-finite
+ *                              coordinate never collides: that node of that obstacle is no constraint (NaN, +-inf),
+ *                              the nodes beside it stay what they are.
  *   tv_sv   [B,2]  enc [B,2]   value-net cost only (may be NULL otherwise):
  *                              (s,v) of the other vehicle's last raw prediction and
  *                              (e_ego, e_tv) scenario encodings     (mpc.py:326-338)
@@ -176,6 +184,9 @@ int igt_set_value_net(igt_handle* h, int32_t n_layers, const int32_t* dims, cons
  *   cost_out[B]  argmin_out[B]  status_out[B]
  *        status 0 <-> is_opt True; 1 <-> no feasible candidate (is_opt False,
  *        mpc.py:402-406): then argmin = -1, cost = +inf, x_out/u_out = NaN.
+ *        A candidate with a non-finite state or cost is infeasible, so a scenario whose inputs leave none finite -- a
+ *        non-finite x0, a NaN in u_prev or in a warm start that is read (an infinite one is clamped to the input box), a
+ *        non-finite tv_sv / enc under the value-network cost -- is answered status 1, and no scenario's answer depends on another scenario's inputs.
  *
  * polish_iters > 0 (_f64 entries, IGT_COST_PROGRESS; igt_create refuses it with IGT_COST_VALUE_NET, the _f32 entries
  *       answer IGT_E_INVALID): after the search every solved scenario's winner is improved on the device by up to

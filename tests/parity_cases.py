@@ -72,12 +72,19 @@ def oracle_passes(case):
     return passes, O.apply_flags(f('x0'), a['flags'])[:, None, :], f('kparams')[:, None, :]
 
 
+def oracle_passes_quiet(case):
+    """oracle_passes on inputs that hold NaN and inf on purpose (tests/nonfinite_cases.py): numpy's warnings say nothing there."""
+    with np.errstate(all='ignore'):
+        return oracle_passes(case)
+
+
 def measure_case(case, oracle=None):
     """The oracle alone -> {key: measured dict} (two entries where the first pass is compared as well)."""
-    passes, x0, kp = oracle_passes(case) if oracle is None else oracle
-    out = {case['key']: measure(passes, case['P'], x0, kp, case['eps'], case['tie'], case['use_bp'])[0]}
-    if case['first']:
-        out[case['key'] + '/first'] = measure(passes[:1], case['P'], x0, kp, case['eps'], case['tie'], case['use_bp'])[0]
+    with np.errstate(all='ignore'):      # (the poisoned inputs of tests/nonfinite_cases.py hold NaN and inf on purpose)
+        passes, x0, kp = oracle_passes(case) if oracle is None else oracle
+        out = {case['key']: measure(passes, case['P'], x0, kp, case['eps'], case['tie'], case['use_bp'])[0]}
+        if case['first']:
+            out[case['key'] + '/first'] = measure(passes[:1], case['P'], x0, kp, case['eps'], case['tie'], case['use_bp'])[0]
     return out
 
 
@@ -710,6 +717,9 @@ def all_cases():
     for seeds, dtype in ((range(LIMITS_N_SEEDS), 'f64'), (LIMITS_F32_SEEDS, 'f32')):
         for seed in seeds:
             yield f'limits[{seed}-{dtype}]', lambda s=seed, d=dtype: limits_case(s, d)
+    import nonfinite_cases as NF                       # test_gpu_nonfinite.py: the poisoned scenarios of every case
+    for name in NF.CASES:
+        yield f'nonfinite[{name}]', lambda n=name: NF.parity_case(n)
 
 
 # The numpy oracle takes ten seconds and more on the larger batches: the CPU-side measurement (the host test and the tool) runs the
