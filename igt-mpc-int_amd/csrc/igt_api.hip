@@ -352,9 +352,9 @@ template <class Carve> int carve_work(igt_handle* h, hipStream_t st, const Carve
 }
 
 // The argument checks solve and rollout-all share (each entry point checks its own outputs).  B == 0: IGT_OK with *empty set,
-// nothing else is checked.
+// nothing else is checked.  own_table: the call brings its candidates (check_candidates), the handle's table is not asked for.
 int check_batch(const igt_handle* h, int32_t B, const void* x0, const void* u_prev, const void* kparams, const void* flags,
-                const void* obs_xy, const void* tv_sv, const void* enc, const void* u_ws, bool* empty) {
+                const void* obs_xy, const void* tv_sv, const void* enc, const void* u_ws, bool* empty, bool own_table = false) {
     *empty = false;
     if (!h) return fail(IGT_E_INVALID, "null handle");
     if (B < 0) return fail(IGT_E_INVALID, "B < 0");
@@ -362,13 +362,27 @@ int check_batch(const igt_handle* h, int32_t B, const void* x0, const void* u_pr
     if (!x0 || !u_prev || !kparams || !flags) return fail(IGT_E_INVALID, "null buffer");
     const igt_params& p = h->p;
     if (p.n_obs > 0 && !obs_xy) return fail(IGT_E_INVALID, "obs_xy is null but n_obs > 0");
-    if (p.cand_mode == IGT_CAND_TABLE && !h->table_set) return fail(IGT_E_STATE, "candidate table not set");
+    if (p.cand_mode == IGT_CAND_TABLE && !h->table_set && !own_table) return fail(IGT_E_STATE, "candidate table not set");
     if (u_ws && p.cand_mode != IGT_CAND_RAMP_HOLD && p.cand_mode != IGT_CAND_TRACK)
         return fail(IGT_E_INVALID, "a warm start needs IGT_CAND_RAMP_HOLD or IGT_CAND_TRACK (the families whose targets are centred on it)");
     if (p.cost_mode == IGT_COST_VALUE_NET) {
         if (!h->net_set) return fail(IGT_E_STATE, "value net not set (igt_set_value_net)");
         if (!tv_sv || !enc) return fail(IGT_E_INVALID, "tv_sv / enc required for the value-net cost");
     }
+    return IGT_OK;
+}
+
+// What igt_solve_candidates_f64 / igt_rollout_candidates_f64 refuse ahead of check_batch: U[B,C,2,N] stands in for the handle's
+// table, so the handle must be of the table family (which fixes C and N); the oracle-order and literal developer kernels know
+// one shared table only.
+int check_candidates(const igt_handle* h, int32_t B, const void* U) {
+    if (!h) return fail(IGT_E_INVALID, "null handle");
+    if (B < 0) return fail(IGT_E_INVALID, "B < 0");
+    if (!U && B > 0) return fail(IGT_E_INVALID, "U is null (per-scenario candidates U[B,C,2,N])");      // B == 0: an empty buffer
+    if (h->p.cand_mode != IGT_CAND_TABLE)
+        return fail(IGT_E_INVALID, "per-scenario candidates need a handle created with IGT_CAND_TABLE (it fixes C and N)");
+    if (h->kp.dev & (igt::DEV_EXACT64 | igt::DEV_LITERAL))
+        return fail(IGT_E_INVALID, "per-scenario candidates are not available with the developer kernels of IGT_DEV_FLAGS 1024 / 2048");
     return IGT_OK;
 }
 
@@ -380,9 +394,11 @@ inline bool host_zeroes_counters(const igt::KP&, int, const igt::SolveArgs<doubl
 template <typename T>
 int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* kparams, const uint32_t* flags,
                const T* obs_xy, const T* tv_sv, const T* enc, const T* u_ws, T* x_out, T* u_out, T* cost_out,
-               int32_t* argmin_out, int32_t* status_out, int mem, void* stream) {
+               int32_t* argmin_out, int32_t* status_out, int mem, void* stream, const double* U_own = nullptr) {
+    // U_own (igt_solve_candidates_f64, T = double): the candidates U[B,C,2,N], staged like the other inputs, in place of the
+    // handle's table -- the search and emit of plan_candidates64, everything behind the emit as for any table handle
     bool empty;
-    if (int rc = check_batch(h, B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, u_ws, &empty)) return rc;
+    if (int rc = check_batch(h, B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, u_ws, &empty, U_own != nullptr)) return rc;
     if (empty) return IGT_OK;
     if (!x_out || !u_out || !cost_out || !argmin_out || !status_out) return fail(IGT_E_INVALID, "null buffer");
     const igt_params& p = h->p;
@@ -415,6 +431,10 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     stg.in(&A.flags, flags, (size_t)B); stg.in(&A.obs, obs_xy, n_obs);
     stg.in(&A.tv_sv, tv_sv, n_u, value); stg.in(&A.enc, enc, n_u, value);
     stg.in(&A.u_ws, u_ws, n_uo);
+    if (U_own) {
+        A.table_stride = igt::cand_table_doubles(p.C, p.N);
+        stg.in(&A.table, U_own, (size_t)B * A.table_stride);
+    }
     stg.out(&A.x_out, x_out, n_xo); stg.out(&A.u_out, u_out, n_uo); stg.out(&A.cost_out, cost_out, (size_t)B);
     stg.out(&A.argmin_out, argmin_out, (size_t)B); stg.out(&A.status_out, status_out, (size_t)B);
     if (int rc = stg.upload()) return rc;
@@ -444,8 +464,9 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     A.n_cu = h->n_cu;
     A.waves_per_simd = h->concurrency >= 3 ? 1 : 2;      // two solves in flight do not overlap on this runtime (igtmpc.h)
     if constexpr (sizeof(T) == 8)
-        A.plan = igt::plan_search64(h->kp, B, value, igt::Search64Env{A.n_cu, A.waves_per_simd, h->dev_reserve_pool,
-                                                                       h->dev_reserve_units, h->dev_traj_max});
+        A.plan = U_own ? igt::plan_candidates64(h->kp, B, value)
+                       : igt::plan_search64(h->kp, B, value, igt::Search64Env{A.n_cu, A.waves_per_simd, h->dev_reserve_pool,
+                                                                               h->dev_reserve_units, h->dev_traj_max});
     const igt::Search64Plan& plan = A.plan;
     // float path, small batches: the search queues are sorted longest unit first (build_queues_kernel)
     const size_t queue_order_words = sizeof(T) == 8 ? plan.queue_order_words : (B <= 6144 ? (size_t)((B + 7) / 8) * 8 * Wk : 0);
@@ -561,9 +582,9 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
 template <typename T>
 int rollout_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* kparams, const uint32_t* flags,
                  const T* obs_xy, const T* tv_sv, const T* enc, const T* u_ws, T* X_all, T* U_all, T* cost_all,
-                 uint32_t* viol_all, int mem, void* stream) {
-    bool empty;
-    if (int rc = check_batch(h, B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, u_ws, &empty)) return rc;
+                 uint32_t* viol_all, int mem, void* stream, const double* U_own = nullptr) {
+    bool empty;      // U_own (igt_rollout_candidates_f64): as in solve_impl
+    if (int rc = check_batch(h, B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, u_ws, &empty, U_own != nullptr)) return rc;
     if (empty) return IGT_OK;
     if (!cost_all || !viol_all) return fail(IGT_E_INVALID, "null buffer");
     const igt_params& p = h->p;
@@ -581,6 +602,10 @@ int rollout_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T
     stg.in(&A.flags, flags, (size_t)B); stg.in(&A.obs, obs_xy, n_obs);
     stg.in(&A.tv_sv, tv_sv, n_u, value); stg.in(&A.enc, enc, n_u, value);
     stg.in(&A.u_ws, u_ws, (size_t)B * 2 * p.N);
+    if (U_own) {
+        A.table_stride = igt::cand_table_doubles(p.C, p.N);
+        stg.in(&A.table, U_own, (size_t)B * A.table_stride);
+    }
     stg.out(&dX, X_all, n_X); stg.out(&dU, U_all, n_U);      // optional: null = not wanted
     stg.out(&dc, cost_all, n_c); stg.out(&dv, viol_all, n_c);
     if (int rc = stg.upload()) return rc;
@@ -1124,6 +1149,22 @@ int igt_rollout_batch_ws_f64(igt_handle* h, int32_t B, const double* x0, const d
                              int mem, void* stream) {
     return rollout_impl<double>(h, B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, u_ws, X_all, U_all, cost_all,
                                 viol_all, mem, stream);
+}
+
+int igt_solve_candidates_f64(igt_handle* h, int32_t B, const double* x0, const double* u_prev, const double* kparams,
+                             const uint32_t* flags, const double* obs_xy, const double* tv_sv, const double* enc, const double* U,
+                             double* x_out, double* u_out, double* cost_out, int32_t* argmin_out, int32_t* status_out, int mem,
+                             void* stream) {
+    if (int rc = check_candidates(h, B, U)) return rc;
+    return solve_impl<double>(h, B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, nullptr, x_out, u_out, cost_out, argmin_out,
+                              status_out, mem, stream, U);
+}
+int igt_rollout_candidates_f64(igt_handle* h, int32_t B, const double* x0, const double* u_prev, const double* kparams,
+                               const uint32_t* flags, const double* obs_xy, const double* tv_sv, const double* enc, const double* U,
+                               double* X_all, double* U_all, double* cost_all, uint32_t* viol_all, int mem, void* stream) {
+    if (int rc = check_candidates(h, B, U)) return rc;
+    return rollout_impl<double>(h, B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, nullptr, X_all, U_all, cost_all, viol_all, mem,
+                                stream, U);
 }
 
 int igt_frenet_step_f32(igt_handle* h, int32_t n, const float* x, const float* u, const float* kparams, float* x_next,

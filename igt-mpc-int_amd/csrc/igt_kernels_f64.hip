@@ -1,6 +1,8 @@
 // igt_kernels_f64.hip -- gfx950 kernels of the float64 entry points (the reference's precision) and their launchers:
 //   search_f64_kernel_*   persistent waves, one unit -- 64 candidates of one scenario -- at a time (igt_fast64.h); _cap: small
 //                         batches, every unit also keeps its 64 trajectories
+//   search_cand_*_f64_kernel   per-scenario candidate sets U[B,C,2,N]: one wave per unit, the unit's slab staged in LDS, or
+//                         search_unit64 on the scenario's own table
 //   accel_rows_kernel     ahead of the search (batches above 1024 scenarios): the acceleration rows that can still win
 //   emit_f64_kernel       one lane per scenario: the winner re-rolled with the same arithmetic -> x*[7,N+1], u*[2,N]
 //   emit_gather_f64_kernel   small batches: the winner's trajectory copied out of the unit that rolled it
@@ -522,6 +524,87 @@ __global__ __launch_bounds__(64) void search_f64_kernel_cap(IGT_SEARCH64_ARGS, d
                                                    rec_sN, rec_vN, rec_J, rec_viol, rec_count, rec_b, unit_seg, nullptr, traj);
     });
 }
+// ---- per-scenario candidate sets U[B,C,2,N] (igt_solve_candidates_f64; igt_launch.h plan_candidates64) ----
+// The table family, every scenario with a table of its own: U[b] = U + b cand_table_doubles(C, N).  One wave per (scenario,
+// 64-candidate unit) on a plain grid, the unit being candidates 64 p .. 64 p + 63 in index order (unit_layout kind 0).
+//
+// Staged (progress cost, N <= CAND_STAGE_ROWS / 2).  The unit's slab is 2 N 64 contiguous doubles, candidate-major: entry r of
+// candidate j at slab[j 2 N + r].  The wave lays it out in LDS as columns, cols[r 64 + j] -- polish_f64_kernel's layout -- and
+// rolls with rollout_one on the table family, the lane's column as its table (ROLL_STEER_TABLE): the statements of every other
+// roll-out, so the bits of the shared table's solve.  Every byte of U crosses HBM once; the control-step loop reads LDS
+// (ds_read_b64 of cols[k 64 + lane]: 64 consecutive doubles, no two lanes on one bank in a pass).
+// The copy.  A ds_write_b64 of cols[r 64 + j] lands on banks (128 r + 2 j) % 32 = 2 (j % 16) and the one above: the row does not
+// count, 512 B being a multiple of the 128 B the banks span, only the candidate does.  A straight transpose of a coalesced load
+// (lane = consecutive r of one candidate) would put a pass's 16 lanes on ONE bank pair, 16-way.  Here lane l of trip (rb, q)
+// takes candidate 16 q + (l & 15), row 4 rb + (l >> 4): the 16 lanes of a pass hold 16 different candidates modulo 16 -- all 32
+// banks once, no conflict -- and the load they come from reads four 32-byte pieces per candidate, sixteen candidates 16 N bytes
+// apart: sectors, not lines, but every sector it touches is used whole across the four lane groups of the same instruction.
+// All trips' loads are issued before the first store (the bounds are constants, a row past 2 N is loaded from row 2 N - 1 and
+// not stored): up to 40 loads in flight per lane, in registers that the roll-out has not claimed yet.
+// LDS: CAND_STAGE_ROWS rows of 512 B, 20 KB whatever N is: eight waves fill a compute unit's 160 KB, and two waves per SIMD is
+// what the roll-out's registers allow anyway.
+constexpr int CAND_STAGE_ROWS = (int)(CAND_SLAB_MAX_BYTES / (64 * sizeof(double)));      // 40: horizons up to N = 20
+template <bool HI, int NRK>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_cand_staged_f64_kernel(
+        KP P, int B, int W, const double* __restrict__ x0, const double* __restrict__ u_prev, const double* __restrict__ kparams,
+        const uint32_t* __restrict__ flags, const double* __restrict__ obs, const double* __restrict__ U,
+        const double* __restrict__ cinf, double* __restrict__ part_J, int32_t* __restrict__ part_c) {
+    __shared__ double cols[CAND_STAGE_ROWS * 64];
+    const int b = (int)(blockIdx.x / (unsigned)W), p = (int)(blockIdx.x % (unsigned)W), lane = threadIdx.x;
+    if (b >= B) return;
+    const int n2 = 2 * P.N;                                   // <= CAND_STAGE_ROWS (plan_candidates64)
+    const double* __restrict__ slab = U + ((size_t)b * P.C + (size_t)p * 64) * n2;
+    {
+        constexpr int TRIPS = CAND_STAGE_ROWS / 4;
+        const int j = lane & 15, r0 = lane >> 4;
+        double held[TRIPS][4];
+#pragma unroll
+        for (int rb = 0; rb < TRIPS; ++rb) {
+            const int r = 4 * rb + r0, rr = r < n2 ? r : n2 - 1;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) held[rb][q] = slab[(size_t)(16 * q + j) * n2 + rr];
+        }
+#pragma unroll
+        for (int rb = 0; rb < TRIPS; ++rb) {
+            const int r = 4 * rb + r0;
+            if (r < n2) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) cols[r * 64 + 16 * q + j] = held[rb][q];
+            }
+        }
+    }
+    __syncthreads();
+    Scenario<double> S;
+    load_scenario<double>(S, P, b, x0, u_prev, kparams, flags, obs);
+    const bool far = !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
+    NullSink sink;
+    const int c = p * 64 + lane;
+    double J, sN, vN;
+    unsigned viol;
+    if (far) f64::rollout_one<CAND_TABLE, HI, ROLL_SEARCH | ROLL_STEER_TABLE | ROLL_NO_XY, NRK>(P, S, c, nullptr, cinf, sink, J, viol, sN, vN, cols + lane, 64);
+    else f64::rollout_one<CAND_TABLE, HI, ROLL_SEARCH | ROLL_STEER_TABLE, NRK>(P, S, c, nullptr, cinf, sink, J, viol, sN, vN, cols + lane, 64);
+    // what search_unit64 leaves for a unit without checkpoint slots or an incumbent: its statements
+    const double Jq = J - (sN - S.x0[2]);                       // mpc.py:372
+    double bestJ = Jq;
+    int bestC = ((viol == 0) && finite_d(Jq)) ? c : -1;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {                   // wave butterfly arg-min, ties -> lowest candidate index
+        const double oJ = __shfl_xor(bestJ, off, 64);
+        const int oC = __shfl_xor(bestC, off, 64);
+        const bool take = (oC >= 0) && (bestC < 0 || oJ < bestJ || (oJ == bestJ && oC < bestC));
+        if (take) { bestJ = oJ; bestC = oC; }
+    }
+    if (lane == 0) { part_J[b * W + p] = bestJ; part_c[b * W + p] = bestC; }
+}
+// Direct (horizons whose slab does not fit; the value-network cost, whose units leave records): search_unit64 itself, its
+// table the scenario's own, read from HBM step by step as the shared table is read from L2.
+template <bool HI, bool VALUE, int NRK>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_cand_direct_f64_kernel(IGT_SEARCH64_ARGS) {
+    const int b = (int)(blockIdx.x / (unsigned)W), p = (int)(blockIdx.x % (unsigned)W);
+    if (b >= B) return;
+    search_unit64<CAND_TABLE, HI, VALUE, NRK>(P, W, b, p, x0, u_prev, kparams, flags, obs, table + (size_t)b * cand_table_doubles(P.C, P.N),
+                                              cinf, cpar, part_J, part_c, rec_sN, rec_vN, rec_J, rec_viol, rec_count, rec_b, unit_seg);
+}
 // one 64-thread block per scenario: final arg-min over the W partials, then the winner's trajectory copied out of the unit
 // that rolled it.  Which lane that was is asked of unit_candidate itself, so the two cannot drift apart.
 template <int CAND>
@@ -577,7 +660,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 // the issue slots they leave; it raises its priority once, before anything else, and keeps it.  A build of its own, not a
 // run-time condition: s_setprio ignores EXEC and must not sit under a branch the compiler cannot prove wave-uniform, and the
 // PRIO = 0 build stays the code it was.
-template <int CAND, bool HI, int NRK, int PRIO = 0>
+// OWN (the per-scenario candidate sets): `table` is U[B,C,2,N] and the scenario rolls from its own part of it.
+template <int CAND, bool HI, int NRK, int PRIO = 0, bool OWN = false>
 __global__ __launch_bounds__(64) void emit_f64_kernel(KP P, int B, int W, const double* __restrict__ x0,
                                                       const double* __restrict__ u_prev,
                                                       const double* __restrict__ kparams,
@@ -613,7 +697,8 @@ __global__ __launch_bounds__(64) void emit_f64_kernel(KP P, int B, int W, const 
     StoreSink<double> sink{xo, uo, P.N};
     double J, sN, vN;
     unsigned viol;
-    f64::rollout_one<CAND, HI, ROLL_EMIT, NRK>(P, S, c, table, cinf, sink, J, viol, sN, vN);
+    f64::rollout_one<CAND, HI, ROLL_EMIT, NRK>(P, S, c, OWN ? table + (size_t)b * cand_table_doubles(P.C, P.N) : table, cinf, sink, J, viol,
+                                               sN, vN);
 }
 
 // ---- emit in pieces (batches that do not keep trajectories; progress cost) ----
@@ -1201,7 +1286,7 @@ __global__ __launch_bounds__(64) void cost_gradient_f64_kernel(KP P, int B, cons
     }
 }
 
-template <int CAND, bool HI>
+template <int CAND, bool HI, bool OWN = false>      // OWN: `table` is U[B,C,2,N], the scenario rolls its own part of it
 __global__ __launch_bounds__(256) void rollout_all_f64_kernel(KP P, int B, const double* __restrict__ x0,
                                                               const double* __restrict__ u_prev,
                                                               const double* __restrict__ kparams,
@@ -1224,7 +1309,7 @@ __global__ __launch_bounds__(256) void rollout_all_f64_kernel(KP P, int B, const
         StoreSink<double> sink{X_all ? X_all + bc * 7 * (P.N + 1) : nullptr, U_all ? U_all + bc * 2 * P.N : nullptr, P.N};
         double J, sN, vN;
         unsigned viol;
-        f64::rollout_one<CAND, HI, ROLL_ALL>(P, S, c, table, cinf, sink, J, viol, sN, vN);
+        f64::rollout_one<CAND, HI, ROLL_ALL>(P, S, c, OWN ? table + (size_t)b * cand_table_doubles(P.C, P.N) : table, cinf, sink, J, viol, sN, vN);
         if (rec_J) {   // value-net cost: value_kernel adds the terminal term and fills cost_all / viol_all
             rec_sN[bc] = sN; rec_vN[bc] = vN; rec_J[bc] = J; rec_viol[bc] = viol;
             continue;
@@ -1402,6 +1487,20 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
             return with_bool((plan.launch_dev_bits & DEV_LAUNCH_CKPT) != 0,
                              [&](auto ckpt) { return search(search_f64_kernel_pool<CAND, HI, VALUE, NRK, ckpt()>); });
         break;
+    case SearchKernel64::CANDIDATES_STAGED:      // per-scenario candidate sets (plan_candidates64): A.table is U[B,C,2,N]
+        if constexpr (CAND == CAND_TABLE && !VALUE) {
+            if (A.table_stride != cand_table_doubles(P.C, P.N) || cand_slab_doubles(P.N) > (size_t)CAND_STAGE_ROWS * 64) break;
+            hipLaunchKernelGGL((search_cand_staged_f64_kernel<HI, NRK>), dim3(plan.grid), dim3(64), 0, st, P, B, W, A.x0, A.u_prev, A.kparams,
+                               A.flags, A.obs, A.table, A.cinf, A.part_J, A.part_c);
+            return hipGetLastError();
+        }
+        break;
+    case SearchKernel64::CANDIDATES_DIRECT:
+        if constexpr (CAND == CAND_TABLE) {
+            if (A.table_stride != cand_table_doubles(P.C, P.N)) break;
+            return search(search_cand_direct_f64_kernel<HI, VALUE, NRK>);
+        }
+        break;
     case SearchKernel64::UNITS:
         // NRK = 4: the reference's discretisation (4 sub-steps, short polynomials) has its own build of the kernel
         if constexpr (CAND == CAND_TRACK) return search(search_f64_kernel_o2w<CAND, HI, VALUE, NRK>);
@@ -1459,6 +1558,11 @@ static hipError_t launch_emit64(const KP& P, int B, int W, const SolveArgs<doubl
         };
         // the build that raises its wave priority: asked for behind the pool search alone (plan_search64 emit_priority), so the
         // lattice's emit alone has it.  No per-kernel setup depends on the build (prepare_emit_kernels: emit in pieces and polish).
+        if (A.table_stride != 0) {      // per-scenario candidate sets: the scenario's own table
+            if constexpr (CAND == CAND_TABLE)
+                if (A.table_stride == cand_table_doubles(P.C, P.N) && A.plan.emit_priority == 0) { emit(emit_f64_kernel<CAND, HI, NRK, 0, true>); break; }
+            return hipErrorInvalidValue;
+        }
         if (A.plan.emit_priority == 0) { emit(emit_f64_kernel<CAND, HI, NRK>); break; }
         if constexpr (CAND == CAND_LATTICE)
             if (A.plan.emit_priority == EMIT_PRIORITY_OVERLAP) { emit(emit_f64_kernel<CAND, HI, NRK, EMIT_PRIORITY_OVERLAP>); break; }
@@ -1577,6 +1681,15 @@ hipError_t launch_rollout_all<double>(const KP& P, int B, const SolveArgs<double
         return hipGetLastError();
     }
 #endif
+    if (A.table_stride != 0) {      // per-scenario candidate sets: A.table is U[B,C,2,N]
+        if (P.cand_mode != CAND_TABLE || A.table_stride != cand_table_doubles(P.C, P.N)) return hipErrorInvalidValue;
+        return with_bool(P.hi_order != 0, [&](auto hi) {
+            hipLaunchKernelGGL((rollout_all_f64_kernel<CAND_TABLE, hi(), true>), dim3((B + 3) / 4), dim3(256), 0, st, P, B, A.x0, A.u_prev,
+                               A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), X_all, U_all, cost_all, viol_all, A.rec_sN,
+                               A.rec_vN, A.rec_J, A.rec_viol);
+            return hipGetLastError();
+        });
+    }
     return with_family(P.cand_mode, P.hi_order, [&](auto cand, auto hi) {
         hipLaunchKernelGGL((rollout_all_f64_kernel<cand(), hi()>), dim3((B + 3) / 4), dim3(256), 0, st, P, B, A.x0, A.u_prev,
                            A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), X_all, U_all, cost_all, viol_all, A.rec_sN, A.rec_vN,

@@ -81,6 +81,9 @@ enum class SearchKernel64 {
     POOL,             // search_f64_kernel_pool: one item per scenario
     UNITS_WAVES3,     // search_f64_kernel_o3: the 3-waves-per-SIMD developer builds (DEV_WAVES3)
     UNITS,            // search_f64_kernel_o2 / _o2w (tracking family) on 64-candidate units
+    // per-scenario candidate sets U[B,C,2,N] (plan_candidates64; never chosen by plan_search64)
+    CANDIDATES_STAGED,   // search_cand_staged_f64_kernel: the unit's slab of U staged in LDS, one wave per unit
+    CANDIDATES_DIRECT,   // search_cand_direct_f64_kernel: search_unit64 on the scenario's own table, one wave per unit
 };
 enum class EmitKernel64 {
     ORACLE,           // emit_kernel<ExactStepper>
@@ -248,6 +251,30 @@ inline Search64Plan plan_search64(const KP& P, int B, bool value, const Search64
     return p;
 }
 
+// ---- the plan of a solve on per-scenario candidate sets U[B,C,2,N] (igt_solve_candidates_f64) ----
+// The table family with a table of the scenario's own.  Every other input of the solve together is 1.8 MB at B = 4096; U is
+// 335 MB at C = 256, N = 20, and no two units read the same bytes: a streaming read with a roll-out behind it.
+//   * progress cost, the unit's slab U[b, 64 p .. 64 p + 63, :, :] -- 2 N 64 contiguous doubles -- fits an eighth of a compute
+//     unit's LDS (N <= 20: 20 KB, eight waves a compute unit, the two per SIMD the roll-out's registers allow):
+//     CANDIDATES_STAGED loads it once and rolls from LDS;
+//   * longer horizons, and the value-network cost (whose units leave records, not partials): CANDIDATES_DIRECT, search_unit64
+//     on the scenario's table in HBM.
+// A plain grid of one wave per unit, no queues, no counters, no prelude.  Nothing keeps trajectories or checkpoint records, so
+// emit rolls the winner in one piece at every batch size (at priority 0) and the workspace is the partials alone.
+constexpr size_t CAND_LDS_BUDGET = 160 * 1024, CAND_SLAB_MAX_BYTES = CAND_LDS_BUDGET / 8;
+__host__ __device__ inline size_t cand_table_doubles(int C, int N) { return (size_t)C * 2 * N; }      // one scenario's U[b]
+__host__ __device__ inline size_t cand_slab_doubles(int N) { return (size_t)2 * N * 64; }              // one unit's part of it
+inline Search64Plan plan_candidates64(const KP& P, int B, bool value) {
+    Search64Plan p{};
+    p.W = P.C / 64;
+    p.grid = (size_t)B * p.W;
+    p.order_stride = ((B + 7) / 8) * p.W;
+    const bool staged = !value && cand_slab_doubles(P.N) * 8 <= CAND_SLAB_MAX_BYTES;
+    p.search_kernel = staged ? SearchKernel64::CANDIDATES_STAGED : SearchKernel64::CANDIDATES_DIRECT;
+    p.emit_kernel = EmitKernel64::ONE_PIECE;
+    return p;      // queues 0, no prelude, no launch-time bits, no trajectories, records or queue order, no memset, priority 0
+}
+
 template <typename T>
 struct SolveArgs {   // all device pointers
     const T* x0;
@@ -258,7 +285,9 @@ struct SolveArgs {   // all device pointers
     const T* tv_sv;
     const T* enc;
     const double* table;   // [C,2,N] or null
-    const double* cinf;    // [F,3] or null
+    size_t table_stride = 0;   // doubles from one scenario's table to the next: 0, one table shared by the batch (every entry
+                               // but the two on per-scenario candidate sets); cand_table_doubles(C, N), table is U[B,C,2,N]
+    const double* cinf;   // [F,3] or null
     const double* cpar;    // [B,4] ramp-hold centre offset / span of a refinement pass, or null (first pass)
     const T* u_ws;         // [B,2,N] warm start (previous solution shifted by one step), or null; used where flags & 2
     Centre<T> centre() const { return Centre<T>{cpar, u_ws}; }

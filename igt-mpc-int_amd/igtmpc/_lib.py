@@ -79,6 +79,8 @@ SYMBOLS = {
     'igt_cost_gradient_f64': (_i, [_vp, _i32] + [_vp] * 6 + [_i, _vp]),
     'igt_terminal_value_f64': (_i, [_vp, _i32] + [_vp] * 5 + [_i, _vp]),
     'igt_cost_gradient_vn_f64': (_i, [_vp, _i32] + [_vp] * 8 + [_i, _vp]),
+    'igt_solve_candidates_f64': (_i, _SOLVE_WS),       # U[B,C,2,N] where the _ws entries take u_ws
+    'igt_rollout_candidates_f64': (_i, _ROLL_WS),
     'igt_set_profiling': (_i, [_vp, _i]),
     'igt_get_kernel_ms': (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     'igt_algorithmic_bytes_per_solve': (_i, [_vp, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -86,7 +88,7 @@ SYMBOLS = {
 
 # added without a change of IGT_VERSION: a library of the same ABI from before them (IGT_LIB_PATH, tools/ab_lib.sh) lacks them
 OPTIONAL_SYMBOLS = ('igt_set_polish_gradient', 'igt_cost_gradient_f64', 'igt_terminal_value_f64', 'igt_cost_gradient_vn_f64',
-                    'igt_set_polish_step', 'igt_set_value_polish')
+                    'igt_set_polish_step', 'igt_set_value_polish', 'igt_solve_candidates_f64', 'igt_rollout_candidates_f64')
 
 _libs = {}
 # IGT_DEV_FLAGS bits (csrc/igt_device.h DevFlag; the launch-time bits there are the library's own and not listed here)

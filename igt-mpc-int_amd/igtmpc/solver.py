@@ -291,6 +291,77 @@ class BatchSolver:
         self._check(self._rollout(self._h, B, *ptrs, mode, self._stream_ptr(stream, False)))
         return dict(X=X, U=U, cost=cost, viol=viol)
 
+    # ------------------------------------------------------------------ per-scenario candidate sets
+    def _check_candidates(self, what, x0, U):
+        """What solve_candidates / rollout_candidates refuse before any GPU call; -> B."""
+        if self.dtype != 'f64':
+            raise ValueError(f"{what} needs dtype='f64' (the float kernels read a double table and would need a conversion pass)")
+        if self.params.cand_mode != L.IGT_CAND_TABLE:
+            raise ValueError(f"{what} needs cand_mode='table' (it fixes C and N; set_candidate_table need not be called)")
+        B = int(x0.shape[0])
+        want = (B, self.C, 2, self.N)
+        if U is None or not hasattr(U, 'shape') or tuple(U.shape) != want:
+            raise ValueError(f'U must be [B,C,2,N] = {want}, not {None if U is None else tuple(getattr(U, "shape", ()))}')
+        return B
+
+    def solve_candidates(self, x0, u_prev, kparams, flags, U, obs_xy=None, tv_sv=None, enc=None, out=None, stream=None):
+        """solve() on candidates of the caller's, one set per scenario: U[B,C,2,N], scenario b's C control sequences (a_k, then
+        df_k), judged like any table candidate -- rate limit and input box included (igtmpc.h igt_solve_candidates_f64).
+        -> the dict of solve(); row b is, bit for bit, what a table solver whose shared table is U[b] answers for scenario b.
+        float64 solvers with cand_mode='table'; numpy arrays or tensors on the solver's GPU, as solve -- with tensors the call only
+        enqueues and can be captured, and a replay reads what U holds then.  polish_iters and the device-driven value polish act
+        behind the emit as in solve(); the host-driven value polish is solve()'s own loop and is refused here."""
+        B = self._check_candidates('solve_candidates', x0, U)
+        if self.value_polish_iters > 0 and self.value_polish_driver == 'host':
+            raise TypeError("value_polish_iters > 0 under value_polish_driver='host' is solve()'s loop: "
+                            "set_value_polish_driver('device') takes the steps inside solve_candidates, set_value_polish(0) none")
+        fn = self._entry('igt_solve_candidates_f64')
+        dt, N, no, Cn = self.np_dtype, self.N, self.n_obs, self.C
+        if out is None:
+            if _is_torch(x0):
+                import torch
+                dev = x0.device
+                out = dict(x=torch.empty((B, 7, N + 1), dtype=torch.float64, device=dev),
+                           u=torch.empty((B, 2, N), dtype=torch.float64, device=dev),
+                           cost=torch.empty((B,), dtype=torch.float64, device=dev),
+                           argmin=torch.empty((B,), dtype=torch.int32, device=dev),
+                           status=torch.empty((B,), dtype=torch.int32, device=dev))
+            else:
+                out = dict(x=np.empty((B, 7, N + 1), dt), u=np.empty((B, 2, N), dt), cost=np.empty((B,), dt),
+                           argmin=np.empty((B,), np.int32), status=np.empty((B,), np.int32))
+        arrs = [x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, U, out['x'], out['u'], out['cost'], out['argmin'], out['status']]
+        shapes = [(B, 7), (B, 2), (B, 3), (B,), (B, no, 2, N + 1), (B, 2), (B, 2), (B, Cn, 2, N),
+                  (B, 7, N + 1), (B, 2, N), (B,), (B,), (B,)]
+        dts = [dt, dt, dt, np.uint32, dt, dt, dt, dt, dt, dt, dt, np.int32, np.int32]
+        mode, ptrs, keep = self._prep(arrs, shapes, dts)
+        if mode == L.IGT_MEM_HOST:
+            for k, i in (('x', 8), ('u', 9), ('cost', 10), ('argmin', 11), ('status', 12)):
+                if keep_is_copy(out[k], ptrs[i]):
+                    raise ValueError(f'out[{k!r}] must be a contiguous array of the solver dtype')
+        self._check(fn(self._h, B, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        return out
+
+    def rollout_candidates(self, x0, u_prev, kparams, flags, U, obs_xy=None, tv_sv=None, enc=None, want_X=True, want_U=True,
+                           stream=None):
+        """rollout_all() on the per-scenario candidates U[B,C,2,N] of solve_candidates (igtmpc.h igt_rollout_candidates_f64):
+        -> dict(X[B,C,7,N+1] | None, U[B,C,2,N] | None, cost[B,C], viol[B,C]).  Host mode, like rollout_all."""
+        B = self._check_candidates('rollout_candidates', x0, U)
+        if _is_torch(x0) or _is_torch(U):
+            raise TypeError('rollout_candidates is a host-mode entry (numpy buffers), like rollout_all')
+        fn = self._entry('igt_rollout_candidates_f64')
+        dt, N, no, Cn = self.np_dtype, self.N, self.n_obs, self.C
+        X = np.empty((B, Cn, 7, N + 1), dt) if want_X else None
+        Uo = np.empty((B, Cn, 2, N), dt) if want_U else None
+        cost = np.empty((B, Cn), dt)
+        viol = np.empty((B, Cn), np.uint32)
+        arrs = [x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, U, X, Uo, cost, viol]
+        shapes = [(B, 7), (B, 2), (B, 3), (B,), (B, no, 2, N + 1), (B, 2), (B, 2), (B, Cn, 2, N),
+                  (B, Cn, 7, N + 1), (B, Cn, 2, N), (B, Cn), (B, Cn)]
+        dts = [dt, dt, dt, np.uint32, dt, dt, dt, dt, dt, dt, dt, np.uint32]
+        mode, ptrs, keep = self._prep(arrs, shapes, dts)
+        self._check(fn(self._h, B, *ptrs, mode, self._stream_ptr(stream, False)))
+        return dict(X=X, U=Uo, cost=cost, viol=viol)
+
     # ------------------------------------------------------------------ polish under the value-network cost
     def _drop_vp_table(self):
         t, self._vp_table = getattr(self, '_vp_table', None), None

@@ -465,6 +465,29 @@ int igt_cost_gradient_vn_f64(igt_handle* h, int32_t B, const double* x0, const d
                              const double* tv_sv, const double* enc, const double* U, double* cost_out, double* grad_out,
                              int mem, void* stream);
 
+/* Per-scenario candidate sets: solve, and roll out all, on U [B,C,2,N] -- scenario b's C control sequences (a_k, then df_k, as
+ * igt_set_candidate_table lays one table out), read from wherever the other buffers of the call live.  For every scenario b the
+ * answer is what igt_solve_batch_f64 / igt_rollout_batch_f64 give for that scenario on a handle of the same parameters whose
+ * shared table is U[b], bit for bit: ties go to the lowest index, status 1 carries NaN rows, +inf and -1, the rate limit and the
+ * input box are judged as for any table candidate, a row of U with a NaN makes that candidate infeasible, and no scenario's
+ * answer depends on another scenario's inputs, U among them.  Every other buffer, both costs (IGT_COST_VALUE_NET: tv_sv / enc
+ * and a loaded network), polish_iters and igt_set_value_polish are igt_solve_batch_f64's / igt_rollout_batch_f64's.
+ * The handle must be IGT_CAND_TABLE, which fixes C and N; igt_set_candidate_table need not have been called.
+ * U follows `mem` like the other buffers.  IGT_MEM_HOST: it is staged with them, 16 C N bytes per scenario (82 KB at C = 256,
+ * N = 20: a host-mode call pays for that copy).  IGT_MEM_DEVICE: the call only enqueues; after one call at that B it neither
+ * allocates nor synchronises (capturable), and a replayed graph reads what U holds at replay time.
+ * IGT_E_INVALID for a null handle, B < 0, a null U, a handle of another candidate family and with the developer kernels of
+ * IGT_DEV_FLAGS 1024 / 2048; B = 0 is a no-op.  There is no _f32 entry: the float kernels read a double table and would need a
+ * conversion pass of their own.  (Added without a change of IGT_VERSION; callers probe the symbols.) */
+int igt_solve_candidates_f64(igt_handle* h, int32_t B, const double* x0, const double* u_prev, const double* kparams,
+                             const uint32_t* flags, const double* obs_xy, const double* tv_sv, const double* enc,
+                             const double* U, double* x_out, double* u_out, double* cost_out, int32_t* argmin_out,
+                             int32_t* status_out, int mem, void* stream);
+int igt_rollout_candidates_f64(igt_handle* h, int32_t B, const double* x0, const double* u_prev, const double* kparams,
+                               const uint32_t* flags, const double* obs_xy, const double* tv_sv, const double* enc,
+                               const double* U, double* X_all, double* U_all, double* cost_all, uint32_t* viol_all, int mem,
+                               void* stream);
+
 /* Workspace (owned by the handle, grown on the first solve of a batch size, never shrunk; growth synchronises the stream and is
  * refused under stream capture with IGT_E_STATE).  Per scenario, C = 256: 48 B of slice partials, 16 B of live-row masks and
  * incumbent keys (float64; float32: 8 B), 128 B of the acceleration rows' travel sums (float64), 768 B of horizon checkpoints of
