@@ -57,7 +57,6 @@ struct igt_handle {
     bool prof = false;
     hipEvent_t ev[3];
     bool ev_recorded = false;
-    int nc = 2;
     int n_cu = 256;                // compute units of the device (sizes the persistent search grid)
     int concurrency = 1;           // solves the caller keeps in flight on the device (igt_set_concurrency)
     int polish_grad = IGT_GRAD_FORWARD_DIFF;      // or IGT_GRAD_ADJOINT (igt_set_polish_gradient)
@@ -386,11 +385,6 @@ int check_candidates(const igt_handle* h, int32_t B, const void* U) {
     return IGT_OK;
 }
 
-// Whether the host zeroes the search kernel's unit counters: not where a queue builder does it or the search uses none.  The
-// double path reads its plan; the overloads exist only because the float path has no plan and asks its launcher's predicate.
-inline bool host_zeroes_counters(const igt::KP& kp, int B, const igt::SolveArgs<float>& A) { return !igt::search_builds_queues(kp, B, A); }
-inline bool host_zeroes_counters(const igt::KP&, int, const igt::SolveArgs<double>& A) { return A.plan.memset_counters; }
-
 template <typename T>
 int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* kparams, const uint32_t* flags,
                const T* obs_xy, const T* tv_sv, const T* enc, const T* u_ws, T* x_out, T* u_out, T* cost_out,
@@ -440,40 +434,25 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     if (int rc = stg.upload()) return rc;
     hipStream_t st = stg.stream();
 
-    // workspace (grows on first use, never shrinks): per-slice partial arg-min [+ value-net records]
-    // per-scenario partials: float value path reduces to ONE per scenario (compact list + atomicMin),
-    // double value path keeps one per 64-candidate chunk, progress cost one per 128-candidate slice
-    const bool compact = value && sizeof(T) == 4;
-    // units per scenario of the search kernel: 128-candidate slices (float, two candidates per lane) or 64 (double)
-    const size_t Wk = sizeof(T) == 4 ? ((size_t)p.C + 127) / 128 : (size_t)p.C / 64;
-    const size_t W = compact ? 1 : (value ? (size_t)p.C / 64 : Wk);
-    const bool exact64 = sizeof(T) == 8 && (h->kp.dev & igt::DEV_EXACT64);      // developer switch: oracle-order double kernels
-    // small float batches: emit in 4 pieces from checkpoints of the search pass.  Measured (search + emit): +15 % at
-    // B = 1024, +12 % at 2048, +3 % at 4096, -1 % at 8192 -- but the records are ~150 MB of HBM writes per B = 4096 solve
-    // against ~1 MB of algorithmic traffic, so they are only spent where emit latency dominates.
-    int ck_parts = 1;
-    if (sizeof(T) == 4 && B <= 2048 && p.N % 4 == 0 && p.N >= 8) ck_parts = 4;
-    else if (sizeof(T) == 4 && B <= 2048 && p.N % 2 == 0 && p.N >= 4) ck_parts = 2;
-    if (h->dev_ckpt >= 0) {
-        const int v = h->dev_ckpt;
-        if (sizeof(T) == 4 && v >= 1 && v <= igt::SEG_MAX_PARTS && p.N % v == 0 && p.N >= 2 * v) ck_parts = v;
-    }
-    const bool use_ckpt = ck_parts > 1;
-    // double path: which kernels search and emit run, and with them the trajectories, checkpoint records and queue order to carve
-    // (igt_launch.h plan_search64).  One plan for the solve: a refinement pass changes nothing it reads.
+    // Which kernels search and emit run, and with them the partials, checkpoints, trajectories and queue order to carve and the
+    // memsets of a pass: decided once, in igt_launch.h (plan_search32, plan_search64, plan_candidates64).  One plan for the
+    // solve: a refinement pass changes nothing it reads.
     A.n_cu = h->n_cu;
-    A.waves_per_simd = h->concurrency >= 3 ? 1 : 2;      // two solves in flight do not overlap on this runtime (igtmpc.h)
-    if constexpr (sizeof(T) == 8)
+    const int waves_per_simd = h->concurrency >= 3 ? 1 : 2;      // two solves in flight do not overlap on this runtime (igtmpc.h)
+    if constexpr (sizeof(T) == 4)
+        A.plan = igt::plan_search32(h->kp, B, value, igt::Search32Env{h->n_cu, waves_per_simd, h->dev_ckpt});
+    else
         A.plan = U_own ? igt::plan_candidates64(h->kp, B, value)
-                       : igt::plan_search64(h->kp, B, value, igt::Search64Env{A.n_cu, A.waves_per_simd, h->dev_reserve_pool,
+                       : igt::plan_search64(h->kp, B, value, igt::Search64Env{h->n_cu, waves_per_simd, h->dev_reserve_pool,
                                                                                h->dev_reserve_units, h->dev_traj_max});
-    const igt::Search64Plan& plan = A.plan;
-    // float path, small batches: the search queues are sorted longest unit first (build_queues_kernel)
-    const size_t queue_order_words = sizeof(T) == 8 ? plan.queue_order_words : (B <= 6144 ? (size_t)((B + 7) / 8) * 8 * Wk : 0);
+    const auto& plan = A.plan;
+    const size_t Wk = (size_t)plan.W, W = (size_t)plan.partials;      // units and partials per scenario
+    const bool exact64 = sizeof(T) == 8 && (h->kp.dev & igt::DEV_EXACT64);      // developer switch: oracle-order double kernels
     const bool trace = (h->kp.dev & igt::DEV_TRACE) != 0;      // developer trace: 32 B per unit behind the counters
     const size_t n_rec = value ? (size_t)B * p.C : 0;
     double* d_cpar = nullptr;
     double* vp_work = nullptr;      // igt_value_polish_layout.h: the scratch of igt_set_value_polish's iterations
+    // workspace (grows on first use, never shrinks): per-unit partial arg-min [+ value-net records]
     const auto carve = [&](Arena& wa) {
         A.part_J = wa.take<double>(igt::PartJTail<T>(nullptr, B, (int)W, h->kp.G).doubles(plan.ck_records != 0));
         const igt::PartJTail<T> tail(A.part_J, B, (int)W, h->kp.G);
@@ -486,10 +465,9 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
         A.part_c = wa.take<int32_t>((size_t)B * W);
         d_cpar = wa.take<double>((size_t)B * 4);
         A.work_counter = wa.take<unsigned>(igt::WORK_COUNTER_WORDS + (trace ? (size_t)((B + 7) / 8) * 8 * Wk * 8 : 0));
-        // small batches: the search pass leaves horizon checkpoints, emit rolls the winner's four quarters at once
-        A.ckpt = use_ckpt ? wa.take<double>((size_t)(ck_parts - 1) * B * Wk * igt::SEG_UNIT_DOUBLES) : nullptr;
-        A.queue_order = queue_order_words ? wa.take<unsigned>(queue_order_words) : nullptr;
-        if constexpr (sizeof(T) == 8) A.traj = plan.traj_doubles ? wa.take<double>(plan.traj_doubles) : nullptr;
+        A.ckpt = plan.ckpt_doubles ? wa.take<double>(plan.ckpt_doubles) : nullptr;
+        A.queue_order = plan.queue_order_words ? wa.take<unsigned>(plan.queue_order_words) : nullptr;
+        A.traj = plan.traj_doubles ? wa.take<double>(plan.traj_doubles) : nullptr;
         if (value) {
             A.rec_J = wa.take<double>(n_rec);
             A.rec_sN = wa.take<T>(n_rec);
@@ -508,28 +486,22 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
         if (vp_iters > 0) vp_work = wa.take<double>(igt::ValuePolishLayout::doubles(B, p.N));      // behind everything else
     };
     if (int rc = carve_work(h, st, carve)) return rc;
-    A.ck_parts = ck_parts;
     if (h->prof) HIPCHK(hipEventRecord(h->ev[0], st));
     igt::KP kp = h->kp;
     for (int it = 0; it <= p.refine_iters; ++it) {
         kp.refine_it = it;
         A.cpar = it == 0 ? nullptr : d_cpar;
+        // the unit counters where no queue builder zeroes them; the compact list of feasible candidates (both precisions) and
+        // the float path's per-scenario keys
+        if (plan.memset_counters) HIPCHK(hipMemsetAsync(A.work_counter, 0, 8 * 256, st));
+        if (plan.reset_rec_count) HIPCHK(hipMemsetAsync(A.rec_count, 0, 256, st));
+        if (plan.reset_best_key) HIPCHK(hipMemsetAsync(A.best_key, 0xff, (size_t)B * 8, st));
         if (value) {
-            if (compact) {
-                if (host_zeroes_counters(kp, B, A)) HIPCHK(hipMemsetAsync(A.work_counter, 0, 8 * 256, st));
-                HIPCHK(hipMemsetAsync(A.rec_count, 0, 256, st));
-                HIPCHK(hipMemsetAsync(A.best_key, 0xff, (size_t)B * 8, st));
-            }
-            else if (!exact64) {      // double path: compact list of feasible candidates as well
-                if (host_zeroes_counters(kp, B, A)) HIPCHK(hipMemsetAsync(A.work_counter, 0, 8 * 256, st));
-                HIPCHK(hipMemsetAsync(A.rec_count, 0, 256, st));
-            }
             HIPCHK(igt::launch_search_records<T>(kp, B, A, st));
             HIPCHK(igt::launch_value<T>(kp, B, net_of<T>(h), A, nullptr, nullptr, st));
             if (exact64) HIPCHK(igt::launch_reduce<T>(B, (int)W, A, st));
         } else {
-            if (host_zeroes_counters(kp, B, A)) HIPCHK(hipMemsetAsync(A.work_counter, 0, 8 * 256, st));
-            HIPCHK(igt::launch_search<T>(kp, B, A, h->nc, st));
+            HIPCHK(igt::launch_search<T>(kp, B, A, st));
         }
         if (it < p.refine_iters) {   // winner of this pass -> centre / span of the next one
             igt::SolveArgs<T> R = A;
@@ -885,11 +857,6 @@ int igt_create(const igt_params* p, int device, igt_handle** out) {
     h->p = *p;
     h->kp = make_kp(*p, 0);
     h->device = device;
-    if (const char* e = std::getenv("IGT_NC")) {
-        const int v = std::atoi(e);
-        if (v == 1 || v == 2 || v == 4) h->nc = v;
-    }
-    while ((p->C / 64) % h->nc) h->nc /= 2;
     // developer sweeps: the environment is read here, not on every solve
     if (const char* e = std::getenv("IGT_DEV_CKPT")) h->dev_ckpt = std::max(std::atoi(e), 0);
     if (const char* e = std::getenv("IGT_DEV_TRAJ_MAX")) h->dev_traj_max = std::max(std::atoi(e), 0);

@@ -671,57 +671,46 @@ __global__ __launch_bounds__(256) void cartesian_euler_kernel(int n, int steps, 
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-// whether launch_search_fast will run build_queues_kernel (which also zeroes the unit counters)
-bool search_builds_queues(const KP& P, int B, const SolveArgs<float>& A) {
-    const int W = (P.C + 127) / 128;
-    return A.queue_order && W <= 256 && ((B + 7) / 8) * W <= QB_THREADS * QB_TRIPS && !(P.dev & DEV_NO_QUEUE_ORDER);
-}
-// The arguments every float search kernel takes (IGT_SEARCH_ARGS), out of SolveArgs
-template <class Kernel>
-static hipError_t launch_search_kernel(Kernel kernel, size_t grid, const KP& Pr, int B, int W, int queues, const unsigned* order,
-                                       int order_stride, const SolveArgs<float>& A, hipStream_t st) {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, st, Pr, B, W, queues, A.work_counter, order, order_stride, A.ckpt, A.ck_parts,
-                       A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.rec_sN, A.rec_vN,
-                       A.rec_J, A.rec_viol, A.rec_count, A.rec_b);
-    return hipGetLastError();
-}
+// float search: the prelude and the kernel that A.plan names (igt_launch.h plan_search32, where the rules and their
+// measurements are) -- persistent waves on the per-XCD queues, one 128-candidate unit at a time
 template <int CAND, bool HI, bool VALUE>
 static hipError_t launch_search_fast(const KP& P, int B, const SolveArgs<float>& A, hipStream_t st) {
-    const int W = (P.C + 127) / 128;
-    const size_t total = (size_t)B * W;
-    // persistent waves on per-XCD queues, 2 per SIMD.  The 3-per-SIMD build (168 VGPRs, a spill around each unit) was
-    // ahead on big batches in round 1; with the sub-step variants unrolled it spills 228 B/lane and is behind at every
-    // size but one (B = 32 768: +0.7 %) -- it stays selectable for A/B runs (DEV_WAVES3)
-    const bool o3 = IGT_DEV_KERNELS && (P.dev & DEV_WAVES3) != 0;
-    const size_t slots = (size_t)A.n_cu * 4 * (o3 ? 3 : (A.waves_per_simd == 1 ? 1 : 2));
-    const size_t grid = total < slots ? total : slots;
-    const unsigned* order = nullptr;
-    const int order_stride = ((B + 7) / 8) * W;
+    const Search32Plan& plan = A.plan;
+    const int W = plan.W;
     KP Pr = P;
-    if constexpr (CAND == CAND_TRACK && !VALUE) {
-        // tracking family, progress cost: units of acceleration rows, pruned against the scenario's incumbent (igt_fast64.h
-        // BOUND).  The [B] keys behind the partials start every pass at "none" (all ones: above every cost's key).
-        if (P.G * P.G == P.C && W * 128 == P.C && P.G >= 16 && P.G <= 64 &&
-            !(P.dev & (DEV_NO_SLICES | DEV_STEER_SLICES | DEV_NO_BOUND)) && W > 1) {
-            hipError_t e = hipMemsetAsync(A.incumbents, 0xff, (size_t)B * 8, st);
-            if (e != hipSuccess) return e;
-            Pr.dev |= DEV_LAUNCH_INCUMBENTS;
-        }
+    Pr.dev |= plan.launch_dev_bits;      // what the kernel finds behind the partials (PartJTail)
+    if (plan.incumbents()) {
+        if (CAND != CAND_TRACK || VALUE) return hipErrorInvalidValue;
+        hipError_t e = hipMemsetAsync(A.incumbents, 0xff, (size_t)B * 8, st);
+        if (e != hipSuccess) return e;
     }
-    if (search_builds_queues(P, B, A)) {                     // small batches: longest units first
+    if (plan.builds_queues)
         hipLaunchKernelGGL(build_queues_kernel<float>, dim3(8), dim3(QB_THREADS), 0, st, Pr, B, W, A.x0, A.kparams, A.queue_order,
-                           order_stride, A.work_counter);
-        order = A.queue_order;
-    }
+                           plan.order_stride, A.work_counter);
+    const unsigned* order = plan.builds_queues ? A.queue_order : nullptr;
+    const auto search = [&](auto kernel) {      // the arguments every float search kernel takes (IGT_SEARCH_ARGS), out of SolveArgs
+        hipLaunchKernelGGL(kernel, dim3(plan.grid), dim3(64), 0, st, Pr, B, W, plan.queues, A.work_counter, order, plan.order_stride,
+                           A.ckpt, plan.ck_parts, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J,
+                           A.part_c, A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol, A.rec_count, A.rec_b);
+        return hipGetLastError();
+    };
+    switch (plan.search_kernel) {
 #if IGT_DEV_KERNELS
-    if (o3) return launch_search_kernel(search_fast_kernel_o3<CAND, HI, VALUE>, grid, Pr, B, W, 8, order, order_stride, A, st);
+    case SearchKernel32::WAVES3:
+        return search(search_fast_kernel_o3<CAND, HI, VALUE>);
 #endif
-    if (A.ckpt && A.ck_parts > 1)
-        return launch_search_kernel(search_fast_kernel_o2c<CAND, HI, VALUE>, grid, Pr, B, W, 8, order, order_stride, A, st);
-    if constexpr (CAND == CAND_TRACK)
-        return launch_search_kernel(search_fast_kernel_o2w<CAND, HI, VALUE>, grid, Pr, B, W, 8, order, order_stride, A, st);
-    else
-        return launch_search_kernel(search_fast_kernel_o2<CAND, HI, VALUE>, grid, Pr, B, W, 8, order, order_stride, A, st);
+    case SearchKernel32::CHECKPOINTS:
+        return search(search_fast_kernel_o2c<CAND, HI, VALUE>);
+    case SearchKernel32::TRACK:
+        if constexpr (CAND == CAND_TRACK) return search(search_fast_kernel_o2w<CAND, HI, VALUE>);
+        break;
+    case SearchKernel32::UNITS:
+        if constexpr (CAND != CAND_TRACK) return search(search_fast_kernel_o2<CAND, HI, VALUE>);
+        break;
+    default:
+        break;
+    }
+    return hipErrorInvalidValue;      // a plan made for another family, cost or library
 }
 template <bool VALUE>
 static hipError_t dispatch_search_fast(const KP& P, int B, const SolveArgs<float>& A, hipStream_t st) {
@@ -730,7 +719,7 @@ static hipError_t dispatch_search_fast(const KP& P, int B, const SolveArgs<float
 }
 
 template <>
-hipError_t launch_search<float>(const KP& P, int B, const SolveArgs<float>& A, int, hipStream_t st) {
+hipError_t launch_search<float>(const KP& P, int B, const SolveArgs<float>& A, hipStream_t st) {
     return dispatch_search_fast<false>(P, B, A, st);
 }
 template <>
@@ -873,17 +862,19 @@ template hipError_t launch_reduce<double>(int, int, const SolveArgs<double>&, hi
 
 template <int CAND, bool HI>
 static hipError_t launch_emit_fast(const KP& P, int B, int W, const SolveArgs<float>& A, hipStream_t st) {
-    if (A.ckpt) {
-        const int Wk = (P.C + 127) / 128;
-        hipLaunchKernelGGL((emit_seg_kernel<CAND, HI>), dim3(((size_t)B * A.ck_parts + 63) / 64), dim3(64), 0, st, P, B, W, Wk,
-                           A.ck_parts,
+    const Search32Plan& plan = A.plan;      // the same plan as the search pass's, which left the checkpoints PIECES reads
+    switch (plan.emit_kernel) {
+    case EmitKernel32::PIECES:
+        hipLaunchKernelGGL((emit_seg_kernel<CAND, HI>), dim3(plan.emit_grid), dim3(64), 0, st, P, B, W, plan.W, plan.ck_parts,
                            A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.ckpt,
                            A.cost_out, A.argmin_out, A.status_out, A.x_out, A.u_out);
-        return hipGetLastError();
+        break;
+    case EmitKernel32::ONE_PIECE:
+        hipLaunchKernelGGL((emit_fast_kernel<CAND, HI>), dim3(plan.emit_grid), dim3(64), 0, st, P, B, W, A.x0, A.u_prev,
+                           A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.cost_out, A.argmin_out,
+                           A.status_out, A.x_out, A.u_out);
+        break;
     }
-    hipLaunchKernelGGL((emit_fast_kernel<CAND, HI>), dim3((B + 63) / 64), dim3(64), 0, st, P, B, W, A.x0, A.u_prev,
-                       A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), A.part_J, A.part_c, A.cost_out, A.argmin_out,
-                       A.status_out, A.x_out, A.u_out);
     return hipGetLastError();
 }
 // float path: W per-slice partials per scenario are reduced here; double path: argmin_out is already final

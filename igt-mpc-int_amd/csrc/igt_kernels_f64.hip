@@ -1526,7 +1526,7 @@ static hipError_t dispatch_search64(const KP& P, int B, const SolveArgs<double>&
     return with_build(P, [&](auto cand, auto hi, auto nrk) { return launch_search64<cand(), hi(), nrk(), VALUE>(P, B, A, st); });
 }
 template <>
-hipError_t launch_search<double>(const KP& P, int B, const SolveArgs<double>& A, int, hipStream_t st) {
+hipError_t launch_search<double>(const KP& P, int B, const SolveArgs<double>& A, hipStream_t st) {
     return dispatch_search64<false>(P, B, A, st);
 }
 template <>

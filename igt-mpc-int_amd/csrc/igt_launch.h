@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "igt_device.h"
 #include "igt_value_net.h"
 #include "igt_value_polish_layout.h"
@@ -101,6 +102,7 @@ struct Search64Env {      // what the plan reads besides KP, the batch size and 
 constexpr int EMIT_PRIORITY_OVERLAP = 3;         // s_setprio level of the one-piece emit beside resident searches (plan_search64 emit_priority)
 struct Search64Plan {
     int W;                            // 64-candidate units per scenario
+    int partials;                     // [B, partials] part_J / part_c: one per unit
     SearchKernel64 search_kernel;
     size_t grid;                      // workgroups of the search kernel
     int queues;                       // 8, or 0: every unit has a wave of its own
@@ -118,15 +120,19 @@ struct Search64Plan {
     size_t ck_records;                // [B W] checkpoint records of CK_RECORD_DOUBLES behind the partials (PIECES reads them)
     size_t queue_order_words;         // [8][ceil(B/8) W] unit order of the queues (either queue builder)
     bool memset_counters;             // the host zeroes the unit counters: queues that no builder zeroes
+    bool reset_rec_count;             // value-network cost: the host zeroes rec_count before every pass (the compact list's lengths)
     int emit_priority;                // ONE_PIECE: the wave priority emit_f64_kernel sets at its top (0: none)
     bool sorts_queues() const { return rows_build_queues || separate_queue_builder; }
+    // what only a float solve has (Search32Plan): solve_impl reads either plan under one set of names
+    static constexpr size_t ckpt_doubles = 0;
+    static constexpr bool reset_best_key = false;
 };
 
 // value: the pass writes per-candidate records for the value network (launch_search_records), else the progress cost.
 // P.refine_it is not read: one plan serves every refinement pass of a solve.
 inline Search64Plan plan_search64(const KP& P, int B, bool value, const Search64Env& env) {
     Search64Plan p{};
-    const int W = p.W = P.C / 64;
+    const int W = p.W = p.partials = P.C / 64;
     const size_t total = (size_t)B * W;
     p.order_stride = ((B + 7) / 8) * W;
     if (env.dev_kernels && (P.dev & DEV_EXACT64)) {      // developer switch: oracle-order kernels, four scenarios per workgroup
@@ -248,6 +254,7 @@ inline Search64Plan plan_search64(const KP& P, int B, bool value, const Search64
     if (captures_trajectories) p.traj_doubles = total * traj_unit_doubles(P.N);
     if (search_builds_queues) p.queue_order_words = (size_t)((B + 7) / 8) * 8 * W;
     p.memset_counters = !search_is_static && !search_builds_queues;
+    p.reset_rec_count = value;
     return p;
 }
 
@@ -266,13 +273,122 @@ __host__ __device__ inline size_t cand_table_doubles(int C, int N) { return (siz
 __host__ __device__ inline size_t cand_slab_doubles(int N) { return (size_t)2 * N * 64; }              // one unit's part of it
 inline Search64Plan plan_candidates64(const KP& P, int B, bool value) {
     Search64Plan p{};
-    p.W = P.C / 64;
+    p.W = p.partials = P.C / 64;
     p.grid = (size_t)B * p.W;
     p.order_stride = ((B + 7) / 8) * p.W;
     const bool staged = !value && cand_slab_doubles(P.N) * 8 <= CAND_SLAB_MAX_BYTES;
     p.search_kernel = staged ? SearchKernel64::CANDIDATES_STAGED : SearchKernel64::CANDIDATES_DIRECT;
     p.emit_kernel = EmitKernel64::ONE_PIECE;
-    return p;      // queues 0, no prelude, no launch-time bits, no trajectories, records or queue order, no memset, priority 0
+    p.reset_rec_count = value;
+    return p;      // queues 0, no prelude, no launch-time bits, no trajectories, records or queue order, no counter memset, priority 0
+}
+
+// ---- the plan of one float solve: what it runs, decided once on the host ----
+// plan_search32 states the search kernel and its grid, the queue builder, the tracking family's incumbents, the checkpoints and
+// the emit kernel, the workspace and the memsets.  igt_api.hip solve_impl carves its workspace from the plan; launch_search_fast /
+// launch_emit_fast (igt_kernels.hip) switch on it.  Host code over KP and plain numbers, no pointers: tests/search_plan32.cpp
+// checks it without a GPU.
+enum class SearchKernel32 {
+    WAVES3,           // search_fast_kernel_o3: the 3-waves-per-SIMD developer builds (DEV_WAVES3)
+    CHECKPOINTS,      // search_fast_kernel_o2c: leaves horizon checkpoints for the emit in pieces
+    TRACK,            // search_fast_kernel_o2w: the tracking family, held to two waves per SIMD
+    UNITS,            // search_fast_kernel_o2
+};
+enum class EmitKernel32 {
+    PIECES,           // emit_seg_kernel: ck_parts lanes per scenario roll the winner's pieces from the search's checkpoints
+    ONE_PIECE,        // emit_fast_kernel
+};
+struct Search32Env {      // what the plan reads besides KP, the batch size and the cost
+    int n_cu;
+    int waves_per_simd;   // of the persistent search grid: 2, or 1 when solves overlap (igt_set_concurrency >= 3)
+    int dev_ckpt = -1;                           // developer sweeps (IGT_DEV_CKPT): the pieces of the emit (-1, 0: the shipped rule)
+    bool dev_kernels = IGT_DEV_KERNELS;          // the library carries the developer kernels; without them igt_create refuses their flags
+};
+constexpr int SEARCH32_QUEUES = 8;
+struct Search32Plan {
+    int W;                            // units per scenario: 128-candidate slices, two candidates per lane
+    int partials;                     // [B, partials] part_J / part_c: one per unit, or one per scenario (value-network cost)
+    SearchKernel32 search_kernel;
+    size_t grid;                      // workgroups (one wave each) of the search kernel
+    int queues;                       // SEARCH32_QUEUES, always
+    int order_stride;                 // entries per queue of the unit order
+    bool builds_queues;               // build_queues_kernel<float> runs: the queues longest unit first, the unit counters zeroed
+    int launch_dev_bits;              // OR-ed into the search kernel's and the builder's KP::dev (DEV_LAUNCH_INCUMBENTS)
+    int ck_parts;                     // pieces the horizon is emitted in (igt_device.h Seg / Ckpt): 1, 2, 4 -- up to SEG_MAX_PARTS
+    EmitKernel32 emit_kernel;
+    size_t emit_grid;                 // workgroups (one wave each) of the emit kernel
+    // workspace to carve; 0: not taken
+    size_t ckpt_doubles;              // [ck_parts - 1][B W][SEG_UNIT_DOUBLES] horizon checkpoints of the search pass for emit
+    size_t queue_order_words;         // [8][ceil(B/8) W] unit order of the queues
+    bool memset_counters;             // the host zeroes the unit counters: no builder does
+    bool reset_rec_count, reset_best_key;   // value-network cost: the host resets the compact list's length (0) and the [B] keys (0xff)
+    // the [B] incumbents behind the partials are in use: the host sets them to "none" (0xff) before every pass
+    bool incumbents() const { return (launch_dev_bits & DEV_LAUNCH_INCUMBENTS) != 0; }
+    // what only a float64 solve has (Search64Plan): solve_impl reads either plan under one set of names
+    static constexpr size_t ck_records = 0, traj_doubles = 0;
+};
+
+// value: the pass appends the feasible candidates to the compact list for the value network (launch_search_records), else the
+// progress cost.  P.refine_it is not read: one plan serves every refinement pass of a solve.
+inline Search32Plan plan_search32(const KP& P, int B, bool value, const Search32Env& env) {
+    Search32Plan p{};
+    // units per scenario of the search kernel: 128-candidate slices (two candidates per lane; an odd number of 64-candidate
+    // chunks: the last slice rolls its chunk twice)
+    const int W = p.W = (P.C + 127) / 128;
+    // per-scenario partials: the value path reduces to ONE per scenario (compact list + atomicMin), the progress cost keeps
+    // one per 128-candidate slice
+    p.partials = value ? 1 : W;
+    const size_t total = (size_t)B * W;
+    // persistent waves on per-XCD queues, 2 per SIMD.  The 3-per-SIMD build (168 VGPRs, a spill around each unit) was
+    // ahead on big batches in round 1; with the sub-step variants unrolled it spills 228 B/lane and is behind at every
+    // size but one (B = 32 768: +0.7 %) -- it stays selectable for A/B runs (DEV_WAVES3)
+    const bool o3 = env.dev_kernels && (P.dev & DEV_WAVES3) != 0;
+    const size_t slots = (size_t)env.n_cu * 4 * (o3 ? 3 : (env.waves_per_simd == 1 ? 1 : 2));
+    p.grid = total < slots ? total : slots;
+    p.queues = SEARCH32_QUEUES;
+    p.order_stride = ((B + 7) / 8) * W;
+
+    // small float batches: emit in 4 pieces from checkpoints of the search pass.  Measured (search + emit): +15 % at
+    // B = 1024, +12 % at 2048, +3 % at 4096, -1 % at 8192 -- but the records are ~150 MB of HBM writes per B = 4096 solve
+    // against ~1 MB of algorithmic traffic, so they are only spent where emit latency dominates.
+    int ck_parts = 1;
+    if (B <= 2048 && P.N % 4 == 0 && P.N >= 8) ck_parts = 4;
+    else if (B <= 2048 && P.N % 2 == 0 && P.N >= 4) ck_parts = 2;
+    if (env.dev_ckpt >= 1 && env.dev_ckpt <= SEG_MAX_PARTS && P.N % env.dev_ckpt == 0 && P.N >= 2 * env.dev_ckpt)
+        ck_parts = env.dev_ckpt;      // threshold sweeps, at every batch size; a count the horizon does not take is ignored
+    // The 3-per-SIMD build leaves no checkpoints, so its solves emit in one piece.  (Before the plan the search launcher took
+    // the _o3 build first and the emit launcher the checkpoints all the same: a DEV_WAVES3 solve of B <= 2048 emitted its
+    // pieces from checkpoints nobody had written.  No test ran one; tests/search_plan32.cpp states both sides.)
+    if (o3) ck_parts = 1;
+    p.ck_parts = ck_parts;
+    const bool ckpt = ck_parts > 1;
+    if (ckpt) p.ckpt_doubles = (size_t)(ck_parts - 1) * total * SEG_UNIT_DOUBLES;
+
+    // Small batches: the search queues are sorted longest unit first (build_queues_kernel), which also zeroes the unit counters.
+    // The order words are taken for every B <= 6144, also where no builder runs (W > 256, a queue longer than the builder's
+    // QB_THREADS * QB_TRIPS, DEV_NO_QUEUE_ORDER): they lie in front of the value path's records, and on the float64 side moving
+    // one such array changed the headline by 2 % with identical kernels (profiles/search_plan_identity.txt, section 4) -- the
+    // workspace stays where it was measured.
+    if (B <= 6144) p.queue_order_words = (size_t)((B + 7) / 8) * 8 * W;
+    p.builds_queues = p.queue_order_words != 0 && W <= 256 && ((B + 7) / 8) * W <= QB_THREADS * QB_TRIPS && !(P.dev & DEV_NO_QUEUE_ORDER);
+    p.memset_counters = !p.builds_queues;
+
+    // tracking family, progress cost: units of acceleration rows (igt_kernels.hip accel_units), pruned against the scenario's
+    // incumbent (igt_fast64.h BOUND).  The [B] keys behind the partials start every pass at "none" (all ones: above every
+    // cost's key).  Not with one unit per scenario -- nothing to prune against -- and not with DEV_NO_BOUND.
+    if (P.cand_mode == CAND_TRACK && !value && P.G * P.G == P.C && W * 128 == P.C && P.G >= 16 && P.G <= 64 &&
+        !(P.dev & (DEV_NO_SLICES | DEV_STEER_SLICES | DEV_NO_BOUND)) && W > 1)
+        p.launch_dev_bits |= DEV_LAUNCH_INCUMBENTS;
+
+    p.search_kernel = o3                          ? SearchKernel32::WAVES3
+                      : ckpt                      ? SearchKernel32::CHECKPOINTS
+                      : P.cand_mode == CAND_TRACK ? SearchKernel32::TRACK
+                                                  : SearchKernel32::UNITS;
+    // emit: ck_parts lanes per scenario on the checkpoints, else one lane per scenario
+    p.emit_kernel = ckpt ? EmitKernel32::PIECES : EmitKernel32::ONE_PIECE;
+    p.emit_grid = ((size_t)B * ck_parts + 63) / 64;
+    p.reset_rec_count = p.reset_best_key = value;
+    return p;
 }
 
 template <typename T>
@@ -306,12 +422,11 @@ struct SolveArgs {   // all device pointers
     T* p_vec;              // [B, 128] first-layer offsets
     // float path: feasible candidates appended by the search pass (count, scenario, candidate in rec_viol's storage)
     unsigned* work_counter;         // the search's 8 unit counters, 256 B apart (zeroed before every launch); unit_trace behind them
-    int n_cu;                       // compute units (sizes the persistent search grid)
-    int waves_per_simd;             // of the persistent search grid: 2, or 1 when solves overlap (igt_set_concurrency); 0 = 2
-    Search64Plan plan;              // double path: what the search and emit launchers run (plan_search64)
-    double* ckpt;                   // [ck_parts-1][B*Wk] horizon checkpoints of the search pass for emit (null: none)
-    int ck_parts;                   // pieces the horizon is emitted in (igt_device.h Seg / Ckpt)
-    unsigned* queue_order;          // [8][ceil(B/8) W] longest-first unit order of the search queues (null: index order)
+    int n_cu;                       // compute units: the grids of the value-network kernels (launch_value)
+    // what the search and emit launchers run, and what solve_impl carved for them (plan_search32; plan_search64 / plan_candidates64)
+    std::conditional_t<sizeof(T) == 4, Search32Plan, Search64Plan> plan;
+    double* ckpt;                   // float path: [ck_parts-1][B W] horizon checkpoints of the search pass for emit (null: none)
+    unsigned* queue_order;          // [8][ceil(B/8) W] longest-first unit order of the search queues (null: not taken)
     unsigned* rec_count;
     int32_t* rec_b;
     unsigned long long* best_key;   // [B] per-scenario (orderable cost, candidate) minimum
@@ -369,8 +484,7 @@ __host__ __device__ inline unsigned long long* unit_trace(unsigned* work_counter
     return reinterpret_cast<unsigned long long*>(work_counter + WORK_COUNTER_WORDS);
 }
 
-bool search_builds_queues(const KP& P, int B, const SolveArgs<float>& A);   // then no memset of the counters is needed
-template <typename T> hipError_t launch_search(const KP& P, int B, const SolveArgs<T>& A, int nc, hipStream_t st);
+template <typename T> hipError_t launch_search(const KP& P, int B, const SolveArgs<T>& A, hipStream_t st);
 template <typename T> hipError_t launch_emit(const KP& P, int B, int W, const SolveArgs<T>& A, hipStream_t st);
 // value-net cost: search pass that writes per-candidate records, then prep + MLP + per-chunk arg-min
 template <typename T> hipError_t launch_search_records(const KP& P, int B, const SolveArgs<T>& A, hipStream_t st);

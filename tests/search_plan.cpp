@@ -178,7 +178,9 @@ static void check_point(const KP& P, int B, bool value, const Search64Env& env) 
     const bool pool = p.search_kernel == SearchKernel64::POOL;
 
     // every field against what the parent did
-    CHECK(p.W == W);
+    CHECK(p.W == W && p.partials == W);                                    // solve_impl: W = value ? C / 64 : Wk, Wk = C / 64
+    CHECK(p.reset_rec_count == (value && !(P.dev & DEV_EXACT64)));         // solve_impl: if (value) ... else if (!exact64) memset(rec_count)
+    CHECK(p.ckpt_doubles == 0 && !p.reset_best_key);                       // the float plan's
     CHECK(p.search_kernel == d.search);
     CHECK(p.grid == d.grid && p.grid >= 1);
     CHECK(p.emit_kernel == d.emit);

@@ -14,8 +14,7 @@ from igtmpc import BatchSolver  # noqa: E402
 from igtmpc.scenarios import make_batch  # noqa: E402
 
 
-def run(dtype, B, nc, iters=5, straight=None, net=None):
-    os.environ['IGT_NC'] = str(nc)
+def run(dtype, B, iters=5, straight=None, net=None):
     npdt = np.float32 if dtype == 'f32' else np.float64
     b = make_batch(B, dtype=npdt)
     if straight is True:
@@ -61,14 +60,14 @@ def host_mode(B=4096):
 
 if __name__ == '__main__':
     host_mode()
-    run('f32', 4096, 2)
-    run('f32', 65536, 2)
+    run('f32', 4096)
+    run('f32', 65536)
     g = np.load(os.path.join(ROOT, 'tests', 'golden', 'value_net_golden.npz'))
     for sc in (1, 3):
         layers, i = [], 0
         while f'sc{sc}_W{i}' in g:
             layers.append((g[f'sc{sc}_W{i}'], g[f'sc{sc}_b{i}'])); i += 1
-        run('f32', 65536, 2, net=layers)
-        run('f32', 4096, 2, net=layers)
+        run('f32', 65536, net=layers)
+        run('f32', 4096, net=layers)
     if len(sys.argv) > 1:
-        run('f64', 4096, 1, iters=2)
+        run('f64', 4096, iters=2)
