@@ -70,6 +70,8 @@ struct igt_handle {
     int dev_ckpt = -1;             // IGT_DEV_CKPT / IGT_DEV_TRAJ_MAX (threshold sweeps), read once at igt_create; -1: not set
     int dev_traj_max = -1;
     int dev_reserve_pool = -1, dev_reserve_units = -1;      // IGT_DEV_RESERVE / IGT_DEV_RESERVE_UNITS (developer library only); -1: not set
+    int dev_poison = -1;           // IGT_DEV_POISON (0..255), read once at igt_create: every call that carves the workspace first fills
+                                   // all of it with this byte (carve_work); -1: not set, nothing is enqueued
 };
 
 namespace {
@@ -345,6 +347,10 @@ template <class Carve> int carve_work(igt_handle* h, hipStream_t st, const Carve
     Arena sizing{nullptr, 0};
     carve(sizing);
     if (int rc = ensure_work(h, sizing.off, st)) return rc;
+    // IGT_DEV_POISON: the whole workspace -- not this call's share alone -- holds one known byte before the entry's own memsets and
+    // launches, so that a piece read before it is written shows as a wrong answer whatever the call before left there (DESIGN
+    // section 6).  A memset node would change a captured graph: not under capture.
+    if (h->dev_poison >= 0 && h->d_work && !capturing(st)) HIPCHK(hipMemsetAsync(h->d_work, h->dev_poison, h->work_bytes, st));
     Arena wa{(char*)h->d_work, 0};
     carve(wa);
     return IGT_OK;
@@ -860,6 +866,11 @@ int igt_create(const igt_params* p, int device, igt_handle** out) {
     // developer sweeps: the environment is read here, not on every solve
     if (const char* e = std::getenv("IGT_DEV_CKPT")) h->dev_ckpt = std::max(std::atoi(e), 0);
     if (const char* e = std::getenv("IGT_DEV_TRAJ_MAX")) h->dev_traj_max = std::max(std::atoi(e), 0);
+    if (const char* e = std::getenv("IGT_DEV_POISON")) {      // a whole decimal number in 0..255; anything else is ignored
+        char* end = nullptr;
+        const long v = std::strtol(e, &end, 10);
+        if (end != e && *end == '\0' && v >= 0 && v <= 255) h->dev_poison = (int)v;
+    }
 #if IGT_DEV_KERNELS
     // sweeps of the slot reserve (igt_launch.h search64_grid): waves per 8 compute units a float64 search leaves alone
     if (const char* e = std::getenv("IGT_DEV_RESERVE")) h->dev_reserve_pool = std::max(std::atoi(e), 0);

@@ -494,7 +494,10 @@ int igt_rollout_candidates_f64(igt_handle* h, int32_t B, const double* x0, const
  * the unit winners (float64, progress cost, N >= 8),
  * 288 B of queue order / counters; value-network cost: + 36 B per candidate (the list of feasible candidates).  Small float64
  * batches (no more 64-candidate units than the device has SIMDs: B <= 256 at C = 256) keep every candidate's trajectory for
- * the emit pass: 9 (N + 1) 64 doubles per unit = 97 KB per unit at N = 20, i.e. up to 99 MB per handle at B C / 64 = 1024. */
+ * the emit pass: 9 (N + 1) 64 doubles per unit = 97 KB per unit at N = 20, i.e. up to 99 MB per handle at B C / 64 = 1024.
+ * Growth frees the old workspace, so it invalidates every stream graph captured on the handle before it (a replay would use the
+ * freed addresses).  The size depends on the plan, not on B alone -- a float64 solve of B = 33 needs more than one of B = 4096 --:
+ * before capturing, run once eagerly every kind of call the handle will serve while the graph is in use. */
 
 /* Per-kernel timing with HIP events on the launch stream (used by bench.py for the
  * roofline line).  While enabled, every solve records events around its kernels;
