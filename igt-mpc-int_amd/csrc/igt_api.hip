@@ -621,6 +621,55 @@ int frenet_step_impl(igt_handle* h, int32_t n, const T* x, const T* u, const T* 
     return stg.download();
 }
 
+// The closed-loop step behind a solve: one launch of loop_advance_kernel, nothing carved and nothing kept.  Host mode stages x and
+// u_prev twice, as input and as output (the kernel reads the one and writes the other); the counter and the two log columns need
+// only what the call brings back, so the host writes them itself and the logs never cross the bus.
+template <typename T>
+int loop_advance_impl(igt_handle* h, int32_t n, double* x, double* u_prev, const double* kparams, const int32_t* status,
+                      const T* x_sol, const T* u_sol, double a_brake, int32_t* has_plan, T* plan_x, T* plan_u, T* u_ws,
+                      const uint32_t* flags_in, uint32_t* flags_out, int64_t* infeasible, double* x_log, double* u_log,
+                      const int64_t* step, int32_t T_log, int mem, void* stream) {
+    if (!h) return fail(IGT_E_INVALID, "null handle");
+    if (n < 0) return fail(IGT_E_INVALID, "n < 0");
+    Staging stg(h, mem, stream);
+    if (int rc = stg.check_mem()) return rc;      // (refused for an empty batch as well)
+    if (!flags_in != !flags_out) return fail(IGT_E_INVALID, "flags_in and flags_out go together");
+    if (!x_log != !u_log) return fail(IGT_E_INVALID, "x_log and u_log go together");
+    if (x_log && !step) return fail(IGT_E_INVALID, "logging needs step");
+    if (n == 0) return IGT_OK;
+    if (!x || !u_prev || !kparams || !status || !x_sol || !u_sol) return fail(IGT_E_INVALID, "null buffer");
+    if (!has_plan || !plan_x || !plan_u) return fail(IGT_E_INVALID, "null output buffer (has_plan, plan_x, plan_u)");
+    const int N = h->p.N;
+    const size_t n_x = (size_t)n * 7, n_u = (size_t)n * 2, n_k = (size_t)n * 3;
+    const size_t n_sx = n_x * (N + 1), n_su = n_u * N;
+    const bool host = mem == IGT_MEM_HOST;
+    igt::LoopArgs<T> A{};
+    A.a_brake = a_brake;
+    stg.in(&A.x_in, (const double*)x, n_x); stg.in(&A.u_in, (const double*)u_prev, n_u); stg.in(&A.kparams, kparams, n_k);
+    stg.in(&A.status, status, (size_t)n); stg.in(&A.x_sol, x_sol, n_sx); stg.in(&A.u_sol, u_sol, n_su);
+    stg.in(&A.flags_in, flags_in, (size_t)n);
+    stg.out(&A.x_out, x, n_x); stg.out(&A.u_out, u_prev, n_u); stg.out(&A.has_plan, has_plan, (size_t)n);
+    stg.out(&A.plan_x, plan_x, n_sx); stg.out(&A.plan_u, plan_u, n_su); stg.out(&A.u_ws, u_ws, n_su);
+    stg.out(&A.flags_out, flags_out, (size_t)n);
+    if (!host) {
+        A.infeasible = infeasible;
+        A.x_log = x_log; A.u_log = u_log; A.step = step; A.T_log = T_log;
+    }
+    if (int rc = stg.upload()) return rc;
+    HIPCHK(igt::launch_loop_advance<T>(h->kp, n, A, stg.stream()));
+    if (int rc = stg.download()) return rc;
+    if (host) {
+        if (infeasible)
+            for (int32_t i = 0; i < n; ++i) infeasible[i] += status[i] != 0;
+        if (x_log && *step >= 0 && *step < (int64_t)T_log) {
+            const size_t t = (size_t)*step, Tl = (size_t)T_log;
+            for (size_t r = 0; r < n_x; ++r) x_log[r * (Tl + 1) + t + 1] = x[r];
+            for (size_t r = 0; r < n_u; ++r) u_log[r * Tl + t] = u_prev[r];
+        }
+    }
+    return IGT_OK;
+}
+
 int cost_gradient_impl(igt_handle* h, int32_t B, const double* x0, const double* kparams, const uint32_t* flags, const double* U,
                        double* cost_out, double* grad_out, int mem, void* stream) {
     if (!h) return fail(IGT_E_INVALID, "null handle");
@@ -1170,6 +1219,20 @@ int igt_forecast_batch_f32(igt_handle* h, int32_t B, const float* ego_xyh, const
                            const int32_t* opp_route, const float* plan_x, const float* plan_u, const int32_t* has_plan,
                            float* obs_xy, float* tv_sv, int mem, void* stream) {
     return forecast_impl<float>(h, B, ego_xyh, opp, opp_a, opp_route, plan_x, plan_u, has_plan, obs_xy, tv_sv, mem, stream);
+}
+int igt_loop_advance_f64(igt_handle* h, int32_t n, double* x, double* u_prev, const double* kparams, const int32_t* status,
+                         const double* x_sol, const double* u_sol, double a_brake, int32_t* has_plan, double* plan_x,
+                         double* plan_u, double* u_ws, const uint32_t* flags_in, uint32_t* flags_out, int64_t* infeasible,
+                         double* x_log, double* u_log, const int64_t* step, int32_t T_log, int mem, void* stream) {
+    return loop_advance_impl<double>(h, n, x, u_prev, kparams, status, x_sol, u_sol, a_brake, has_plan, plan_x, plan_u, u_ws,
+                                     flags_in, flags_out, infeasible, x_log, u_log, step, T_log, mem, stream);
+}
+int igt_loop_advance_f32(igt_handle* h, int32_t n, double* x, double* u_prev, const double* kparams, const int32_t* status,
+                         const float* x_sol, const float* u_sol, double a_brake, int32_t* has_plan, float* plan_x,
+                         float* plan_u, float* u_ws, const uint32_t* flags_in, uint32_t* flags_out, int64_t* infeasible,
+                         double* x_log, double* u_log, const int64_t* step, int32_t T_log, int mem, void* stream) {
+    return loop_advance_impl<float>(h, n, x, u_prev, kparams, status, x_sol, u_sol, a_brake, has_plan, plan_x, plan_u, u_ws,
+                                    flags_in, flags_out, infeasible, x_log, u_log, step, T_log, mem, stream);
 }
 int igt_forecast_scene_f32(igt_handle* h, int32_t E, const float* x, const float* a_prev, const int32_t* route,
                            const float* plan_x, const float* plan_u, const int32_t* has_plan, float* obs_xy, float* tv_sv,

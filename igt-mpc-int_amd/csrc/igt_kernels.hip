@@ -948,6 +948,92 @@ template hipError_t launch_forecast<double>(const KP&, int, const double*, int, 
                                             const int32_t*, const double*, const double*, const int32_t*, double*, double*,
                                             hipStream_t);
 
+// ---------------------------------------------------------------------------------------
+// igt_loop_advance_*: the closed-loop step behind a solve (evaluate.py:491-545, utils.py:339-363)
+// ---------------------------------------------------------------------------------------
+// torch.nan_to_num with its defaults: NaN -> 0, +-inf -> the largest finite value of the type
+__device__ __forceinline__ double nan_to_num_dev(double v) {
+    return v != v ? 0.0 : (v > __DBL_MAX__ ? __DBL_MAX__ : (v < -__DBL_MAX__ ? -__DBL_MAX__ : v));
+}
+__device__ __forceinline__ float nan_to_num_dev(float v) {
+    return v != v ? 0.0f : (v > __FLT_MAX__ ? __FLT_MAX__ : (v < -__FLT_MAX__ ? -__FLT_MAX__ : v));
+}
+
+// One workgroup per LOOP_AGENTS agents (igt_launch.h).  Lane t < agents applies agent a0 + t's answer or takes the brake fallback
+// -- the model step is ExactStepper<double>'s, as frenet_step_kernel<ExactStepper<double>, double> calls it --, writes the new
+// state, the applied input, has_plan, the flag word, the counter and the two log columns.  Then every lane of the workgroup
+// walks the workgroup's span of x_sol and u_sol: plan_x, plan_u and the shifted warm start are written with consecutive lanes on
+// consecutive elements.  The two parts share nothing, so there is no barrier, no LDS and no atomic.
+template <typename T>
+__global__ __launch_bounds__(LOOP_THREADS) void loop_advance_kernel(KP P, int n, LoopArgs<T> A) {
+    const int N = P.N, t = threadIdx.x;
+    const int agents = loop_block_agents(n, blockIdx.x);
+    const size_t a0 = (size_t)blockIdx.x * LOOP_AGENTS;
+    if (t < agents) {
+        const size_t i = a0 + t;
+        const bool ok = A.status[i] == 0;
+        double x0[7], xn[7], un[2];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) x0[k] = A.x_in[i * 7 + k];
+        const double df_prev = A.u_in[i * 2 + 1];
+        if (ok) {                                                    // evaluate.py:491-510
+#pragma unroll
+            for (int k = 0; k < 7; ++k) xn[k] = (double)A.x_sol[(i * 7 + k) * (N + 1) + 1];
+            un[0] = (double)A.u_sol[i * 2 * N];
+            un[1] = (double)A.u_sol[(i * 2 + 1) * N];
+        } else {                                                     // evaluate.py:511-545
+            const double v = x0[5];
+            const double a_fb = v > 0 ? A.a_brake : 0.0;
+            ExactStepper<double> stp;
+            stp.init(P, A.kparams[i * 3 + 0], A.kparams[i * 3 + 1], A.kparams[i * 3 + 2]);
+            ExactStepper<double>::State st;
+            stp.set(st, x0);
+            stp.step(st, a_fb, stp.prep(df_prev));
+            stp.get(st, xn);
+            const bool neg = v < 0;                                  // evaluate.py:523-526: instantaneous stop
+#pragma unroll
+            for (int k = 0; k < 7; ++k) xn[k] = neg ? (k == 5 ? 0.0 : x0[k]) : xn[k];
+            un[0] = neg ? 0.0 : a_fb;
+            un[1] = df_prev;
+        }
+#pragma unroll
+        for (int k = 0; k < 7; ++k) A.x_out[i * 7 + k] = xn[k];
+        A.u_out[i * 2 + 0] = un[0];
+        A.u_out[i * 2 + 1] = un[1];
+        A.has_plan[i] = ok ? 1 : 0;
+        if (A.flags_out) A.flags_out[i] = A.flags_in[i] | (ok ? 2u : 0u);      // IGT_FLAG_WARM
+        if (A.infeasible) A.infeasible[i] = A.infeasible[i] + (ok ? 0 : 1);
+        if (A.x_log) {
+            const long long s = (long long)*A.step, T_log = A.T_log;
+            if (s >= 0 && s < T_log) {
+#pragma unroll
+                for (int k = 0; k < 7; ++k) A.x_log[(i * 7 + k) * (size_t)(T_log + 1) + (size_t)(s + 1)] = xn[k];
+                A.u_log[(i * 2 + 0) * (size_t)T_log + (size_t)s] = un[0];
+                A.u_log[(i * 2 + 1) * (size_t)T_log + (size_t)s] = un[1];
+            }
+        }
+    }
+    const size_t row_x = (size_t)7 * (N + 1), row_u = (size_t)2 * N;
+    const T* xs = A.x_sol + a0 * row_x;
+    T* px = A.plan_x + a0 * row_x;
+    loop_walk(agents, row_x, t, [&](size_t e) { px[e] = nan_to_num_dev(xs[e]); });
+    const T* us = A.u_sol + a0 * row_u;
+    T* pu = A.plan_u + a0 * row_u;
+    T* ws = A.u_ws ? A.u_ws + a0 * row_u : nullptr;
+    loop_walk(agents, row_u, t, [&](size_t e) {
+        const T v = nan_to_num_dev(us[e]);
+        pu[e] = v;
+        if (ws) ws[e] = (int)(e % (size_t)N) + 1 < N ? nan_to_num_dev(us[e + 1]) : v;      // utils.py:354-363: shifted, the last one held
+    });
+}
+template <typename T>
+hipError_t launch_loop_advance(const KP& P, int n, const LoopArgs<T>& A, hipStream_t st) {
+    hipLaunchKernelGGL((loop_advance_kernel<T>), dim3(loop_grid(n)), dim3(LOOP_THREADS), 0, st, P, n, A);
+    return hipGetLastError();
+}
+template hipError_t launch_loop_advance<float>(const KP&, int, const LoopArgs<float>&, hipStream_t);
+template hipError_t launch_loop_advance<double>(const KP&, int, const LoopArgs<double>&, hipStream_t);
+
 // u[B,2,N] -> u0[B,2] = u[:, :, 0]: the (a, df) each agent applies (evaluate.py:492), contiguous for the all-gather
 template <typename T>
 __global__ __launch_bounds__(256) void first_controls_kernel(int B, int N, const T* __restrict__ u, T* __restrict__ u0) {

@@ -526,6 +526,40 @@ template <typename T>
 hipError_t launch_forecast_scene(const KP& P, int E, const double* routes, int n_routes, const T* x, const T* a_prev,
                                  const int32_t* route, const T* plan_x, const T* plan_u, const int32_t* has_plan, T* obs_xy,
                                  T* tv_sv, hipStream_t st);
+// ---- igt_loop_advance_*: the closed-loop step behind a solve (igt_kernels.hip loop_advance_kernel) ----
+// A workgroup of LOOP_THREADS lanes owns LOOP_AGENTS consecutive agents.  Its lanes 0 .. agents - 1 decide and step one agent each;
+// then all of its lanes walk the agents' rows of x_sol and of u_sol -- contiguous per agent, so one contiguous span per
+// workgroup -- with consecutive lanes on consecutive elements.  What the launcher, the kernel and tests/loop_advance_shape.cpp
+// count with:
+constexpr int LOOP_THREADS = 256, LOOP_AGENTS = 16;
+inline int loop_grid(int n) { return (int)(((size_t)(n > 0 ? n : 0) + LOOP_AGENTS - 1) / LOOP_AGENTS); }
+__host__ __device__ inline int loop_block_agents(int n, int block) {      // agents of workgroup `block`: LOOP_AGENTS, fewer in the last
+    const long long left = (long long)n - (long long)block * LOOP_AGENTS;
+    return left >= LOOP_AGENTS ? LOOP_AGENTS : (left > 0 ? (int)left : 0);
+}
+// lane `thread`'s elements of a span of `agents` rows of `row` elements each: f(offset into the span)
+template <class F>
+__host__ __device__ inline void loop_walk(int agents, size_t row, int thread, F&& f) {
+    const size_t span = (size_t)agents * row;
+    for (size_t e = (size_t)thread; e < span; e += LOOP_THREADS) f(e);
+}
+// The buffers of one call.  x / u_prev are read from *_in and written to *_out: one array in device mode, the staged input and
+// output copies in host mode (a lane reads its agent's row before it writes it).
+template <typename T>
+struct LoopArgs {
+    const double* x_in; double* x_out;                  // [n,7]
+    const double* u_in; double* u_out;                  // [n,2]
+    const double* kparams;                              // [n,3]
+    const int32_t* status;                              // [n]
+    const T *x_sol, *u_sol;                             // [n,7,N+1], [n,2,N]
+    double a_brake;
+    int32_t* has_plan;                                  // [n]
+    T *plan_x, *plan_u, *u_ws;                          // u_ws may be null
+    const uint32_t* flags_in; uint32_t* flags_out;      // both or neither null
+    int64_t* infeasible;                                // may be null
+    double *x_log, *u_log; const int64_t* step; int32_t T_log;      // logs: both or neither null
+};
+template <typename T> hipError_t launch_loop_advance(const KP& P, int n, const LoopArgs<T>& A, hipStream_t st);
 template <typename T> hipError_t launch_first_controls(int B, int N, const T* u, T* u0, hipStream_t st);
 template <typename T>
 hipError_t launch_cartesian(int n, int steps, double dt, double l_r, double l_f, const T* z0, const T* u, T* z_out,

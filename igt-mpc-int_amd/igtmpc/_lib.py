@@ -40,6 +40,8 @@ _CART = [_vp, _i32, _i32, _vp, _vp, _vp, _i, _vp]
 _FSTEP = [_vp, _i32, _vp, _vp, _vp, _vp, _i, _vp]
 _FCAST = [_vp, _i32] + [_vp] * 9 + [_i, _vp]
 _FSCENE = [_vp, _i32] + [_vp] * 8 + [_i, _vp]
+# x, u_prev, kparams, status, x_sol, u_sol | a_brake | has_plan, plan_x, plan_u, u_ws, flags_in, flags_out, infeasible, x_log, u_log, step | T_log
+_LOOP = [_vp, _i32] + [_vp] * 6 + [C.c_double] + [_vp] * 10 + [_i32, _i, _vp]
 SYMBOLS = {
     'igt_version': (_i, []),
     'igt_last_error': (C.c_char_p, []),
@@ -81,6 +83,8 @@ SYMBOLS = {
     'igt_cost_gradient_vn_f64': (_i, [_vp, _i32] + [_vp] * 8 + [_i, _vp]),
     'igt_solve_candidates_f64': (_i, _SOLVE_WS),       # U[B,C,2,N] where the _ws entries take u_ws
     'igt_rollout_candidates_f64': (_i, _ROLL_WS),
+    'igt_loop_advance_f64': (_i, _LOOP),
+    'igt_loop_advance_f32': (_i, _LOOP),
     'igt_set_profiling': (_i, [_vp, _i]),
     'igt_get_kernel_ms': (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     'igt_algorithmic_bytes_per_solve': (_i, [_vp, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -88,7 +92,8 @@ SYMBOLS = {
 
 # added without a change of IGT_VERSION: a library of the same ABI from before them (IGT_LIB_PATH, tools/ab_lib.sh) lacks them
 OPTIONAL_SYMBOLS = ('igt_set_polish_gradient', 'igt_cost_gradient_f64', 'igt_terminal_value_f64', 'igt_cost_gradient_vn_f64',
-                    'igt_set_polish_step', 'igt_set_value_polish', 'igt_solve_candidates_f64', 'igt_rollout_candidates_f64')
+                    'igt_set_polish_step', 'igt_set_value_polish', 'igt_solve_candidates_f64', 'igt_rollout_candidates_f64',
+                    'igt_loop_advance_f64', 'igt_loop_advance_f32')
 
 _libs = {}
 # IGT_DEV_FLAGS bits (csrc/igt_device.h DevFlag; the launch-time bits there are the library's own and not listed here)

@@ -70,7 +70,7 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
                     eval_mode='mpc', value_net=None, device_resident=False, warm_start=None, init=None,
                     terminal_set=True, feas_tol=None, limits=None, graph=False, a_min_policy=None, constant_speed=False,
                     v0=0.0, polish_iters=0, num_agents=2, polish_grad='fd', polish_step='gradient', value_polish_iters=0,
-                    value_polish_driver='host'):
+                    value_polish_driver='host', step='torch'):
     """eval_mode 'mpc' (evaluate.py:370-639) or 'gt_mpc' (123-369: terminal value network in the cost;
     value_net = dict(layers=[(W,b),...][, Wn, mu_f, sigma_t, mu_t]), default: the network the reference ships for
     scenario sc -- its normalisation statistics are not shipped, identity unless given).  device_resident=True keeps every per-step array in HBM (torch tensors;
@@ -86,6 +86,9 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     library's 1e-6; IPOPT's constr_viol_tol is 1e-3, mpc.py:135); limits: further igt_params fields by name
     (e.g. dict(track_env=0.0); without it the tracking family's envelope scale follows the horizon: auto_track_env).
     graph=True (with device_resident): the time loop replays one captured step.
+    step (with device_resident): what turns a solve into the next step's inputs -- 'torch' (default): about 40 tensor operations
+    and the stepper handle's model step; 'fused': one kernel on the solver's own handle (BatchSolver.loop_advance, igtmpc.h
+    igt_loop_advance_*), the same bytes.  'fused' without device_resident raises ValueError.
     a_min_policy: deceleration of the brake fallback (mpc.yaml:8 a_min through evaluate.py:514; default -4);
     constant_speed: the forecast holds the other agent's speed (mpc.yaml:13-14 prediction_type, evaluate.py:76-79);
     v0: initial speed (fourwayint.yaml:11) -- load_reference_configs reads all three from the reference's files.
@@ -101,6 +104,10 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     agent against the forecast / shared plan of every other one (Jacobi, evaluate.py:469-558).  Scenario `sc`'s route tuples for
     M > 2: routes.scene_routes; init = (x[E,M,7], route tuples of length M).  eval_mode 'mpc' only beyond two (the value
     network's features are those of a two-vehicle scene, mpc.py:326-338)."""
+    if step not in ('torch', 'fused'):
+        raise ValueError(f"step must be 'torch' or 'fused', not {step!r}")
+    if step == 'fused' and not device_resident:
+        raise ValueError("step='fused' is the device-resident loop's step (igt_loop_advance_*): it needs device_resident=True")
     M = int(num_agents)
     if not 2 <= M <= 4:
         raise ValueError(f'num_agents = {num_agents}: a scene has 2, 3 or 4 vehicles (one per approach lane)')
@@ -169,7 +176,7 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
 
     if device_resident:
         out = _loop_device(solver, stepper, x, u_prev, kp, flags, rid, enc if gt else None, gt, E, M, N, M_sim, device, warm,
-                           graph=graph, a_min_policy=a_min_policy, constant_speed=constant_speed)
+                           graph=graph, a_min_policy=a_min_policy, constant_speed=constant_speed, fused=step == 'fused')
         solver.close()
         stepper.close()
         out['routes'] = pairs
@@ -246,12 +253,14 @@ def shift_controls(u):
 
 
 def _loop_device(solver, stepper, x, u_prev, kp, flags, rid, enc, gt, E, M, N, M_sim, device, warm, graph=False,
-                 a_min_policy=A_MIN_POLICY, constant_speed=False):
+                 a_min_policy=A_MIN_POLICY, constant_speed=False, fused=False):
     """The same time loop with every array resident in HBM (float64 state, solver-dtype views per call).
     graph=True: steps 0 and 1 run eagerly, then ONE step -- forecast, solve, fallback step and the ~40 small tensor
     operations between them -- is captured in a stream graph and replayed for the remaining steps (the state lives in
     fixed buffers that the captured step updates in place; the column of x_data / u_data it writes is a device-side
-    counter).  The loop is launch-bound at a few hundred problems per step; the replay removes the launches."""
+    counter).  The loop is launch-bound at a few hundred problems per step; the replay removes the launches.
+    fused=True (run_closed_loop step='fused'): the tensor operations behind the solve and the stepper's model step are one
+    launch of igt_loop_advance_* on the solver's handle; `stepper` is not used."""
     import torch
     dev = torch.device('cuda', device)
     td = torch.float32 if solver.dtype == 'f32' else torch.float64
@@ -310,6 +319,33 @@ def _loop_device(solver, stepper, x, u_prev, kp, flags, rid, enc, gt, E, M, N, M
         u_data.index_copy_(2, col, u_prev.reshape(E, 2 * M, 1))
         col.add_(1)
         x_data.index_copy_(2, col, x.reshape(E, 7 * M, 1))
+
+    if fused:
+        # step='fused': everything behind the solve is ONE kernel (igtmpc.h igt_loop_advance_*) on the solver's own handle.  It
+        # updates x and u_prev in place and writes the shared plans, the warm start, the flag words, the counter and the two
+        # log columns into the same buffers every step, so the captured step replays as it is.
+        n = E * M
+        x_n, u_n = x.reshape(n, 7), u_prev.reshape(n, 2)                  # views: the forecast reads what the kernel wrote
+        have_i = torch.zeros((E, M), dtype=torch.int32, device=dev)       # zeros until the first step has run
+        adv = dict(has_plan=have_i.reshape(n), plan_x=sol_x.reshape(n, 7, N + 1), plan_u=sol_u.reshape(n, 2, N),
+                   u_ws=torch.zeros((n, 2, N), dtype=td, device=dev), flags=torch.zeros_like(flags_t))
+        x_log, u_log = x_data.reshape(n, 7, M_sim + 1), u_data.reshape(n, 2, M_sim)      # [E,7M,T+1] agent-major: the same bytes
+        infeasible_n = infeasible.reshape(n)
+
+        def step(first, warm_ok=True):      # noqa: F811 -- replaces the torch step above
+            a_fc = a_fc0 if (gt and first) else u_prev[..., 0]
+            if constant_speed:
+                a_fc = torch.zeros_like(u_prev[..., 0])
+            obs, tv = solver.forecast_scene(x.to(td), a_fc.to(td).contiguous(), rid_t, sol_x, sol_u, have_i)
+            tv = tv.reshape(E * M, -1)
+            fl, u_ws = flags_t, None
+            if warm and not first and warm_ok:
+                fl, u_ws = adv['flags'], adv['u_ws']                     # the previous step's loop_advance left both
+            out = solver.solve(x_n.to(td).contiguous(), u_n.to(td).contiguous(), kp_s, fl, obs, tv if gt else None, enc_t,
+                               u_ws=u_ws)
+            solver.loop_advance(x_n, u_n, kp_d, out['status'], out['x'], out['u'], a_min_policy, flags=flags_t,
+                                infeasible=infeasible_n, x_log=x_log, u_log=u_log, step=col, out=adv)
+            col.add_(1)
 
     torch.cuda.synchronize(dev)
     t_start = time.perf_counter()
@@ -477,6 +513,8 @@ def main():
     ap.add_argument('--verbose', action='store_true')
     ap.add_argument('--device_resident', action='store_true', help='keep all per-step arrays in HBM (torch tensors)')
     ap.add_argument('--graph', action='store_true', help='with --device_resident: capture one step in a stream graph and replay it')
+    ap.add_argument('--step', default='torch', choices=['torch', 'fused'],
+                    help="with --device_resident: 'fused' runs everything behind the solve as one kernel (igt_loop_advance_*)")
     ap.add_argument('--cand_mode', default='track', choices=['lattice', 'ramp_hold', 'track'])
     ap.add_argument('--dtype', default='f64', choices=['f64', 'f32'])
     ap.add_argument('--polish_iters', type=int, default=0, help='f64, eval_mode mpc: projected-gradient steps on each winner (0..4)')
@@ -510,7 +548,7 @@ def main():
                         value_net=net, device_resident=a.device_resident, cand_mode=a.cand_mode, dtype=a.dtype, graph=a.graph,
                         polish_iters=a.polish_iters, polish_grad=a.polish_grad, polish_step=a.polish_step,
                         value_polish_iters=a.value_polish_iters, value_polish_driver=a.value_polish_driver,
-                        num_agents=a.num_agents,
+                        num_agents=a.num_agents, step=a.step,
                         **kw)
     if a.save_dir is not None:
         policy = {'type': 'MPC', 'N': a.N, 'dt': kw.get('dt', 0.1), 'a_min': -4, 'a_max': 3, 'v_min': -1.0, 'v_max': 5,      # mpc.yaml's keys

@@ -193,7 +193,7 @@ class BatchSolver:
                 if not _is_torch(a) or not a.is_cuda:
                     raise TypeError('device mode needs every buffer to be a CUDA torch tensor')
                 want = {np.float32: torch.float32, np.float64: torch.float64, np.uint32: torch.int32,
-                        np.int32: torch.int32}[dt]
+                        np.int32: torch.int32, np.int64: torch.int64}[dt]
                 if a.dtype != want and not (dt is np.uint32 and a.dtype in (torch.int32, torch.uint32)):
                     raise TypeError(f'tensor dtype {a.dtype} does not match {dt.__name__}')
                 if a.device.index != self.device:
@@ -622,6 +622,66 @@ class BatchSolver:
             out = np.empty((n, 7), dt)
         mode, ptrs, keep = self._prep([x, u, kparams, out], [(n, 7), (n, 2), (n, 3), (n, 7)], [dt] * 4)
         self._check(self._fstep(self._h, n, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        return out
+
+    def loop_advance(self, x, u_prev, kparams, status, x_sol, u_sol, a_brake, flags=None, infeasible=None, x_log=None,
+                     u_log=None, step=None, want_ws=True, out=None, stream=None):
+        """The closed-loop step behind a solve, in one kernel (igtmpc.h igt_loop_advance_*; evaluate.py:491-545): per agent,
+        apply the first control of a solved problem or take the brake fallback (deceleration a_brake), and leave what the next
+        forecast and solve read.  n = E M agents in the solve's row order.
+        x[n,7], u_prev[n,2] (float64) are UPDATED IN PLACE; kparams[n,3] (float64); status[n], x_sol[n,7,N+1], u_sol[n,2,N]: the
+        solve's out['status'], out['x'], out['u'] (the solver's dtype)
+        -> dict(has_plan[n] int32, plan_x[n,7,N+1], plan_u[n,2,N], u_ws[n,2,N] | None (want_ws=False), flags[n] | None);
+        `out` may bring those buffers (a captured step writes the same ones every replay).
+        flags[n]: out['flags'] = flags | IGT_FLAG_WARM where solved -- with u_ws the next solve's warm start.
+        infeasible[n] (int64): += 1 where not solved, in place.  x_log[n,7,T+1], u_log[n,2,T] (float64) with step (an int64
+        tensor of one element on the device; host mode: an int): u_log[:,:,step] and x_log[:,:,step+1] are written in place,
+        a step outside 0..T-1 writes nothing.  numpy arrays or tensors on the solver's GPU, as solve."""
+        fn = self._entry(f'igt_loop_advance_{self.dtype}')
+        n, N, dt, f8 = int(x.shape[0]), self.N, self.np_dtype, np.float64
+        torch_mode = _is_torch(x)
+        if (x_log is None) != (u_log is None):
+            raise ValueError('x_log and u_log go together')
+        if x_log is not None and step is None:
+            raise ValueError('logging needs step')
+        T_log = int(u_log.shape[2]) if u_log is not None else 0
+        if step is not None and not torch_mode and not isinstance(step, np.ndarray):
+            step = np.array([int(step)], dtype=np.int64)
+        if x_log is None:
+            step = None
+        out = dict(out or {})
+        if torch_mode:
+            import torch
+            td = torch.float32 if self.dtype == 'f32' else torch.float64
+            new = lambda shp, d: torch.empty(shp, dtype=d, device=x.device)
+            i32, u32 = torch.int32, torch.int32
+        else:
+            td, new, i32, u32 = dt, lambda shp, d: np.empty(shp, d), np.int32, np.uint32
+        out.setdefault('has_plan', new((n,), i32))
+        out.setdefault('plan_x', new((n, 7, N + 1), td))
+        out.setdefault('plan_u', new((n, 2, N), td))
+        if want_ws:
+            out.setdefault('u_ws', new((n, 2, N), td))
+        else:
+            out['u_ws'] = None
+        if flags is not None:
+            out.setdefault('flags', new((n,), u32))
+        else:
+            out['flags'] = None
+        arrs = [x, u_prev, kparams, status, x_sol, u_sol, out['has_plan'], out['plan_x'], out['plan_u'], out['u_ws'], flags,
+                out['flags'], infeasible, x_log, u_log, step]
+        shapes = [(n, 7), (n, 2), (n, 3), (n,), (n, 7, N + 1), (n, 2, N), (n,), (n, 7, N + 1), (n, 2, N), (n, 2, N), (n,), (n,),
+                  (n,), (n, 7, T_log + 1), (n, 2, T_log), (1,)]
+        dts = [f8, f8, f8, np.int32, dt, dt, np.int32, dt, dt, dt, np.uint32, np.uint32, np.int64, f8, f8, np.int64]
+        mode, p, keep = self._prep(arrs, shapes, dts)
+        if mode == L.IGT_MEM_HOST:
+            written = dict(x=(x, 0), u_prev=(u_prev, 1), has_plan=(out['has_plan'], 6), plan_x=(out['plan_x'], 7),
+                           plan_u=(out['plan_u'], 8), u_ws=(out['u_ws'], 9), flags=(out['flags'], 11), infeasible=(infeasible, 12),
+                           x_log=(x_log, 13), u_log=(u_log, 14))
+            for k, (a, i) in written.items():
+                if a is not None and keep_is_copy(a, p[i]):
+                    raise ValueError(f'{k} is written in place: it must be a contiguous array of its dtype')
+        self._check(fn(self._h, n, *p[:6], float(a_brake), *p[6:], T_log, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
         return out
 
     def cartesian_euler(self, z0, u, stream=None):

@@ -488,6 +488,41 @@ int igt_rollout_candidates_f64(igt_handle* h, int32_t B, const double* x0, const
                                const double* U, double* X_all, double* U_all, double* cost_all, uint32_t* viol_all, int mem,
                                void* stream);
 
+/* The closed-loop step behind a solve: what the reference's driver does with every agent's answer before the next timestep
+ * (evaluate.py:491-545), for n = E M agents in the row order of igt_forecast_scene_* / the solve's B.  Per agent i, with
+ * ok = status[i] == 0:
+ *   ok      x <- x_sol[i,:,1], u_prev <- u_sol[i,:,0] (widened to double)                              (evaluate.py:491-510)
+ *   not ok  the brake fallback (evaluate.py:511-545): a_fb = a_brake where v = x[5] > 0, else 0; x <- one model step of
+ *           (x, (a_fb, u_prev[1]), kparams) -- igt_frenet_step_f64's arithmetic and bits, with the handle's dt, n_rk4, l_r,
+ *           l_f, in both entries --, u_prev <- (a_fb, u_prev[1]); where v < 0 instead x <- x with v = 0 and u_prev[0] <- 0
+ *           (evaluate.py:523-526).  A NaN v takes neither comparison: a = 0 and the model step.
+ *   has_plan[i] = ok; plan_x, plan_u = the solution as the agent shares it (utils.py:339-352) with NaN -> 0 and +-inf -> the
+ *   largest finite value (torch.nan_to_num); the solver answers status 1 with NaN rows, so such an agent's plan is zeros
+ *   u_ws = plan_u shifted by one step, the last column repeated (utils.py:354-363 augment_prev_sol): the next solve's warm start
+ *   flags_out[i] = flags_in[i] | (ok ? IGT_FLAG_WARM : 0);   infeasible[i] += !ok
+ *   the log (the reference driver's cl_traj [E,7M,T+1] and u_cl [E,2M,T] seen agent-major -- the same bytes): with t = *step in
+ *   0 .. T_log - 1, u_log[i,:,t] = the new u_prev and x_log[i,:,t+1] = the new x; any other t writes nothing.
+ * T is the precision of the solve that produced status / x_sol / u_sol; the state, kparams and the log are double in both.
+ *   x [n,7] in/out   u_prev [n,2] in/out   kparams [n,3]   status [n]   x_sol [n,7,N+1]   u_sol [n,2,N]
+ *   has_plan [n], plan_x [n,7,N+1], plan_u [n,2,N] out;  u_ws [n,2,N] out, may be NULL;  flags_in / flags_out [n], both or
+ *   neither NULL;  infeasible [n] in/out, may be NULL;  x_log [n,7,T_log+1] / u_log [n,2,T_log], both or neither NULL;
+ *   step: one int64 where the other buffers live, read only when logging.
+ * No output may alias x_sol / u_sol; x and u_prev are updated in place.
+ * IGT_MEM_DEVICE: one kernel enqueued on `stream`; no workspace, no allocation, no host synchronisation, nothing kept in the
+ * handle (capturable; a replayed graph reads *step at replay time).  IGT_MEM_HOST: staged like every other entry; the counter
+ * and the two log columns are then written by the host from the staged results, the logs are not copied.
+ * IGT_E_INVALID for a null handle, n < 0, a bad mem, one buffer of a both-or-neither pair without the other, a log without
+ * step, and -- n > 0 -- a null required buffer; n = 0 is a no-op.  (Added without a change of IGT_VERSION; callers probe the
+ * symbols.) */
+int igt_loop_advance_f64(igt_handle* h, int32_t n, double* x, double* u_prev, const double* kparams, const int32_t* status,
+                         const double* x_sol, const double* u_sol, double a_brake, int32_t* has_plan, double* plan_x,
+                         double* plan_u, double* u_ws, const uint32_t* flags_in, uint32_t* flags_out, int64_t* infeasible,
+                         double* x_log, double* u_log, const int64_t* step, int32_t T_log, int mem, void* stream);
+int igt_loop_advance_f32(igt_handle* h, int32_t n, double* x, double* u_prev, const double* kparams, const int32_t* status,
+                         const float* x_sol, const float* u_sol, double a_brake, int32_t* has_plan, float* plan_x,
+                         float* plan_u, float* u_ws, const uint32_t* flags_in, uint32_t* flags_out, int64_t* infeasible,
+                         double* x_log, double* u_log, const int64_t* step, int32_t T_log, int mem, void* stream);
+
 /* Workspace (owned by the handle, grown on the first solve of a batch size, never shrunk; growth synchronises the stream and is
  * refused under stream capture with IGT_E_STATE).  Per scenario, C = 256: 48 B of slice partials, 16 B of live-row masks and
  * incumbent keys (float64; float32: 8 B), 128 B of the acceleration rows' travel sums (float64), 768 B of horizon checkpoints of

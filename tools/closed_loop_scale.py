@@ -1,17 +1,43 @@
 #!/usr/bin/env python3
-"""Developer probe (GPU box): device-resident closed loop with E episodes in lock-step (tracking candidates, warm start,
-f64, N = 20, 50 steps), eager and replayed from a stream graph.      python tools/closed_loop_scale.py [episodes ...]"""
-import os, sys, json
+"""Developer probe (GPU box): device-resident closed loop with E episodes in lock-step (tracking candidates, f64, N = 20,
+50 steps), eager and replayed from a stream graph.      python tools/closed_loop_scale.py [episodes ...] [--step torch|fused|both]
+[--runs R]
+--step (default torch, the table of DESIGN.md section 9): what runs behind the solve -- the ~40 tensor operations or the one
+kernel of igt_loop_advance_*; `both` alternates the two, R timed runs a side (default 3) after one warm-up each, and prints
+every run and the median (profiles/loop_advance_time.txt)."""
+import os, sys, json, statistics
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'igt-mpc-int_amd'))
 from igtmpc.evaluate import run_closed_loop
+argv, which, runs = sys.argv[1:], 'torch', 1
+if '--step' in argv:
+    i = argv.index('--step')
+    which = argv[i + 1]
+    del argv[i:i + 2]
+    runs = 3
+if '--runs' in argv:
+    i = argv.index('--runs')
+    runs = int(argv[i + 1])
+    del argv[i:i + 2]
+if which not in ('torch', 'fused', 'both'):
+    sys.exit("--step takes torch, fused or both")
+sides = ('torch', 'fused') if which == 'both' else (which,)
 steps = 50
-for E in ([int(a) for a in sys.argv[1:]] or [16, 256, 2048, 8192]):
+for E in ([int(a) for a in argv] or [16, 256, 2048, 8192]):
     row = {'episodes': E, 'problems_per_step': 2 * E}
     for name, g in (('eager', False), ('graph', True)):
-        run_closed_loop(sc=1, num_samples=E, N=20, T_sim=steps / 10, device_resident=True, graph=g)      # warm-up (first-touch costs)
-        r = run_closed_loop(sc=1, num_samples=E, N=20, T_sim=steps / 10, device_resident=True, graph=g)
-        row[f'{name}_ms_per_step'] = round(r['wall_s'] / steps * 1e3, 3)
-        row[f'{name}_agent_steps_per_s'] = round(2 * E * steps / r['wall_s'])
+        ms = {s: [] for s in sides}
+        for s in sides:                                                                                      # warm-up (first-touch costs)
+            run_closed_loop(sc=1, num_samples=E, N=20, T_sim=steps / 10, device_resident=True, graph=g, step=s)
+        for _ in range(runs):
+            for s in sides:                                                                                  # alternating
+                r = run_closed_loop(sc=1, num_samples=E, N=20, T_sim=steps / 10, device_resident=True, graph=g, step=s)
+                ms[s].append(round(r['wall_s'] / steps * 1e3, 4))
+        for s in sides:
+            key = name if which == 'torch' else f'{name}_{s}'
+            row[f'{key}_ms_per_step'] = round(statistics.median(ms[s]), 3)
+            if runs > 1:
+                row[f'{key}_runs_ms'] = ms[s]
+            row[f'{key}_agent_steps_per_s'] = round(2 * E * steps / (statistics.median(ms[s]) * 1e-3 * steps))
     row['infeasible'] = float(r['infeasible_ratio'].mean().round(3))
     print(json.dumps(row), flush=True)
