@@ -391,10 +391,30 @@ int check_candidates(const igt_handle* h, int32_t B, const void* U) {
     return IGT_OK;
 }
 
+// What igt_solve_batch_box_f64 / igt_rollout_batch_box_f64 refuse ahead of check_batch, and the model the kernels take.  The
+// polish kernels judge their trial plans with the circle, so a handle that polishes is refused; the developer kernels know the
+// circle alone.
+int check_box(const igt_handle* h, int32_t B, double length, double width, double d_box, igt::BoxModel* box) {
+    if (!h) return fail(IGT_E_INVALID, "null handle");
+    if (B < 0) return fail(IGT_E_INVALID, "B < 0");
+    static_assert(IGT_MAX_OBS * IGT_MAX_N <= igt::BOX_TAB_MAX_ENTRIES, "fill_box_table's LDS holds every (obstacle, node)");
+    if (const char* why = igt::box_model(length, width, d_box, box)) return fail(IGT_E_INVALID, why);
+    if (h->p.polish_iters > 0)
+        return fail(IGT_E_INVALID, "box collision model: polish_iters > 0 is not supported (the polish judges its trial plans with the circle)");
+    if (h->value_polish > 0)
+        return fail(IGT_E_INVALID, "box collision model: igt_set_value_polish > 0 is not supported (the polish judges its trial plans "
+                                   "with the circle); igt_set_value_polish(h, 0) for a box solve");
+    if (h->kp.dev & igt::DEV_KERNEL_FLAGS)
+        return fail(IGT_E_INVALID, "box collision model: not available with the developer kernels of IGT_DEV_FLAGS 32 / 1024 / 2048");
+    return IGT_OK;
+}
+
+// box (igt_solve_batch_box_f64, T = double): obs_xy is the poses [B,n_obs,3,N+1] and the search is plan_box64's
 template <typename T>
 int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* kparams, const uint32_t* flags,
                const T* obs_xy, const T* tv_sv, const T* enc, const T* u_ws, T* x_out, T* u_out, T* cost_out,
-               int32_t* argmin_out, int32_t* status_out, int mem, void* stream, const double* U_own = nullptr) {
+               int32_t* argmin_out, int32_t* status_out, int mem, void* stream, const double* U_own = nullptr,
+               const igt::BoxModel* box = nullptr) {
     // U_own (igt_solve_candidates_f64, T = double): the candidates U[B,C,2,N], staged like the other inputs, in place of the
     // handle's table -- the search and emit of plan_candidates64, everything behind the emit as for any table handle
     bool empty;
@@ -420,10 +440,11 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
     }
     const bool value = p.cost_mode == IGT_COST_VALUE_NET;
     const size_t n_x = (size_t)B * 7, n_u = (size_t)B * 2, n_k = (size_t)B * 3;
-    const size_t n_obs = (size_t)B * p.n_obs * 2 * (p.N + 1);
+    const size_t n_obs = (size_t)B * p.n_obs * (box ? 3 : 2) * (p.N + 1);
     const size_t n_xo = (size_t)B * 7 * (p.N + 1), n_uo = (size_t)B * 2 * p.N;
 
     igt::SolveArgs<T> A{};
+    if (box) A.box = *box;
     A.table = h->table_set ? h->d_table : nullptr;
     A.cinf = h->kp.F > 0 ? h->d_cinf : nullptr;
     Staging stg(h, mem, stream, /*pack=*/true);
@@ -449,6 +470,7 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
         A.plan = igt::plan_search32(h->kp, B, value, igt::Search32Env{h->n_cu, waves_per_simd, h->dev_ckpt});
     else
         A.plan = U_own ? igt::plan_candidates64(h->kp, B, value)
+                 : box ? igt::plan_box64(h->kp, B, value)
                        : igt::plan_search64(h->kp, B, value, igt::Search64Env{h->n_cu, waves_per_simd, h->dev_reserve_pool,
                                                                                h->dev_reserve_units, h->dev_traj_max});
     const auto& plan = A.plan;
@@ -560,17 +582,18 @@ int solve_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* 
 template <typename T>
 int rollout_impl(igt_handle* h, int32_t B, const T* x0, const T* u_prev, const T* kparams, const uint32_t* flags,
                  const T* obs_xy, const T* tv_sv, const T* enc, const T* u_ws, T* X_all, T* U_all, T* cost_all,
-                 uint32_t* viol_all, int mem, void* stream, const double* U_own = nullptr) {
-    bool empty;      // U_own (igt_rollout_candidates_f64): as in solve_impl
+                 uint32_t* viol_all, int mem, void* stream, const double* U_own = nullptr, const igt::BoxModel* box = nullptr) {
+    bool empty;      // U_own (igt_rollout_candidates_f64), box (igt_rollout_batch_box_f64): as in solve_impl
     if (int rc = check_batch(h, B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, u_ws, &empty, U_own != nullptr)) return rc;
     if (empty) return IGT_OK;
     if (!cost_all || !viol_all) return fail(IGT_E_INVALID, "null buffer");
     const igt_params& p = h->p;
     const bool value = p.cost_mode == IGT_COST_VALUE_NET;
     const size_t n_x = (size_t)B * 7, n_u = (size_t)B * 2, n_k = (size_t)B * 3;
-    const size_t n_obs = (size_t)B * p.n_obs * 2 * (p.N + 1);
+    const size_t n_obs = (size_t)B * p.n_obs * (box ? 3 : 2) * (p.N + 1);
     const size_t n_X = (size_t)B * p.C * 7 * (p.N + 1), n_U = (size_t)B * p.C * 2 * p.N, n_c = (size_t)B * p.C;
     igt::SolveArgs<T> A{};
+    if (box) A.box = *box;
     A.table = h->table_set ? h->d_table : nullptr;
     A.cinf = h->kp.F > 0 ? h->d_cinf : nullptr;
     T *dX, *dU, *dc;
@@ -1192,6 +1215,25 @@ int igt_rollout_candidates_f64(igt_handle* h, int32_t B, const double* x0, const
     if (int rc = check_candidates(h, B, U)) return rc;
     return rollout_impl<double>(h, B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, nullptr, X_all, U_all, cost_all, viol_all, mem,
                                 stream, U);
+}
+
+int igt_solve_batch_box_f64(igt_handle* h, int32_t B, const double* x0, const double* u_prev, const double* kparams,
+                            const uint32_t* flags, const double* obs_pose, const double* tv_sv, const double* enc,
+                            const double* u_ws, double length, double width, double d_box, double* x_out, double* u_out,
+                            double* cost_out, int32_t* argmin_out, int32_t* status_out, int mem, void* stream) {
+    igt::BoxModel box;
+    if (int rc = check_box(h, B, length, width, d_box, &box)) return rc;
+    return solve_impl<double>(h, B, x0, u_prev, kparams, flags, obs_pose, tv_sv, enc, u_ws, x_out, u_out, cost_out, argmin_out,
+                              status_out, mem, stream, nullptr, &box);
+}
+int igt_rollout_batch_box_f64(igt_handle* h, int32_t B, const double* x0, const double* u_prev, const double* kparams,
+                              const uint32_t* flags, const double* obs_pose, const double* tv_sv, const double* enc,
+                              const double* u_ws, double length, double width, double d_box, double* X_all, double* U_all,
+                              double* cost_all, uint32_t* viol_all, int mem, void* stream) {
+    igt::BoxModel box;
+    if (int rc = check_box(h, B, length, width, d_box, &box)) return rc;
+    return rollout_impl<double>(h, B, x0, u_prev, kparams, flags, obs_pose, tv_sv, enc, u_ws, X_all, U_all, cost_all, viol_all, mem,
+                                stream, nullptr, &box);
 }
 
 int igt_frenet_step_f32(igt_handle* h, int32_t n, const float* x, const float* u, const float* kparams, float* x_next,

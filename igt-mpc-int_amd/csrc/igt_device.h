@@ -427,6 +427,17 @@ struct Scenario {           // wave-uniform inputs of one scenario
     const T* ws;            // [2, N] warm start of this scenario (base sequence of the ramp-hold targets), or null
 };
 
+// ---- the rectangle (OBCA) collision model of the _box entries (include/igtmpc.h; igt_fast64.h box_gap) ----
+// Ego and obstacles are rectangles of one size.  What a kernel takes of the model, made once on the host (igt_launch.h box_model):
+// the half extents, the distance to keep d_box + 1e-6 (mpc.py:221), and the gate: centres at least dsafe + 2 |h| apart are clear.
+struct BoxModel {
+    double h0, h1, dsafe, gate2;      // half length, half width, d_box + 1e-6, (dsafe + 2 |h|)^2; h0 == 0: no box model
+};
+// fill_box_table's table of one scenario: the model, then (q_x, q_y, cos phi, sin phi) of obstacle o at node k = 1 .. N at
+// entry o N + k - 1.  The largest: IGT_MAX_OBS x IGT_MAX_N entries, 8 KB.
+constexpr int BOX_TAB_HEADER = 4, BOX_TAB_FIELDS = 4, BOX_TAB_MAX_ENTRIES = 4 * 64;
+constexpr int BOX_TAB_DOUBLES = BOX_TAB_HEADER + BOX_TAB_MAX_ENTRIES * BOX_TAB_FIELDS;
+
 // Whether no candidate of the scenario that holds the speed box can come within d_min of any forecast position (wave-uniform;
 // the lanes share the horizon).  A control step moves the vehicle by at most dt max(|v_k|, |v_k+1|) (the RK4 stage speeds lie
 // between the two), speed-feasible candidates have |v_k| <= max(|v_min|, |v_max|) + tol for k < N, and |v_N| exceeds that by at

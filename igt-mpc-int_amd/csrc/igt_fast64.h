@@ -434,6 +434,101 @@ constexpr int CK_FIELDS = 8, CK_PARTS = 4;                      // record: s ey 
 constexpr int ck_fields(int cand) { return cand == CAND_TRACK ? 8 : 5; }                   // fields the family writes of a record
 __host__ __device__ inline int ckpt_step(int N, int i) { return (i * N) / CK_PARTS; }      // first step of piece i
 
+// ---- the rectangle (OBCA) collision verdict (ROLL_BOX; igt_solve_batch_box_f64 / igt_rollout_batch_box_f64) ----
+// The reference's 'obca' mode (mpc.py:211-221) certifies with dual variables that the ego rectangle (centre p, heading psi) and
+// an obstacle rectangle (centre q, heading phi, same half extents h) are at least d_box + 1e-6 apart.  A shooting solver judges
+// the distance itself: signed gap = rectangle-to-rectangle distance, or minus the penetration depth when they overlap, and
+// g = d_box + 1e-6 - gap is violated where g > tol (include/igtmpc.h has the definition, tests/box_collision_restated.py
+// restates it).  Centres at least dsafe + 2 |h| apart are clear -- the gate, the only thing most pairs pay for.
+//
+// (q, cos phi, sin phi) of an (obstacle, node) is the same for all 64 lanes of a unit, and a libm-grade sincos of phi per pair,
+// lane and step would cost more than the control step: the unit's wave lays them out once in LDS, lanes on different (o, k),
+// and the step loop reads them by same-address (broadcast) ds_reads -- no bank conflict, no register held across the loop, no
+// kernel argument more (the search kernels spill scalar registers as it is).  Chosen over a prelude kernel with scalar loads:
+// the box solve stays one launch per pass without workspace beyond the partials, and the table costs a unit at most four
+// sincos per lane against N control steps.
+// A non-finite coordinate or heading (|phi| beyond 1e6 counts: sincos_reduced's domain) makes the node no constraint: the entry
+// is moved out of every gate.
+constexpr double BOX_NOWHERE = 1.0e150;      // its square is finite and beyond any gate
+__device__ __forceinline__ void fill_box_table(const KP& P, const BoxModel& M, const double* __restrict__ pose, int lane,
+                                               double* __restrict__ tab) {
+    if (lane == 0) { tab[0] = M.h0; tab[1] = M.h1; tab[2] = M.dsafe; tab[3] = M.gate2; }
+    for (int e = lane; e < P.n_obs * P.N; e += 64) {                  // <= BOX_TAB_MAX_ENTRIES (igt_create: n_obs, N)
+        const int o = e / P.N, k = e - o * P.N + 1;
+        const double* r = pose + (size_t)o * 3 * (P.N + 1) + k;      // pose [n_obs, 3, N+1]: x, y, heading
+        double qx = r[0], qy = r[P.N + 1];
+        const double phi = r[2 * (P.N + 1)];
+        double sq = 0.0, cq = 1.0;
+        if (fabs(qx) < 1.79e308 && fabs(qy) < 1.79e308 && fabs(phi) <= 1.0e6) sincos_reduced(phi, sq, cq);
+        else { qx = BOX_NOWHERE; qy = 0.0; }
+        double* t = tab + BOX_TAB_HEADER + e * BOX_TAB_FIELDS;
+        t[0] = qx; t[1] = qy; t[2] = cq; t[3] = sq;
+    }
+    __syncthreads();
+}
+// obstacles_out_of_reach (igt_device.h) for the rectangles: dsafe + 2 |h| in place of d_min, the poses' layout
+__device__ __forceinline__ bool box_out_of_reach(const KP& P, const Scenario<double>& S, const BoxModel& M,
+                                                 const double* __restrict__ pose, int lane) {
+    const double reach = (fmax(fabs(P.v_min), fabs(P.v_max)) + fmax(fabs(P.a_min), fabs(P.a_max)) * P.dt) * (P.N * P.dt) + 1.0;
+    const double lim = sqrt(M.gate2) + reach, lim2 = lim * lim;
+    bool near = false;
+    for (int e = lane; e < P.n_obs * P.N; e += 64) {
+        const int o = e / P.N, k = e - o * P.N + 1;
+        const double dx = S.x0[0] - pose[(o * 3 + 0) * (P.N + 1) + k], dy = S.x0[1] - pose[(o * 3 + 1) * (P.N + 1) + k];
+        near |= !(dx * dx + dy * dy > lim2);                      // NaN counts as near: the table sorts it out
+    }
+    return !__any(near);
+}
+// signed gap of two rectangles of half extents (h0, h1): (dx, dy) = q - p, (sp, cp) = (sin, cos) psi, (sq, cq) = (sin, cos) phi
+__device__ __forceinline__ double box_gap(double h0, double h1, double dx, double dy, double sp, double cp, double sq, double cq) {
+    // t = R(psi)^T (q - p): the obstacle's centre in the ego's frame; u = R(phi)^T (p - q): the roles swapped; theta = phi - psi
+    const double t0 = fma(cp, dx, sp * dy), t1 = fma(cp, dy, -(sp * dx));
+    const double u0 = -fma(cq, dx, sq * dy), u1 = -fma(cq, dy, -(sq * dx));
+    const double ct = fma(cq, cp, sq * sp), st = fma(sq, cp, -(cq * sp));
+    const double c = fabs(ct), s = fabs(st);
+    // separating axes: the four depths, the extents h0 + h0 c + h1 s and h1 + h0 s + h1 c being the same in either frame
+    const double e0 = fma(h1, s, fma(h0, c, h0)), e1 = fma(h1, c, fma(h0, s, h1));
+    const double depth = fmin(fmin(e0 - fabs(t0), e1 - fabs(t1)), fmin(e0 - fabs(u0), e1 - fabs(u1)));
+    if (depth > 0.0) return -depth;                               // overlap: minus the penetration depth
+    // apart: the closest pair of points has a vertex of one rectangle at one end -- the eight vertices, each in the other's
+    // frame, where its distance to the rectangle is |max(|v| - h, 0)|
+    const double ax = h0 * ct, ay = h0 * st, bx = h1 * st, by = h1 * ct;
+    double m = (double)INFINITY;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double a = (i & 1) ? -1.0 : 1.0, b = (i & 2) ? -1.0 : 1.0;
+        const double vx = fma(-b, bx, fma(a, ax, t0)), vy = fma(b, by, fma(a, ay, t1));       // t + R(theta) (a h0, b h1)
+        const double wx = fma(b, bx, fma(a, ax, u0)), wy = fma(b, by, fma(-a, ay, u1));       // u + R(-theta) (a h0, b h1)
+        const double ex = fmax(fabs(vx) - h0, 0.0), ey = fmax(fabs(vy) - h1, 0.0);
+        const double fx = fmax(fabs(wx) - h0, 0.0), fy = fmax(fabs(wy) - h1, 0.0);
+        m = fmin(m, fmin(fma(ex, ex, ey * ey), fma(fx, fx, fy * fy)));
+    }
+    return sqrt(m);
+}
+// The verdict of state k >= 1 against every obstacle.  tab: fill_box_table's.  (s2, c2) = (sin, cos)(psi_k + beta_k-1) as the
+// roll-out carries it when state k is judged, (sbp, cbp) = (sin, cos)(beta_k-1): turned back by beta_k-1 they are the ego's
+// (sin, cos) psi_k -- no transcendental.  The gate comes first, under a wave vote: a wave with no lane inside pays the
+// difference, two products and a compare per pair.  A lane outside the gate folds nothing whatever its neighbours do, so the
+// vote changes no answer; a NaN position is inside no gate (the non-finite verdict of horizon_end reports it).
+template <bool LEAN>
+__device__ __forceinline__ void box_collision(const KP& P, const double* __restrict__ tab, int k, double x, double y, double s2,
+                                              double c2, double sbp, double cbp, double& gmax, unsigned& viol) {
+    const double gate2 = tab[3];
+    for (int o = 0; o < P.n_obs; ++o) {
+        const double* e = tab + BOX_TAB_HEADER + (o * P.N + (k - 1)) * BOX_TAB_FIELDS;
+        const double dx = e[0] - x, dy = e[1] - y;
+        const bool in = fma(dx, dx, dy * dy) < gate2;
+        if (__any(in)) {
+            const double sp = fma(s2, cbp, -(c2 * sbp)), cp = fma(c2, cbp, s2 * sbp);
+            const double g = tab[2] - box_gap(tab[0], tab[1], dx, dy, sp, cp, e[3], e[2]);
+            if (in) {
+                if (LEAN) gmax = fmax(gmax, g);
+                else if (g > P.tol) viol |= VIOL_COLLISION;
+            }
+        }
+    }
+}
+
 // What one lane carries from control step to control step (rollout_one, rollout_pool): the state, the candidate's control
 // recurrence, the running cost and verdicts, the carried (sin, cos) pairs, the checkpoint cursor and the incumbent bound.
 template <class FP>
@@ -457,6 +552,7 @@ struct Roll {
     static constexpr bool STAB = (O & ROLL_STEER_TABLE) != 0, XY = !(O & ROLL_NO_XY), STEPTAB = (O & ROLL_STEP_TABLE) != 0;
     static constexpr bool LEAVE_CKPT = (O & ROLL_LEAVE_CKPT) != 0, RESUME = (O & ROLL_RESUME) != 0;
     static constexpr bool EY_FOLDED = (O & ROLL_EY_FOLDED) != 0, WHOLE_D = !(O & ROLL_PART_D);
+    static constexpr bool BOX = (O & ROLL_BOX) != 0;            // the rectangle verdict (box_collision) in place of the circle's
     static constexpr bool LEAN = roll_lean(O), BOUND = roll_bound(CAND, O);
     static constexpr bool KEEP_PSI = Sink::kKeepsStates;        // psi feeds nothing back (search: dead code)
     static constexpr int CKF = ck_fields(CAND);
@@ -612,6 +708,9 @@ __device__ __forceinline__ void step_tail(const KP& P, const Scenario<double>& S
                                           int stab_stride = 0) {
     typedef Roll<CAND, O, Sink> R;
     constexpr bool BOOK = R::BOOK, LEAN = R::LEAN, XY = R::XY, STEPTAB = R::STEPTAB;
+    if constexpr (R::BOX) {                                                      // rectangles, mpc.py:211-221
+        if (BOOK && XY && k >= 1) box_collision<LEAN>(P, S.obs, k, L.x, L.y, L.w.s2, L.w.c2, L.sb_prev, L.cb_prev, L.gmax, L.viol);
+    } else
     if (BOOK && XY && k >= 1) {                                                  // collision, mpc.py:223-226
         for (int o = 0; o < P.n_obs; ++o) {
             const double dx = L.x - S.obs[(o * 2 + 0) * (P.N + 1) + k], dy = L.y - S.obs[(o * 2 + 1) * (P.N + 1) + k];
@@ -661,6 +760,9 @@ __device__ __forceinline__ void horizon_end(const KP& P, const Scenario<double>&
     L.J = L.J + L.ey * L.ey;
     if (LEAN) L.gmax = fmax(L.gmax, fabs(L.ey) - P.ey_lim);
     else if (fabs(L.ey) - P.ey_lim > P.tol) L.viol |= VIOL_EY;
+    if constexpr ((O & ROLL_BOX) != 0) {               // state N: the pair holds psi_N + beta_N-1
+        if (XY) box_collision<LEAN>(P, S.obs, P.N, L.x, L.y, L.w.s2, L.w.c2, L.sb_prev, L.cb_prev, L.gmax, L.viol);
+    } else
     for (int o = 0; XY && o < P.n_obs; ++o) {
         const double dx = L.x - S.obs[(o * 2 + 0) * (P.N + 1) + P.N], dy = L.y - S.obs[(o * 2 + 1) * (P.N + 1) + P.N];
         const double g = P.dmin2 - (dx * dx + dy * dy);

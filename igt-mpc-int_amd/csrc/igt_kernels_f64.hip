@@ -300,7 +300,9 @@ __device__ __forceinline__ bool rank_major_items(const KP& P, int cand, bool val
 
 // One work unit = one (scenario, 64-candidate slice), rolled by one wave; leaves the slice's best (J, c), or -- value-net
 // cost -- every candidate's record for value_kernel<double> (mpc.py:369).
-template <int CAND, bool HI, bool VALUE, int NRK = 0, bool CAPTURE = false>
+// BOX (search_box_f64_kernel): `obs` is the poses [B,n_obs,3,N+1] and the collision verdict is the rectangle one of *box
+// (igt_fast64.h ROLL_BOX) -- the unit lays out its scenario's table in LDS and rolls with it as S.obs.
+template <int CAND, bool HI, bool VALUE, int NRK = 0, bool CAPTURE = false, bool BOX = false>
 __device__ __forceinline__ void search_unit64(const KP& P, int W, int b, int p, const double* __restrict__ x0,
                                               const double* __restrict__ u_prev, const double* __restrict__ kparams,
                                               const uint32_t* __restrict__ flags, const double* __restrict__ obs,
@@ -312,7 +314,9 @@ __device__ __forceinline__ void search_unit64(const KP& P, int W, int b, int p, 
                                               int32_t* __restrict__ rec_b, int2* __restrict__ unit_seg,
                                               const unsigned long long* __restrict__ row_mask = nullptr,
                                               double* __restrict__ traj = nullptr, unsigned long long* inc_all = nullptr,
-                                              double* __restrict__ ck_all = nullptr, const double* __restrict__ rem_all = nullptr) {
+                                              double* __restrict__ ck_all = nullptr, const double* __restrict__ rem_all = nullptr,
+                                              const BoxModel* box = nullptr) {
+    static_assert(!(BOX && CAPTURE), "the rectangle verdict: the plain units only");
     const int lane = threadIdx.x & 63;
     unsigned long long* inc = inc_all ? inc_all + b : nullptr;
     const double* rem_rows = (inc_all && rem_all) ? rem_all + (size_t)b * P.G : nullptr;
@@ -352,11 +356,19 @@ __device__ __forceinline__ void search_unit64(const KP& P, int W, int b, int p, 
     // LDS once per unit instead of being recomputed by each of their 64 W/G lanes at every step (igt_fast64.h)
     // 70 % of the benchmark's scenarios: the other vehicle is out of reach over the whole horizon (or filter_preds moved it
     // away), so the unit rolls without the Cartesian rows -- a sixth of the control step's instructions
-    const bool far = !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
+    bool far_box = false;
+    if constexpr (BOX) {      // the poses of the scenario: out of reach by the rectangles' gate, or the table (nothing leaves checkpoints)
+        __shared__ double boxtab[BOX_TAB_DOUBLES];
+        const double* pose = obs + (size_t)b * P.n_obs * 3 * (P.N + 1);
+        far_box = !(P.dev & DEV_NO_FAR) && f64::box_out_of_reach(P, S, *box, pose, lane);
+        if (!far_box) f64::fill_box_table(P, *box, pose, lane, boxtab);
+        S.obs = boxtab;
+    }
+    const bool far = BOX ? far_box : !(P.dev & DEV_NO_FAR) && obstacles_out_of_reach<double>(P, S, lane);
     // horizon checkpoints of every lane in LDS (igt_fast64.h ROLL_LEAVE_CKPT); the unit winner's go to HBM below
-    constexpr unsigned UNIT = ROLL_SEARCH | (VALUE ? 0u : ROLL_LEAVE_CKPT);
+    constexpr unsigned UNIT = ROLL_SEARCH | ((VALUE || BOX) ? 0u : ROLL_LEAVE_CKPT) | (BOX ? ROLL_BOX : 0u);
     constexpr int CKF = f64::ck_fields(CAND);
-    __shared__ double ckl[VALUE ? 1 : (f64::CK_PARTS - 1) * CKF * 64];
+    __shared__ double ckl[(VALUE || BOX) ? 1 : (f64::CK_PARTS - 1) * CKF * 64];
     ck_lds = (!VALUE && ck_all) ? ckl + lane : nullptr;
     if (L.kind >= 2 && steer_table_fits(P, W, CAND)) {
         __shared__ double stab[f64::STAB_MAX_ENTRIES * 3];
@@ -604,6 +616,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     if (b >= B) return;
     search_unit64<CAND_TABLE, HI, VALUE, NRK>(P, W, b, p, x0, u_prev, kparams, flags, obs, table + (size_t)b * cand_table_doubles(P.C, P.N),
                                               cinf, cpar, part_J, part_c, rec_sN, rec_vN, rec_J, rec_viol, rec_count, rec_b, unit_seg);
+}
+// ---- the rectangle (OBCA) collision model (igt_solve_batch_box_f64; igt_launch.h plan_box64) ----
+// search_unit64 with the rectangle verdict, one wave per (scenario, 64-candidate unit) on a plain grid as the direct kernel
+// above: no queues, no pool, no prelude, every acceleration row, the partials (or the value network's records) as the only
+// workspace.  The generic sub-step build alone (NRK = 0: any n_rk4, the same bits as the unrolled one): 16 kernels, not 24.
+template <int CAND, bool HI, bool VALUE>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_box_f64_kernel(IGT_SEARCH64_ARGS, BoxModel box) {
+    const int b = (int)(blockIdx.x / (unsigned)W), p = (int)(blockIdx.x % (unsigned)W);
+    if (b >= B) return;
+    search_unit64<CAND, HI, VALUE, 0, false, true>(P, W, b, p, x0, u_prev, kparams, flags, obs, table, cinf, cpar, part_J, part_c, rec_sN,
+                                                   rec_vN, rec_J, rec_viol, rec_count, rec_b, unit_seg, nullptr, nullptr, nullptr, nullptr,
+                                                   nullptr, &box);
 }
 // one 64-thread block per scenario: final arg-min over the W partials, then the winner's trajectory copied out of the unit
 // that rolled it.  Which lane that was is asked of unit_candidate itself, so the two cannot drift apart.
@@ -1321,6 +1345,46 @@ __global__ __launch_bounds__(256) void rollout_all_f64_kernel(KP P, int B, const
     }
 }
 
+// igt_rollout_batch_box_f64: rollout_all_f64_kernel with the rectangle verdict.  One wave per scenario (its table of poses is
+// the wave's, in LDS), `obs` the poses [B,n_obs,3,N+1].
+template <int CAND, bool HI>
+__global__ __launch_bounds__(64) void rollout_all_box_f64_kernel(KP P, int B, const double* __restrict__ x0,
+                                                                 const double* __restrict__ u_prev,
+                                                                 const double* __restrict__ kparams,
+                                                                 const uint32_t* __restrict__ flags,
+                                                                 const double* __restrict__ obs,
+                                                                 const double* __restrict__ table,
+                                                                 const double* __restrict__ cinf, Centre<double> cpar,
+                                                                 BoxModel box, double* __restrict__ X_all,
+                                                                 double* __restrict__ U_all, double* __restrict__ cost_all,
+                                                                 uint32_t* __restrict__ viol_all, double* __restrict__ rec_sN,
+                                                                 double* __restrict__ rec_vN, double* __restrict__ rec_J,
+                                                                 uint32_t* __restrict__ rec_viol) {
+    __shared__ double boxtab[BOX_TAB_DOUBLES];
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const int lane = threadIdx.x;
+    Scenario<double> S;
+    load_scenario<double>(S, P, b, x0, u_prev, kparams, flags, obs, cpar);
+    f64::fill_box_table(P, box, obs + (size_t)b * P.n_obs * 3 * (P.N + 1), lane, boxtab);
+    S.obs = boxtab;
+    for (int c = lane; c < P.C; c += 64) {          // C is a multiple of 64: the wave stays whole (votes inside)
+        const size_t bc = (size_t)b * P.C + c;
+        StoreSink<double> sink{X_all ? X_all + bc * 7 * (P.N + 1) : nullptr, U_all ? U_all + bc * 2 * P.N : nullptr, P.N};
+        double J, sN, vN;
+        unsigned viol;
+        f64::rollout_one<CAND, HI, ROLL_ALL | ROLL_BOX>(P, S, c, table, cinf, sink, J, viol, sN, vN);
+        if (rec_J) {   // value-net cost: value_kernel adds the terminal term and fills cost_all / viol_all
+            rec_sN[bc] = sN; rec_vN[bc] = vN; rec_J[bc] = J; rec_viol[bc] = viol;
+            continue;
+        }
+        const double Jq = J - (sN - S.x0[2]);
+        if (!finite_d(Jq)) viol |= VIOL_NONFINITE;
+        cost_all[bc] = Jq;
+        viol_all[bc] = viol;
+    }
+}
+
 #if IGT_DEV_KERNELS
 // ---------------------------------------------------------------------------------------
 // The LITERAL mapping of BASELINE.json's north_star, kept as a measurement variant (IGT_DEV_FLAGS = 2048):
@@ -1477,6 +1541,10 @@ static hipError_t launch_search64(const KP& P, int B, const SolveArgs<double>& A
     const auto search = [&](auto kernel, auto... more) {
         return launch_search_kernel(kernel, plan.grid, Pr, B, W, plan.queues, order, plan.order_stride, A, st, more...);
     };
+    if (plan.box) {      // the rectangle collision model (plan_box64): A.obs is the poses, A.box the model
+        if (plan.search_kernel != SearchKernel64::UNITS || plan.queues != 0 || !(A.box.h0 > 0.0)) return hipErrorInvalidValue;
+        return search(search_box_f64_kernel<CAND, HI, VALUE>, A.box);
+    }
     switch (plan.search_kernel) {
     case SearchKernel64::CAPTURE_STATIC:
     case SearchKernel64::CAPTURE_QUEUES:
@@ -1681,6 +1749,15 @@ hipError_t launch_rollout_all<double>(const KP& P, int B, const SolveArgs<double
         return hipGetLastError();
     }
 #endif
+    if (A.box.h0 > 0.0) {           // the rectangle collision model: A.obs is the poses [B,n_obs,3,N+1]
+        if (A.table_stride != 0) return hipErrorInvalidValue;
+        return with_family(P.cand_mode, P.hi_order, [&](auto cand, auto hi) {
+            hipLaunchKernelGGL((rollout_all_box_f64_kernel<cand(), hi()>), dim3(B), dim3(64), 0, st, P, B, A.x0, A.u_prev, A.kparams, A.flags,
+                               A.obs, A.table, A.cinf, A.centre(), A.box, X_all, U_all, cost_all, viol_all, A.rec_sN, A.rec_vN, A.rec_J,
+                               A.rec_viol);
+            return hipGetLastError();
+        });
+    }
     if (A.table_stride != 0) {      // per-scenario candidate sets: A.table is U[B,C,2,N]
         if (P.cand_mode != CAND_TABLE || A.table_stride != cand_table_doubles(P.C, P.N)) return hipErrorInvalidValue;
         return with_bool(P.hi_order != 0, [&](auto hi) {

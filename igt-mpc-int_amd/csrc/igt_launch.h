@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include <type_traits>
 #include "igt_device.h"
 #include "igt_value_net.h"
@@ -122,6 +123,7 @@ struct Search64Plan {
     bool memset_counters;             // the host zeroes the unit counters: queues that no builder zeroes
     bool reset_rec_count;             // value-network cost: the host zeroes rec_count before every pass (the compact list's lengths)
     int emit_priority;                // ONE_PIECE: the wave priority emit_f64_kernel sets at its top (0: none)
+    bool box = false;                 // plan_box64 alone: the UNITS are search_box_f64_kernel's -- the rectangle verdict, a plain grid
     bool sorts_queues() const { return rows_build_queues || separate_queue_builder; }
     // what only a float solve has (Search32Plan): solve_impl reads either plan under one set of names
     static constexpr size_t ckpt_doubles = 0;
@@ -283,6 +285,38 @@ inline Search64Plan plan_candidates64(const KP& P, int B, bool value) {
     return p;      // queues 0, no prelude, no launch-time bits, no trajectories, records or queue order, no counter memset, priority 0
 }
 
+// ---- the plan of a solve under the rectangle (OBCA) collision model (igt_solve_batch_box_f64) ----
+// Any candidate family, either cost.  search_box_f64_kernel on a plain grid of one wave per (scenario, 64-candidate unit): no
+// queues, no counters, no prelude (every acceleration row is rolled), no launch-time bits.  Nothing keeps trajectories or
+// checkpoint records, so emit rolls the winner in one piece at every batch size (at priority 0; it judges nothing, so it is
+// the circle entries' kernel) and the workspace is the partials alone.
+inline Search64Plan plan_box64(const KP& P, int B, bool value) {
+    Search64Plan p{};
+    p.W = p.partials = P.C / 64;
+    p.grid = (size_t)B * p.W;
+    p.order_stride = ((B + 7) / 8) * p.W;
+    p.search_kernel = SearchKernel64::UNITS;      // 64-candidate units ...
+    p.box = true;                                 // ... of search_box_f64_kernel, one wave each: queues 0
+    p.emit_kernel = EmitKernel64::ONE_PIECE;
+    p.reset_rec_count = value;
+    return p;
+}
+// The model a kernel takes (igt_device.h BoxModel) from the entry's three scalars -> nullptr, or what the entries refuse the
+// values with (non-finite or non-positive extents; d_box non-finite or negative), nothing written: the one place that judges
+// them.  1e-6: the reference's margin on the distance (mpc.py:221).
+inline const char* box_model(double length, double width, double d_box, BoxModel* out) {
+    const auto finite = [](double v) { return v - v == 0.0; };
+    if (!finite(length) || !(length > 0.0)) return "box collision model: length must be finite and positive";
+    if (!finite(width) || !(width > 0.0)) return "box collision model: width must be finite and positive";
+    if (!finite(d_box) || !(d_box >= 0.0)) return "box collision model: d_box must be finite and not below 0";
+    BoxModel m;
+    m.h0 = 0.5 * length; m.h1 = 0.5 * width; m.dsafe = d_box + 1e-6;
+    const double rho = std::sqrt(m.h0 * m.h0 + m.h1 * m.h1), gate = m.dsafe + 2.0 * rho;
+    m.gate2 = gate * gate;
+    *out = m;
+    return nullptr;
+}
+
 // ---- the plan of one float solve: what it runs, decided once on the host ----
 // plan_search32 states the search kernel and its grid, the queue builder, the tracking family's incumbents, the checkpoints and
 // the emit kernel, the workspace and the memsets.  igt_api.hip solve_impl carves its workspace from the plan; launch_search_fast /
@@ -406,6 +440,7 @@ struct SolveArgs {   // all device pointers
     const double* cinf;   // [F,3] or null
     const double* cpar;    // [B,4] ramp-hold centre offset / span of a refinement pass, or null (first pass)
     const T* u_ws;         // [B,2,N] warm start (previous solution shifted by one step), or null; used where flags & 2
+    BoxModel box{};        // h0 > 0 (the _box entries, double): obs is the poses [B,n_obs,3,N+1] and collisions are the rectangles'
     Centre<T> centre() const { return Centre<T>{cpar, u_ws}; }
     T* x_out;
     T* u_out;

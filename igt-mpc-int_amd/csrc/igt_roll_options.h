@@ -17,6 +17,7 @@ enum RollOption : unsigned {
     ROLL_STEP_TABLE = 1u << 7,   // pool: the column is fill_pool_table's -- sblr and the rotation by beta_k - beta_k-1 come from it
     ROLL_EY_FOLDED = 1u << 8,    // pool: |ey_k| - ey_lim is in gmax already when step_head books state k
     ROLL_PART_D = 1u << 9,       // pool: a whole step taken as K == 0 leaves d0, d1 alone (Fast64::substeps WHOLE_D = false)
+    ROLL_BOX = 1u << 10,         // the collision verdict is the rectangle (OBCA) one: S.obs is fill_box_table's table, not [n_obs,2,N+1]
 };
 // The roles.  A call adds what its site decides on top: ROLL_STEER_TABLE, ROLL_NO_XY, ROLL_LEAVE_CKPT / ROLL_STEP_TABLE.
 constexpr unsigned ROLL_SEARCH = ROLL_BOOK | ROLL_UNIFORM | ROLL_EARLY_EXIT;                    // search unit, capture
@@ -36,7 +37,8 @@ constexpr bool roll_bound(int cand, unsigned o) {
 }
 // what no build uses and the code does not support
 constexpr bool roll_supported(unsigned o) {
-    return !((o & ROLL_RESUME) && (o & ROLL_LEAVE_CKPT)) && !((o & ROLL_STEP_TABLE) && !(o & ROLL_STEER_TABLE));
+    return !((o & ROLL_RESUME) && (o & ROLL_LEAVE_CKPT)) && !((o & ROLL_STEP_TABLE) && !(o & ROLL_STEER_TABLE)) &&
+           !((o & ROLL_BOX) && (o & ROLL_STEP_TABLE));      // the rectangle verdict reads (sin, cos)(beta_k-1), which the pool's lanes do not carry
 }
 
 }  // namespace igt

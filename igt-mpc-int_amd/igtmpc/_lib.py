@@ -83,6 +83,9 @@ SYMBOLS = {
     'igt_cost_gradient_vn_f64': (_i, [_vp, _i32] + [_vp] * 8 + [_i, _vp]),
     'igt_solve_candidates_f64': (_i, _SOLVE_WS),       # U[B,C,2,N] where the _ws entries take u_ws
     'igt_rollout_candidates_f64': (_i, _ROLL_WS),
+    # obs_pose[B,n_obs,3,N+1] where the _ws entries take obs_xy; length, width, d_box behind u_ws
+    'igt_solve_batch_box_f64': (_i, [_vp, _i32] + [_vp] * 8 + [C.c_double] * 3 + [_vp] * 5 + [_i, _vp]),
+    'igt_rollout_batch_box_f64': (_i, [_vp, _i32] + [_vp] * 8 + [C.c_double] * 3 + [_vp] * 4 + [_i, _vp]),
     'igt_loop_advance_f64': (_i, _LOOP),
     'igt_loop_advance_f32': (_i, _LOOP),
     'igt_set_profiling': (_i, [_vp, _i]),
@@ -93,7 +96,7 @@ SYMBOLS = {
 # added without a change of IGT_VERSION: a library of the same ABI from before them (IGT_LIB_PATH, tools/ab_lib.sh) lacks them
 OPTIONAL_SYMBOLS = ('igt_set_polish_gradient', 'igt_cost_gradient_f64', 'igt_terminal_value_f64', 'igt_cost_gradient_vn_f64',
                     'igt_set_polish_step', 'igt_set_value_polish', 'igt_solve_candidates_f64', 'igt_rollout_candidates_f64',
-                    'igt_loop_advance_f64', 'igt_loop_advance_f32')
+                    'igt_loop_advance_f64', 'igt_loop_advance_f32', 'igt_solve_batch_box_f64', 'igt_rollout_batch_box_f64')
 
 _libs = {}
 # IGT_DEV_FLAGS bits (csrc/igt_device.h DevFlag; the launch-time bits there are the library's own and not listed here)

@@ -26,6 +26,7 @@ import numpy as np
 from . import routes as R
 from .cinf import cinf_halfplanes
 from ._lib import IGT_FLAG_WARM
+from .predictor import ConstantAccelerationModel
 from .solver import BatchSolver, check_value_polish, check_value_polish_driver
 from .value_nets import shipped_value_net
 
@@ -70,7 +71,7 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
                     eval_mode='mpc', value_net=None, device_resident=False, warm_start=None, init=None,
                     terminal_set=True, feas_tol=None, limits=None, graph=False, a_min_policy=None, constant_speed=False,
                     v0=0.0, polish_iters=0, num_agents=2, polish_grad='fd', polish_step='gradient', value_polish_iters=0,
-                    value_polish_driver='host', step='torch'):
+                    value_polish_driver='host', step='torch', ca_type='circle', log_plans=False):
     """eval_mode 'mpc' (evaluate.py:370-639) or 'gt_mpc' (123-369: terminal value network in the cost;
     value_net = dict(layers=[(W,b),...][, Wn, mu_f, sigma_t, mu_t]), default: the network the reference ships for
     scenario sc -- its normalisation statistics are not shipped, identity unless given).  device_resident=True keeps every per-step array in HBM (torch tensors;
@@ -103,7 +104,24 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     num_agents = M in 2..4 (evaluate.py:46; four approach lanes): every step solves E M problems with n_obs = M - 1 -- each
     agent against the forecast / shared plan of every other one (Jacobi, evaluate.py:469-558).  Scenario `sc`'s route tuples for
     M > 2: routes.scene_routes; init = (x[E,M,7], route tuples of length M).  eval_mode 'mpc' only beyond two (the value
-    network's features are those of a two-vehicle scene, mpc.py:326-338)."""
+    network's features are those of a two-vehicle scene, mpc.py:326-338).
+    ca_type 'circle' (default; mpc.yaml:16) or 'obca' (mpc.py:42-43, 211-221): every vehicle a 4.47 x 2.0 m rectangle, d_min = 0,
+    solved through BatchSolver.solve_box.  The host loop only: device_resident=True or graph=True with 'obca' raises ValueError
+    (there is no device forecast of headings).  The obstacles' x, y stay the device forecast's; their headings come from the host
+    predictor (igtmpc.predictor predict_arrays), or from the plan an agent shares (utils.py:339-352), |heading| for obstacles on
+    routes '32', '41' (mpc.py:250-253), gathered per ego in ascending opponent order.
+    log_plans=True: a diagnostic for tests and probes, not part of the loop's interface (host loop only; the device-resident loops
+    ignore it) -- the result carries 'plans', one dict(ok[E,M], x[E,M,7,N+1], obs[E M,n_obs,2 or 3,N+1]) per step: what every
+    problem was solved against and what it answered.  Copies every step's arrays: leave it off when measuring."""
+    if ca_type not in ('circle', 'obca'):
+        raise ValueError(f"ca_type must be 'circle' or 'obca', not {ca_type!r}")
+    obca = ca_type == 'obca'
+    if obca and (device_resident or graph):
+        raise ValueError("ca_type='obca' runs in the host loop only (no device forecast of headings): not with device_resident=True "
+                         'or graph=True')
+    if obca and (dtype != 'f64' or polish_iters > 0 or value_polish_iters > 0):
+        raise ValueError("ca_type='obca' needs dtype='f64' and takes neither polish_iters nor value_polish_iters (the polish judges "
+                         'its trial plans with the circle)')
     if step not in ('torch', 'fused'):
         raise ValueError(f"step must be 'torch' or 'fused', not {step!r}")
     if step == 'fused' and not device_resident:
@@ -158,7 +176,7 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
                          cost_mode='value_net' if gt else 'progress', polish_iters=polish_iters, polish_grad=polish_grad,
                          polish_step=polish_step, value_polish_iters=vp_iters,
                          value_polish_driver=value_polish_driver if gt else 'host',
-                         **dict({} if feas_tol is None else {'feas_tol': feas_tol}, **(limits or {})))
+                         **dict({} if feas_tol is None else {'feas_tol': feas_tol}, **dict({'d_min': 0.0} if obca else {}, **limits)))
     if gt:
         solver.set_value_net(**value_net)
         # scenario encodings (mpc.py:336-337, utils.py:84-169): (e_ego, e_other) per problem
@@ -188,6 +206,8 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     x_data[:, :, 0] = x.reshape(E, 7 * M)
     infeasible = np.zeros((E, M), dtype=np.int64)
     solve_ms = []
+    plans = []
+    host_pred = ConstantAccelerationModel(N=N, dt=dt, constant_speed=constant_speed) if obca else None
     have_sol = np.zeros((E, M), dtype=bool)
     sol_x = np.zeros((E, M, 7, N + 1))
     sol_u = np.zeros((E, M, 2, N))
@@ -203,6 +223,9 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
         obs, tv = solver.forecast_scene(x.astype(npdt), a_fc.astype(npdt), rid.astype(np.int32), sol_x.astype(npdt),
                                          sol_u.astype(npdt), (have_sol & (t > 0)).astype(np.int32))
         tv = tv.reshape(E * M, -1)                                      # (read by the gt_mpc cost only: M = 2, [E M, 2])
+        if obca:      # the forecast's x, y with the host predictor's (or the shared plan's) headings: pose [E M, n_obs, 3, N+1]
+            head = obca_headings(host_pred, x, a_fc, rid, have_sol & (t > 0), sol_x, sol_u, absh)
+            obs = np.concatenate([obs, gather_opponents(head)[:, :, None, :].astype(npdt)], axis=2)
         # --- solve every (episode, agent) problem at once (evaluate.py:470-482); an agent that solved the previous
         #     step passes that solution, shifted by one step, as its warm start (evaluate.py:478-481)
         t0 = time.perf_counter()
@@ -210,13 +233,20 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
         if warm and t > (1 if gt else 0):                              # evaluate.py:478 (mpc: t >= 1) / :232 (gt_mpc: t > 1)
             fl = flags | np.where(have_sol.reshape(-1), IGT_FLAG_WARM, 0).astype(np.uint32)
             u_ws = shift_controls(sol_u).reshape(E * M, 2, N).astype(npdt)
-        out = solver.solve(x.reshape(E * M, 7).astype(npdt), u_prev.reshape(E * M, 2).astype(npdt),
-                           kp.reshape(E * M, 3).astype(npdt), fl, obs,
-                           tv if gt else None, enc.astype(npdt) if gt else None, u_ws=u_ws)
+        if obca:
+            out = solver.solve_box(x.reshape(E * M, 7).astype(npdt), u_prev.reshape(E * M, 2).astype(npdt),
+                                   kp.reshape(E * M, 3).astype(npdt), fl, obs, tv if gt else None,
+                                   enc.astype(npdt) if gt else None, u_ws=u_ws, length=OBCA_LENGTH, width=OBCA_WIDTH, d_box=0.0)
+        else:
+            out = solver.solve(x.reshape(E * M, 7).astype(npdt), u_prev.reshape(E * M, 2).astype(npdt),
+                               kp.reshape(E * M, 3).astype(npdt), fl, obs,
+                               tv if gt else None, enc.astype(npdt) if gt else None, u_ws=u_ws)
         solve_ms.append((time.perf_counter() - t0) * 1e3)
         ok = (out['status'] == 0).reshape(E, M)
         xs = out['x'].reshape(E, M, 7, N + 1).astype(np.float64)
         us = out['u'].reshape(E, M, 2, N).astype(np.float64)
+        if log_plans:
+            plans.append(dict(ok=ok.copy(), x=xs.copy(), obs=np.array(obs, dtype=np.float64)))
         # --- infeasible: brake fallback (evaluate.py:511-545)
         v_now = x[..., 5]
         a_fb = np.where(v_now > 0, a_min_policy, 0.0)
@@ -240,8 +270,40 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     deadlock = (x_data[:, 2::7, -1] <= 30).sum(axis=1) >= 2             # evaluate.py:566-569
     solver.close()
     stepper.close()
-    return dict(x_data=x_data, u_data=u_data, infeasible_ratio=infeasible / M_sim, deadlock=deadlock,
-                routes=pairs, solve_ms=np.array(solve_ms), track_env=limits.get('track_env'))
+    res = dict(x_data=x_data, u_data=u_data, infeasible_ratio=infeasible / M_sim, deadlock=deadlock,
+               routes=pairs, solve_ms=np.array(solve_ms), track_env=limits.get('track_env'))
+    if log_plans:
+        res['plans'] = plans
+    return res
+
+
+OBCA_LENGTH, OBCA_WIDTH = 4.47, 2.0      # mpc.py:48-51, 105-106: every vehicle's rectangle
+
+
+def obca_headings(pred, x, a_fc, rid, have_plan, sol_x, sol_u, absh):
+    """heading[E,M,N+1] of every agent's forecast as an 'obca' ego reads it: the host predictor's route heading along the
+    constant-acceleration forecast (node 0: the true heading); where the agent shares its plan, the plan's headings shifted by
+    one step and the route heading one predicted step behind its end (utils.py:339-352, the retry with a = 0 above v = 5);
+    |heading| for agents on routes '32', '41' (mpc.py:250-253)."""
+    E, M = x.shape[:2]
+    N, dt = pred.N, pred.dt
+    flat = lambda q: np.asarray(q, dtype=np.float64).reshape(E * M)
+    head = pred.predict_arrays(flat(x[..., 2]), flat(x[..., 5]), flat(a_fc), rid.reshape(E * M))['heading'].reshape(E, M, N + 1).copy()
+    head[..., 0] = x[..., 6]
+    last, a_last = sol_x[..., N], sol_u[:, :, 0, N - 1]
+    a_ext = np.where(np.clip(last[..., 5] + a_last * dt, pred.v_min, pred.v_max) > 5, 0.0, a_last)
+    s_ext = last[..., 2] + (last[..., 5] * dt + 0.5 * a_ext * dt ** 2)
+    shared = np.concatenate([sol_x[:, :, 6, 1:], R.psi_ref(rid.reshape(E * M), flat(s_ext)).reshape(E, M, 1)], axis=-1)
+    head = np.where(np.asarray(have_plan, dtype=bool)[..., None], shared, head)
+    return np.where(np.asarray(absh, dtype=bool)[..., None], np.abs(head), head)
+
+
+def gather_opponents(a):
+    """a[E,M,...] per agent -> [E M, M-1, ...]: for every (episode, ego) problem the other agents' rows in ascending order, the
+    order of the forecast's obstacle slots."""
+    E, M = a.shape[:2]
+    idx = np.array([[j for j in range(M) if j != i] for i in range(M)])      # [M, M-1]
+    return a[:, idx].reshape((E * M, M - 1) + a.shape[2:])
 
 
 def shift_controls(u):
@@ -511,6 +573,8 @@ def main():
                     'default: the network shipped for --sc')
     ap.add_argument('--net_prefix', default='', help="key prefix inside the npz, e.g. 'sc1_'")
     ap.add_argument('--verbose', action='store_true')
+    ap.add_argument('--ca_type', default='circle', choices=['circle', 'obca'],
+                    help="collision model: 'circle' (mpc.yaml:16) or 'obca', 4.47 x 2.0 m rectangles with d_min = 0 (host loop only)")
     ap.add_argument('--device_resident', action='store_true', help='keep all per-step arrays in HBM (torch tensors)')
     ap.add_argument('--graph', action='store_true', help='with --device_resident: capture one step in a stream graph and replay it')
     ap.add_argument('--step', default='torch', choices=['torch', 'fused'],
@@ -548,11 +612,12 @@ def main():
                         value_net=net, device_resident=a.device_resident, cand_mode=a.cand_mode, dtype=a.dtype, graph=a.graph,
                         polish_iters=a.polish_iters, polish_grad=a.polish_grad, polish_step=a.polish_step,
                         value_polish_iters=a.value_polish_iters, value_polish_driver=a.value_polish_driver,
-                        num_agents=a.num_agents, step=a.step,
+                        num_agents=a.num_agents, step=a.step, ca_type=a.ca_type,
                         **kw)
     if a.save_dir is not None:
         policy = {'type': 'MPC', 'N': a.N, 'dt': kw.get('dt', 0.1), 'a_min': -4, 'a_max': 3, 'v_min': -1.0, 'v_max': 5,      # mpc.yaml's keys
-                  'prediction_type': 'constant_acceleration', 'collision_avoidance_type': 'circle', **policy_file, 'N': a.N,
+                  'prediction_type': 'constant_acceleration', 'collision_avoidance_type': 'circle', **policy_file,
+                  'collision_avoidance_type': a.ca_type, 'N': a.N,
                   'solver': {'library': 'igtmpc', 'cand_mode': a.cand_mode, 'C': a.C, 'dtype': a.dtype, 'track_env': r.get('track_env')}}
         r['run_dir'] = save_results(r, a.save_dir, a.eval_mode, a.sc, policy=policy)
     print(json.dumps({'sc': a.sc, 'episodes': a.num_samples, 'routes': r['routes'][:4],

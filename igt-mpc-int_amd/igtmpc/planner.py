@@ -116,12 +116,19 @@ class MPC_Planner:
                  value_polish_driver='host'):
         assert agents is not None, 'Agents are not defined'           # mpc.py:155
         assert index is not None                                      # mpc.py:80
-        if ca_type != 'circle':
-            # OBCA needs dual variables as decision variables (mpc.py:211-221): not a shooting constraint
-            raise NotImplementedError("only ca_type='circle' (mpc.yaml:16) is supported")
+        if ca_type not in ('circle', 'obca'):
+            raise NotImplementedError("ca_type must be 'circle' (mpc.yaml:16) or 'obca'")
+        if ca_type == 'obca':
+            # The reference's dual variables (mpc.py:211-221) certify that the ego and the obstacle rectangles are d_min + 1e-6
+            # apart; the shooting solver judges that distance itself (BatchSolver.solve_box, igtmpc.h igt_solve_batch_box_f64)
+            if dtype != 'f64':
+                raise ValueError("ca_type='obca' needs dtype='f64' (the rectangle collision model has no float32 entry)")
+            if polish_iters > 0 or value_polish_iters > 0:
+                raise ValueError("ca_type='obca' does not take polish_iters or value_polish_iters (the polish judges its trial "
+                                 "plans with the circle)")
         self.N, self.dt, self.ca_type = N, dt, ca_type
         self.x_sol_prev = None
-        self.d_min = 2 * ca_radius                                    # mpc.py:45
+        self.d_min = 0.0 if ca_type == 'obca' else 2 * ca_radius      # mpc.py:42-45
         self.l = 4.47; self.l_f = 4.47 / 2; self.l_r = 4.47 / 2; self.width = 2.0      # mpc.py:48-51
         self.routes = routes
         self.steering_rate_limit = 0.7; self.jerk_limit = 0.9         # mpc.py:55-56
@@ -185,7 +192,7 @@ class MPC_Planner:
         self._dt = self._solver.np_dtype
         self._x0 = np.zeros((1, 7), self._dt)
         self._u_prev = np.zeros((1, 2), self._dt)
-        self._obs = np.zeros((1, self.num_obstacles, 2, N + 1), self._dt)
+        self._obs = np.zeros((1, self.num_obstacles, 3 if ca_type == 'obca' else 2, N + 1), self._dt)      # obca: x, y, heading
         self._tv_sv = np.zeros((1, 2), self._dt)
         self._enc = np.zeros((1, 2), self._dt)
         if use_NN_cost2go:
@@ -215,9 +222,12 @@ class MPC_Planner:
             if i != self.ind:
                 self.pred_ind.append(i)
                 assert len(pred) == self.N + 1, ValueError('Invalid prediction length (Horizon)')
-                # only x,y of the obstacle block are read by the cost / constraints (mpc.py:223-226)
+                # only x,y of the obstacle block are read by the cost / constraints (mpc.py:223-226); 'obca' reads the heading
+                # as well (mpc.py:214), |heading| for obstacles on routes '32', '41' (mpc.py:250-253)
                 self._obs[0, m, 0] = [p.x for p in pred]
                 self._obs[0, m, 1] = [p.y for p in pred]
+                if self.ca_type == 'obca':
+                    self._obs[0, m, 2] = [abs(p.heading) if self._abs_heading[i] else p.heading for p in pred]
                 m += 1
         if raw_preds is not None:
             self.raw_preds_np = np.zeros((1, self.nx * self.M))
@@ -242,9 +252,12 @@ class MPC_Planner:
             u_ws = np.ascontiguousarray(np.asarray(u_sol_prev, dtype=self._dt).reshape(1, 2, self.N))
             flags = flags | np.uint32(IGT_FLAG_WARM)
         t0 = time.time()
-        out = self._solver.solve(self._x0, self._u_prev, kp, flags, self._obs,
-                                 self._tv_sv if self.use_NN_cost2go else None,
-                                 self._enc if self.use_NN_cost2go else None, u_ws=u_ws)
+        tv_sv, enc = (self._tv_sv, self._enc) if self.use_NN_cost2go else (None, None)
+        if self.ca_type == 'obca':
+            out = self._solver.solve_box(self._x0, self._u_prev, kp, flags, self._obs, tv_sv, enc, u_ws=u_ws, length=self.l,
+                                         width=self.width, d_box=self.d_min)
+        else:
+            out = self._solver.solve(self._x0, self._u_prev, kp, flags, self._obs, tv_sv, enc, u_ws=u_ws)
         self.solve_time = time.time() - t0
         status = int(out['status'][0])
         self.sol = _Stats(self.solve_time, status, float(out['cost'][0]), int(out['argmin'][0]))

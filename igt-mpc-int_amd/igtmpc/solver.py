@@ -362,6 +362,75 @@ class BatchSolver:
         self._check(fn(self._h, B, *ptrs, mode, self._stream_ptr(stream, False)))
         return dict(X=X, U=Uo, cost=cost, viol=viol)
 
+    # ------------------------------------------------------------------ rectangle (OBCA) collision model
+    def _check_box(self, what, x0):
+        """What solve_box / rollout_all_box refuse before any GPU call (the library refuses the rest, naming the cause); -> B."""
+        if self.dtype != 'f64':
+            raise ValueError(f"{what} needs dtype='f64' (there is no float32 entry for the rectangle collision model)")
+        if self.value_polish_iters > 0:
+            raise ValueError(f'{what}: value_polish_iters > 0 is not supported (the polish judges its trial plans with the '
+                             f'circle); set_value_polish(0) for a box solve')
+        return int(x0.shape[0])
+
+    def solve_box(self, x0, u_prev, kparams, flags, obs_pose, tv_sv=None, enc=None, out=None, stream=None, u_ws=None,
+                  length=4.47, width=2.0, d_box=0.0):
+        """solve() under the rectangle (OBCA) collision model (igtmpc.h igt_solve_batch_box_f64): obs_pose[B,n_obs,3,N+1] holds
+        the obstacles' x, y and heading; ego and obstacles are rectangles of length x width that must stay d_box + 1e-6 apart
+        (the reference's 'obca' mode: 4.47 x 2.0, d_min = 0).  -> the dict of solve().  float64 solvers, any candidate family,
+        both costs; numpy arrays or tensors on the solver's GPU, as solve -- with tensors the call only enqueues and can be
+        captured.  Stateless: solve() of the same solver keeps judging circles.  Solvers with polish_iters > 0 or a value polish
+        are refused."""
+        B = self._check_box('solve_box', x0)
+        fn = self._entry('igt_solve_batch_box_f64')
+        dt, N, no = self.np_dtype, self.N, self.n_obs
+        if out is None:
+            if _is_torch(x0):
+                import torch
+                dev = x0.device
+                out = dict(x=torch.empty((B, 7, N + 1), dtype=torch.float64, device=dev),
+                           u=torch.empty((B, 2, N), dtype=torch.float64, device=dev),
+                           cost=torch.empty((B,), dtype=torch.float64, device=dev),
+                           argmin=torch.empty((B,), dtype=torch.int32, device=dev),
+                           status=torch.empty((B,), dtype=torch.int32, device=dev))
+            else:
+                out = dict(x=np.empty((B, 7, N + 1), dt), u=np.empty((B, 2, N), dt), cost=np.empty((B,), dt),
+                           argmin=np.empty((B,), np.int32), status=np.empty((B,), np.int32))
+        arrs = [x0, u_prev, kparams, flags, obs_pose, tv_sv, enc, u_ws, out['x'], out['u'], out['cost'], out['argmin'], out['status']]
+        shapes = [(B, 7), (B, 2), (B, 3), (B,), (B, no, 3, N + 1), (B, 2), (B, 2), (B, 2, N),
+                  (B, 7, N + 1), (B, 2, N), (B,), (B,), (B,)]
+        dts = [dt, dt, dt, np.uint32, dt, dt, dt, dt, dt, dt, dt, np.int32, np.int32]
+        mode, ptrs, keep = self._prep(arrs, shapes, dts)
+        if mode == L.IGT_MEM_HOST:
+            for k, i in (('x', 8), ('u', 9), ('cost', 10), ('argmin', 11), ('status', 12)):
+                if keep_is_copy(out[k], ptrs[i]):
+                    raise ValueError(f'out[{k!r}] must be a contiguous array of the solver dtype')
+        self._check(fn(self._h, B, *ptrs[:8], float(length), float(width), float(d_box), *ptrs[8:], mode,
+                       self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        return out
+
+    def rollout_all_box(self, x0, u_prev, kparams, flags, obs_pose, tv_sv=None, enc=None, want_X=True, want_U=True,
+                        stream=None, u_ws=None, length=4.47, width=2.0, d_box=0.0):
+        """rollout_all() under the rectangle collision model of solve_box (igtmpc.h igt_rollout_batch_box_f64):
+        -> dict(X[B,C,7,N+1] | None, U[B,C,2,N] | None, cost[B,C], viol[B,C]); the collision bit is the rectangles'.
+        Host mode, like rollout_all."""
+        B = self._check_box('rollout_all_box', x0)
+        if _is_torch(x0):
+            raise TypeError('rollout_all_box is a host-mode entry (numpy buffers), like rollout_all')
+        fn = self._entry('igt_rollout_batch_box_f64')
+        dt, N, no, Cn = self.np_dtype, self.N, self.n_obs, self.C
+        X = np.empty((B, Cn, 7, N + 1), dt) if want_X else None
+        U = np.empty((B, Cn, 2, N), dt) if want_U else None
+        cost = np.empty((B, Cn), dt)
+        viol = np.empty((B, Cn), np.uint32)
+        arrs = [x0, u_prev, kparams, flags, obs_pose, tv_sv, enc, u_ws, X, U, cost, viol]
+        shapes = [(B, 7), (B, 2), (B, 3), (B,), (B, no, 3, N + 1), (B, 2), (B, 2), (B, 2, N),
+                  (B, Cn, 7, N + 1), (B, Cn, 2, N), (B, Cn), (B, Cn)]
+        dts = [dt, dt, dt, np.uint32, dt, dt, dt, dt, dt, dt, dt, np.uint32]
+        mode, ptrs, keep = self._prep(arrs, shapes, dts)
+        self._check(fn(self._h, B, *ptrs[:8], float(length), float(width), float(d_box), *ptrs[8:], mode,
+                       self._stream_ptr(stream, False)))
+        return dict(X=X, U=U, cost=cost, viol=viol)
+
     # ------------------------------------------------------------------ polish under the value-network cost
     def _drop_vp_table(self):
         t, self._vp_table = getattr(self, '_vp_table', None), None

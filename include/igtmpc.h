@@ -488,6 +488,44 @@ int igt_rollout_candidates_f64(igt_handle* h, int32_t B, const double* x0, const
                                const double* U, double* X_all, double* U_all, double* cost_all, uint32_t* viol_all, int mem,
                                void* stream);
 
+/* Rectangle (OBCA) collision model: the reference's collision_avoidance_type 'obca' (mpc.py:42-43, 105-106, 211-221) for the
+ * shooting solver.  The reference certifies with dual variables that the ego rectangle and every obstacle rectangle are at
+ * least d_box + 1e-6 apart; these entries judge that distance themselves.  Arguments are igt_solve_batch_ws_f64's /
+ * igt_rollout_batch_ws_f64's, except:
+ *   obs_pose [B,n_obs,3,N+1]   obstacle x, y, heading predictions (node 0 is not judged, as for obs_xy) in place of obs_xy;
+ *   length, width, d_box       behind u_ws: the extents of every rectangle (ego and obstacles; the reference: 4.47, 2.0) and the
+ *                              distance to keep (the reference: d_min = 0 in this mode);
+ *   u_ws                       may be NULL.
+ * The verdict, per obstacle o and node k = 1..N, with the ego's centre p = (x_k, y_k) and heading psi_k of the roll-out, the
+ * obstacle's centre q and heading phi, half extents h = (length/2, width/2), rho = |h|:
+ *   1. gate: |p - q|^2 >= (d_box + 1e-6 + 2 rho)^2 is clear, nothing else is evaluated;
+ *   2. separating axes: t = R(psi)^T (q - p), theta = phi - psi, c = |cos theta|, s = |sin theta|; the depths
+ *      h0 + h0 c + h1 s - |t0| and h1 + h0 s + h1 c - |t1|, the same two with the roles swapped (t' = R(phi)^T (p - q)); depth is
+ *      the smallest of the four;
+ *   3. signed gap: depth > 0, the rectangles overlap and gap = -depth (the penetration depth); else gap is the smallest, over
+ *      the eight vertices of one rectangle taken in the other's frame, of |max(|v| - h, 0)| -- the distance of the rectangles;
+ *   4. g = d_box + 1e-6 - gap is violated where g > feas_tol and reports IGT_VIOL_COLLISION.  (The gap is signed on purpose:
+ *      with gap = 0 on overlap g would equal the default feas_tol exactly and an overlap would pass.)
+ *   5. a non-finite obstacle coordinate or heading (|heading| beyond 1e6 counts) makes that node of that obstacle no constraint.
+ * Every candidate family, both costs, refine_iters, the warm start, any N, n_rk4 and n_obs.  The calls are stateless: the handle
+ * keeps nothing of them and the circle entries are untouched; with every obstacle beyond the gate the answers are those of the
+ * circle entries without obstacles, bit for bit.  IGT_MEM_DEVICE: the call only enqueues; after one call at that B it neither
+ * allocates nor synchronises (capturable), and a replayed graph reads what obs_pose holds at replay time.
+ * IGT_E_INVALID, with a message that names the cause, for a null handle, B < 0, a length or width that is not finite and
+ * positive, a d_box that is not finite or below 0, a handle with polish_iters > 0 or igt_set_value_polish > 0 (the polish
+ * kernels judge their trial plans with the circle) and with the developer kernels of IGT_DEV_FLAGS 32 / 1024 / 2048; B = 0 is a
+ * no-op.  Out of scope, each refused or simply absent: _f32 entries, the two polishes, per-scenario candidate sets, a device
+ * forecast of headings, the device-resident closed loop, the pooled search (a box solve runs every 64-candidate unit on a plain
+ * grid).  (Added without a change of IGT_VERSION; callers probe the symbols.) */
+int igt_solve_batch_box_f64(igt_handle* h, int32_t B, const double* x0, const double* u_prev, const double* kparams,
+                            const uint32_t* flags, const double* obs_pose, const double* tv_sv, const double* enc,
+                            const double* u_ws, double length, double width, double d_box, double* x_out, double* u_out,
+                            double* cost_out, int32_t* argmin_out, int32_t* status_out, int mem, void* stream);
+int igt_rollout_batch_box_f64(igt_handle* h, int32_t B, const double* x0, const double* u_prev, const double* kparams,
+                              const uint32_t* flags, const double* obs_pose, const double* tv_sv, const double* enc,
+                              const double* u_ws, double length, double width, double d_box, double* X_all, double* U_all,
+                              double* cost_all, uint32_t* viol_all, int mem, void* stream);
+
 /* The closed-loop step behind a solve: what the reference's driver does with every agent's answer before the next timestep
  * (evaluate.py:491-545), for n = E M agents in the row order of igt_forecast_scene_* / the solve's B.  Per agent i, with
  * ok = status[i] == 0:
