@@ -51,6 +51,7 @@ struct igt_handle {
     size_t work_bytes = 0;
     double* d_routes = nullptr;    // [n_routes, 12] route geometry for the forecast kernel
     int n_routes = 0;
+    double* d_heads = nullptr;     // [n_routes, 3] (h0, hN, abs) per route for the pose forecast (igt_set_route_headings); null: not set
     void* d_net = nullptr;         // value-net parameters (float block followed by double block)
     igt::DevNet<float> net_f;
     igt::DevNet<double> net_d;
@@ -776,41 +777,51 @@ int cost_gradient_vn_impl(igt_handle* h, int32_t B, const double* x0, const doub
     return stg.download();
 }
 
-template <typename T>
+// POSE (igt_forecast_batch_pose_f64, T = double): obs_xy is obs_pose[B,n_obs,3,N+1] and opp_heading[B,n_obs] is read
+template <typename T, bool POSE = false>
 int forecast_impl(igt_handle* h, int32_t B, const T* ego_xyh, const T* opp, const T* opp_a, const int32_t* opp_route,
-                  const T* plan_x, const T* plan_u, const int32_t* has_plan, T* obs_xy, T* tv_sv, int mem, void* stream) {
+                  const T* opp_heading, const T* plan_x, const T* plan_u, const int32_t* has_plan, T* obs_xy, T* tv_sv, int mem,
+                  void* stream) {
     if (!h) return fail(IGT_E_INVALID, "null handle");
     if (B < 0) return fail(IGT_E_INVALID, "B < 0");
     if (B == 0) return IGT_OK;
     if (!h->d_routes) return fail(IGT_E_STATE, "route table not set (igt_set_routes)");
+    if (POSE && !h->d_heads) return fail(IGT_E_INVALID, "route headings not set (igt_set_route_headings)");
     if (h->p.n_obs < 1) return fail(IGT_E_INVALID, "the forecast entry needs at least one other vehicle (n_obs >= 1)");
-    if (!ego_xyh || !opp || !opp_a || !opp_route || !obs_xy || !tv_sv) return fail(IGT_E_INVALID, "null buffer");
+    if (!ego_xyh || !opp || !opp_a || !opp_route || !obs_xy || !tv_sv || (POSE && !opp_heading)) return fail(IGT_E_INVALID, "null buffer");
     const bool plans = plan_x && plan_u && has_plan;
     if (!plans && (plan_x || plan_u || has_plan)) return fail(IGT_E_INVALID, "plan_x, plan_u, has_plan go together");
     const int N = h->p.N;
     const size_t M1 = (size_t)h->p.n_obs;            // other vehicles per scene: every per-opponent array is [B, n_obs, ...]
     const size_t n_e = (size_t)B * 3, n_o = (size_t)B * M1 * 4, n_pairs = (size_t)B * M1;
     const size_t n_px = plans ? n_pairs * 7 * (N + 1) : 0, n_pu = plans ? n_pairs * 2 * N : 0;      // without plans: reserved only
-    const size_t n_out = n_pairs * 2 * (N + 1), n_tv = n_pairs * 2;
-    const T *de, *dop, *da, *dpx, *dpu;
+    const size_t n_out = n_pairs * (POSE ? 3 : 2) * (N + 1), n_tv = n_pairs * 2;
+    const T *de, *dop, *da, *dpx, *dpu, *dh = nullptr;
     const int32_t *dr, *dhp;
     T *dout, *dtv;
     Staging stg(h, mem, stream);
     stg.in(&de, ego_xyh, n_e); stg.in(&dop, opp, n_o); stg.in(&da, opp_a, n_pairs); stg.in(&dr, opp_route, n_pairs);
+    if constexpr (POSE) stg.in(&dh, opp_heading, n_pairs);
     stg.in(&dhp, has_plan, n_pairs, plans); stg.in(&dpx, plan_x, n_px); stg.in(&dpu, plan_u, n_pu);
     stg.out(&dout, obs_xy, n_out); stg.out(&dtv, tv_sv, n_tv);
     if (int rc = stg.upload()) return rc;
-    HIPCHK(igt::launch_forecast<T>(h->kp, B, h->d_routes, h->n_routes, de, dop, da, dr, plans ? dpx : nullptr,
-                                   plans ? dpu : nullptr, plans ? dhp : nullptr, dout, dtv, stg.stream()));
+    if constexpr (POSE)
+        HIPCHK(igt::launch_forecast_pose(h->kp, B, h->d_routes, h->n_routes, h->d_heads, de, dop, da, dr, dh, plans ? dpx : nullptr,
+                                         plans ? dpu : nullptr, plans ? dhp : nullptr, dout, dtv, stg.stream()));
+    else
+        HIPCHK(igt::launch_forecast<T>(h->kp, B, h->d_routes, h->n_routes, de, dop, da, dr, plans ? dpx : nullptr,
+                                       plans ? dpu : nullptr, plans ? dhp : nullptr, dout, dtv, stg.stream()));
     return stg.download();
 }
 
-template <typename T>
+// POSE (igt_forecast_scene_pose_f64, T = double): obs_xy is obs_pose[E M,n_obs,3,N+1]
+template <typename T, bool POSE = false>
 int forecast_scene_impl(igt_handle* h, int32_t E, const T* x, const T* a_prev, const int32_t* route, const T* plan_x,
                         const T* plan_u, const int32_t* has_plan, T* obs_xy, T* tv_sv, int mem, void* stream) {
     if (!h) return fail(IGT_E_INVALID, "null handle");
     if (E < 0) return fail(IGT_E_INVALID, "E < 0");
     if (!h->d_routes) return fail(IGT_E_INVALID, "route table not set (igt_set_routes)");
+    if (POSE && !h->d_heads) return fail(IGT_E_INVALID, "route headings not set (igt_set_route_headings)");
     if (h->p.n_obs < 1) return fail(IGT_E_INVALID, "the forecast entry needs at least one other vehicle (n_obs >= 1)");
     if (E == 0) return IGT_OK;
     if (!x || !a_prev || !route || !obs_xy || !tv_sv) return fail(IGT_E_INVALID, "null buffer");
@@ -821,7 +832,7 @@ int forecast_scene_impl(igt_handle* h, int32_t E, const T* x, const T* a_prev, c
     if ((size_t)E > (size_t)0x7fffffff / (M * (M - 1))) return fail(IGT_E_INVALID, "E (n_obs + 1) n_obs exceeds int32");
     const size_t n_ag = (size_t)E * M, n_x = n_ag * 7;
     const size_t n_px = plans ? n_ag * 7 * (N + 1) : 0, n_pu = plans ? n_ag * 2 * N : 0;      // without plans: reserved only
-    const size_t n_pairs = n_ag * (M - 1), n_out = n_pairs * 2 * (N + 1), n_tv = n_pairs * 2;
+    const size_t n_pairs = n_ag * (M - 1), n_out = n_pairs * (POSE ? 3 : 2) * (N + 1), n_tv = n_pairs * 2;
     const T *dx, *da, *dpx, *dpu;
     const int32_t *dr, *dhp;
     T *dout, *dtv;
@@ -830,8 +841,12 @@ int forecast_scene_impl(igt_handle* h, int32_t E, const T* x, const T* a_prev, c
     stg.in(&dhp, has_plan, n_ag, plans); stg.in(&dpx, plan_x, n_px); stg.in(&dpu, plan_u, n_pu);
     stg.out(&dout, obs_xy, n_out); stg.out(&dtv, tv_sv, n_tv);
     if (int rc = stg.upload()) return rc;
-    HIPCHK(igt::launch_forecast_scene<T>(h->kp, E, h->d_routes, h->n_routes, dx, da, dr, plans ? dpx : nullptr,
-                                         plans ? dpu : nullptr, plans ? dhp : nullptr, dout, dtv, stg.stream()));
+    if constexpr (POSE)
+        HIPCHK(igt::launch_forecast_scene_pose(h->kp, E, h->d_routes, h->n_routes, h->d_heads, dx, da, dr, plans ? dpx : nullptr,
+                                               plans ? dpu : nullptr, plans ? dhp : nullptr, dout, dtv, stg.stream()));
+    else
+        HIPCHK(igt::launch_forecast_scene<T>(h->kp, E, h->d_routes, h->n_routes, dx, da, dr, plans ? dpx : nullptr,
+                                             plans ? dpu : nullptr, plans ? dhp : nullptr, dout, dtv, stg.stream()));
     return stg.download();
 }
 
@@ -972,6 +987,7 @@ int igt_destroy(igt_handle* h) {
     if (h->d_work) (void)hipFree(h->d_work);
     if (h->d_net) (void)hipFree(h->d_net);
     if (h->d_routes) (void)hipFree(h->d_routes);
+    if (h->d_heads) (void)hipFree(h->d_heads);
     if (h->d_u0) (void)hipFree(h->d_u0);
     if (h->comm) { if (Rccl* r = rccl()) (void)r->CommDestroy(h->comm); h->comm = nullptr; rccl_release(); }
     for (int i = 0; i < 3; ++i) (void)hipEventDestroy(h->ev[i]);
@@ -1250,6 +1266,7 @@ int igt_set_routes(igt_handle* h, int32_t n_routes, const double* table) {
     if (n_routes < 1 || n_routes > 64) return fail(IGT_E_INVALID, "n_routes must be in [1, 64]");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->d_heads && n_routes != h->n_routes) { HIPCHK(hipFree(h->d_heads)); h->d_heads = nullptr; }      // headings of another table
     if (h->d_routes) { HIPCHK(hipFree(h->d_routes)); h->d_routes = nullptr; h->n_routes = 0; }
     HIPCHK(hipMalloc((void**)&h->d_routes, (size_t)n_routes * 12 * sizeof(double)));
     HIPCHK(hipMemcpy(h->d_routes, table, (size_t)n_routes * 12 * sizeof(double), hipMemcpyHostToDevice));
@@ -1257,10 +1274,39 @@ int igt_set_routes(igt_handle* h, int32_t n_routes, const double* table) {
     return IGT_OK;
 }
 
+int igt_set_route_headings(igt_handle* h, int32_t n_routes, const double* table) {
+    if (!h) return fail(IGT_E_INVALID, "igt_set_route_headings: null handle");
+    if (!table) return fail(IGT_E_INVALID, "igt_set_route_headings: null table");
+    if (!h->d_routes) return fail(IGT_E_INVALID, "igt_set_route_headings: route table not set (igt_set_routes first)");
+    if (n_routes != h->n_routes)
+        return fail(IGT_E_INVALID, "igt_set_route_headings: n_routes = " + std::to_string(n_routes) + " but the igt_set_routes table has " +
+                                       std::to_string(h->n_routes) + " routes");
+    for (int i = 0; i < n_routes; ++i)
+        if (!std::isfinite(table[(size_t)i * 3 + 0]) || !std::isfinite(table[(size_t)i * 3 + 1]))
+            return fail(IGT_E_INVALID, "igt_set_route_headings: h0 / hN of route " + std::to_string(i) + " is not finite");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (!h->d_heads) HIPCHK(hipMalloc((void**)&h->d_heads, (size_t)n_routes * 3 * sizeof(double)));
+    HIPCHK(hipMemcpy(h->d_heads, table, (size_t)n_routes * 3 * sizeof(double), hipMemcpyHostToDevice));
+    return IGT_OK;
+}
+
+int igt_forecast_scene_pose_f64(igt_handle* h, int32_t E, const double* x, const double* a_prev, const int32_t* route,
+                                const double* plan_x, const double* plan_u, const int32_t* has_plan, double* obs_pose,
+                                double* tv_sv, int mem, void* stream) {
+    return forecast_scene_impl<double, true>(h, E, x, a_prev, route, plan_x, plan_u, has_plan, obs_pose, tv_sv, mem, stream);
+}
+int igt_forecast_batch_pose_f64(igt_handle* h, int32_t B, const double* ego_xyh, const double* opp, const double* opp_a,
+                                const int32_t* opp_route, const double* opp_heading, const double* plan_x, const double* plan_u,
+                                const int32_t* has_plan, double* obs_pose, double* tv_sv, int mem, void* stream) {
+    return forecast_impl<double, true>(h, B, ego_xyh, opp, opp_a, opp_route, opp_heading, plan_x, plan_u, has_plan, obs_pose, tv_sv,
+                                       mem, stream);
+}
+
 int igt_forecast_batch_f32(igt_handle* h, int32_t B, const float* ego_xyh, const float* opp, const float* opp_a,
                            const int32_t* opp_route, const float* plan_x, const float* plan_u, const int32_t* has_plan,
                            float* obs_xy, float* tv_sv, int mem, void* stream) {
-    return forecast_impl<float>(h, B, ego_xyh, opp, opp_a, opp_route, plan_x, plan_u, has_plan, obs_xy, tv_sv, mem, stream);
+    return forecast_impl<float>(h, B, ego_xyh, opp, opp_a, opp_route, nullptr, plan_x, plan_u, has_plan, obs_xy, tv_sv, mem, stream);
 }
 int igt_loop_advance_f64(igt_handle* h, int32_t n, double* x, double* u_prev, const double* kparams, const int32_t* status,
                          const double* x_sol, const double* u_sol, double a_brake, int32_t* has_plan, double* plan_x,
@@ -1289,7 +1335,7 @@ int igt_forecast_scene_f64(igt_handle* h, int32_t E, const double* x, const doub
 int igt_forecast_batch_f64(igt_handle* h, int32_t B, const double* ego_xyh, const double* opp, const double* opp_a,
                            const int32_t* opp_route, const double* plan_x, const double* plan_u, const int32_t* has_plan,
                            double* obs_xy, double* tv_sv, int mem, void* stream) {
-    return forecast_impl<double>(h, B, ego_xyh, opp, opp_a, opp_route, plan_x, plan_u, has_plan, obs_xy, tv_sv, mem, stream);
+    return forecast_impl<double>(h, B, ego_xyh, opp, opp_a, opp_route, nullptr, plan_x, plan_u, has_plan, obs_xy, tv_sv, mem, stream);
 }
 
 int igt_cartesian_euler_f32(igt_handle* h, int32_t n, int32_t T, const float* z0, const float* u, float* z_out,

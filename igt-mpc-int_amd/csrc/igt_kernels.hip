@@ -469,14 +469,40 @@ __device__ __forceinline__ void frenet2global_dev(const double* __restrict__ r, 
     }
 }
 
+// Heading row of the pose forecast (igt_forecast_*_pose_f64): what an 'obca' ego reads as an obstacle's heading at one node.
+// hd = (h0, hN, abs) of the route (igt_set_route_headings), r its geometry row.  given: v IS the heading -- the true one at node 0
+// (cam:40) or the shared plan's (utils.py:339-352); else v is the forecast's arc length s and the heading is the reference's
+// psi_ref(s) = pw_lin(s, [0, b0, b1, 1000], [h0, h0, hN, hN]) (cam:46-66, 74): h0 on a straight route, else h0 + w (hN - h0)
+// with w = (s - b0) / (b1 - b0) clamped to [0, 1].  abs != 0: |heading| (routes '32', '41', mpc.py:250-253).
 template <typename T>
+__device__ __forceinline__ T pose_heading_dev(const double* __restrict__ r, const double* __restrict__ hd, bool given, T v) {
+    T psi = v;
+    if (!given) {
+        const T h0 = (T)hd[0], hN = (T)hd[1];
+        psi = h0;
+        if (r[11] == 0.0) {
+            const T b0 = (T)r[6], b1 = (T)r[7];
+            const T w = fmin(fmax((v - b0) / (b1 - b0), (T)0), (T)1);
+            psi = h0 + w * (hN - h0);
+        }
+    }
+    return hd[2] != 0.0 ? (T)fabs(psi) : psi;
+}
+
+// POSE = false: igt_forecast_batch_*, obs rows (x, y); heads and opp_heading are not read.  POSE = true:
+// igt_forecast_batch_pose_f64, obs rows (x, y, heading) -- the same statements for x, y and tv_sv, and the heading row
+// (pose_heading_dev) is NOT filtered: an opponent behind the ego keeps it while its x, y become -20.
+template <typename T, bool POSE>
 __global__ __launch_bounds__(256) void forecast_kernel(KP P, int B, const double* __restrict__ routes, int n_routes,
+                                                       const double* __restrict__ heads,
                                                        const T* __restrict__ ego_xyh, const T* __restrict__ opp,
                                                        const T* __restrict__ opp_a,
                                                        const int32_t* __restrict__ opp_route,
+                                                       const T* __restrict__ opp_heading,
                                                        const T* __restrict__ plan_x, const T* __restrict__ plan_u,
                                                        const int32_t* __restrict__ has_plan, T* __restrict__ obs_xy,
                                                        T* __restrict__ tv_sv) {
+    constexpr int ROWS = POSE ? 3 : 2;
     // one lane per (problem, other vehicle): pair = b n_obs + o -- the M - 1 obstacles of a scene (mpc.py:82-83 is written for any
     // M) are forecast, shared and filtered independently of each other; `b` below indexes the per-pair arrays, `e` the ego's
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -487,14 +513,18 @@ __global__ __launch_bounds__(256) void forecast_kernel(KP P, int B, const double
     int rid = opp_route[b];
     rid = rid < 0 ? 0 : (rid >= n_routes ? n_routes - 1 : rid);
     const double* __restrict__ r = routes + (size_t)rid * 12;
-    T* ox = obs_xy + (size_t)b * 2 * (N + 1);
+    const double* __restrict__ hd = POSE ? heads + (size_t)rid * 3 : nullptr;
+    T* ox = obs_xy + (size_t)b * ROWS * (N + 1);
     T* oy = ox + (N + 1);
+    T* oh = oy + (N + 1);          // POSE only
     const bool shared = plan_x && has_plan && has_plan[b] != 0;
     T x0, y0, sl, vl;
     if (shared) {
         // utils.py:339-352: plan states k = 1..N, then one predicted step from the plan's last state
         const T* px = plan_x + (size_t)b * 7 * (N + 1);
         for (int k = 0; k < N; ++k) { ox[k] = px[0 * (N + 1) + k + 1]; oy[k] = px[1 * (N + 1) + k + 1]; }
+        if constexpr (POSE)
+            for (int k = 0; k < N; ++k) oh[k] = pose_heading_dev<T>(r, hd, true, px[6 * (N + 1) + k + 1]);
         T s = px[2 * (N + 1) + N], v = px[5 * (N + 1) + N];
         T a = plan_u[(size_t)b * 2 * N + (N - 1)];
         T vn = fmin(fmax(v + a * dt, (T)-2), (T)20);                       // cam:71
@@ -503,6 +533,7 @@ __global__ __launch_bounds__(256) void forecast_kernel(KP P, int B, const double
         T xe, ye;
         frenet2global_dev<T>(r, s, xe, ye);
         ox[N] = xe; oy[N] = ye;
+        if constexpr (POSE) oh[N] = pose_heading_dev<T>(r, hd, false, s);
         sl = s; vl = vn;
         x0 = ox[0]; y0 = oy[0];
     } else {
@@ -510,12 +541,14 @@ __global__ __launch_bounds__(256) void forecast_kernel(KP P, int B, const double
         const T a = opp_a[b];
         x0 = opp[(size_t)b * 4 + 0]; y0 = opp[(size_t)b * 4 + 1];
         ox[0] = x0; oy[0] = y0;                                            // cam:40: k = 0 is the true state
+        if constexpr (POSE) oh[0] = pose_heading_dev<T>(r, hd, true, opp_heading[b]);
         for (int k = 1; k <= N; ++k) {
             s = s + (v * dt + (T)0.5 * a * dt * dt);                       // cam:70
             v = fmin(fmax(v + a * dt, (T)-2), (T)20);                      // cam:71 (fourwayint.yaml:23-24)
             T xk, yk;
             frenet2global_dev<T>(r, s, xk, yk);                            // cam:75
             ox[k] = xk; oy[k] = yk;
+            if constexpr (POSE) oh[k] = pose_heading_dev<T>(r, hd, false, s);      // cam:74
         }
         sl = s; vl = v;
     }
@@ -536,8 +569,11 @@ __global__ __launch_bounds__(256) void forecast_kernel(KP P, int B, const double
 // utils.py:365-388), or (-20, -20) where agent j is behind that ego.  The filter needs only agent j's first point, which is
 // known before the roll, so there is one pass over k and nothing is read back.  The M egos' (x, y, heading) come from the
 // scene's own rows of x; nothing is gathered.
-template <typename T, int M>
+// POSE as in forecast_kernel: igt_forecast_scene_pose_f64 writes rows (x, y, heading) per (ego, opponent), the heading the same
+// for every ego (not filtered); agent j's true heading is x[e,j,6].
+template <typename T, int M, bool POSE>
 __global__ __launch_bounds__(256) void forecast_scene_kernel(KP P, int n_agents, const double* __restrict__ routes, int n_routes,
+                                                             const double* __restrict__ heads,
                                                              const T* __restrict__ x, const T* __restrict__ a_prev,
                                                              const int32_t* __restrict__ route,
                                                              const T* __restrict__ plan_x, const T* __restrict__ plan_u,
@@ -546,11 +582,13 @@ __global__ __launch_bounds__(256) void forecast_scene_kernel(KP P, int n_agents,
     const int b = blockIdx.x * blockDim.x + threadIdx.x;      // agent row e M + j
     if (b >= n_agents) return;
     const int e = b / M, j = b - e * M;
+    constexpr int ROWS = POSE ? 3 : 2;
     const int N = P.N;
     const T dt = (T)P.dt;
     int rid = route[b];
     rid = rid < 0 ? 0 : (rid >= n_routes ? n_routes - 1 : rid);
     const double* __restrict__ r = routes + (size_t)rid * 12;
+    const double* __restrict__ hd = POSE ? heads + (size_t)rid * 3 : nullptr;
     const T* xj = x + (size_t)b * 7;
     const bool shared = plan_x && has_plan && has_plan[b] != 0;
     const T* px = shared ? plan_x + (size_t)b * 7 * (N + 1) : nullptr;
@@ -568,7 +606,7 @@ __global__ __launch_bounds__(256) void forecast_scene_kernel(KP P, int n_agents,
         const T dot = (x0 - xi[0]) * ch + (y0 - xi[1]) * sh;
         behind[q] = dot < 0;
         const size_t pair = ((size_t)e * M + i) * (M - 1) + (size_t)(j - (j > i ? 1 : 0));
-        ox[q] = obs_xy + pair * 2 * (N + 1);
+        ox[q] = obs_xy + pair * ROWS * (N + 1);
         tv[q] = tv_sv + pair * 2;
     }
     const auto put = [&](int k, T xk, T yk) {
@@ -578,10 +616,17 @@ __global__ __launch_bounds__(256) void forecast_scene_kernel(KP P, int n_agents,
             ox[q][N + 1 + k] = behind[q] ? (T)-20 : yk;
         }
     };
+    const auto put_heading = [&](int k, bool given, T v) {      // POSE only; the same for every ego: not filtered
+        const T hk = pose_heading_dev<T>(r, hd, given, v);
+#pragma unroll
+        for (int q = 0; q < M - 1; ++q) ox[q][2 * (N + 1) + k] = hk;
+    };
     T sl, vl;
     if (shared) {
         // utils.py:339-352: plan states k = 1..N, then one predicted step from the plan's last state
         for (int k = 0; k < N; ++k) put(k, px[0 * (N + 1) + k + 1], px[1 * (N + 1) + k + 1]);
+        if constexpr (POSE)
+            for (int k = 0; k < N; ++k) put_heading(k, true, px[6 * (N + 1) + k + 1]);
         T s = px[2 * (N + 1) + N], v = px[5 * (N + 1) + N];
         T a = plan_u[(size_t)b * 2 * N + (N - 1)];
         T vn = fmin(fmax(v + a * dt, (T)-2), (T)20);                       // cam:71
@@ -590,17 +635,20 @@ __global__ __launch_bounds__(256) void forecast_scene_kernel(KP P, int n_agents,
         T xe, ye;
         frenet2global_dev<T>(r, s, xe, ye);
         put(N, xe, ye);
+        if constexpr (POSE) put_heading(N, false, s);
         sl = s; vl = vn;
     } else {
         T s = xj[2], v = xj[5];
         const T a = a_prev[b];
         put(0, x0, y0);                                                    // cam:40: k = 0 is the true state
+        if constexpr (POSE) put_heading(0, true, xj[6]);
         for (int k = 1; k <= N; ++k) {
             s = s + (v * dt + (T)0.5 * a * dt * dt);                       // cam:70
             v = fmin(fmax(v + a * dt, (T)-2), (T)20);                      // cam:71 (fourwayint.yaml:23-24)
             T xk, yk;
             frenet2global_dev<T>(r, s, xk, yk);                            // cam:75
             put(k, xk, yk);
+            if constexpr (POSE) put_heading(k, false, s);                  // cam:74
         }
         sl = s; vl = v;
     }
@@ -914,8 +962,18 @@ hipError_t launch_forecast(const KP& P, int B, const double* routes, int n_route
                            const T* opp_a, const int32_t* opp_route, const T* plan_x, const T* plan_u,
                            const int32_t* has_plan, T* obs_xy, T* tv_sv, hipStream_t st) {
     const int pairs = B * (P.n_obs > 1 ? P.n_obs : 1);
-    hipLaunchKernelGGL((forecast_kernel<T>), dim3((pairs + 255) / 256), dim3(256), 0, st, P, pairs, routes, n_routes, ego_xyh, opp,
-                       opp_a, opp_route, plan_x, plan_u, has_plan, obs_xy, tv_sv);
+    hipLaunchKernelGGL((forecast_kernel<T, false>), dim3((pairs + 255) / 256), dim3(256), 0, st, P, pairs, routes, n_routes,
+                       (const double*)nullptr, ego_xyh, opp, opp_a, opp_route, (const T*)nullptr, plan_x, plan_u, has_plan, obs_xy,
+                       tv_sv);
+    return hipGetLastError();
+}
+hipError_t launch_forecast_pose(const KP& P, int B, const double* routes, int n_routes, const double* heads,
+                                const double* ego_xyh, const double* opp, const double* opp_a, const int32_t* opp_route,
+                                const double* opp_heading, const double* plan_x, const double* plan_u, const int32_t* has_plan,
+                                double* obs_pose, double* tv_sv, hipStream_t st) {
+    const int pairs = B * (P.n_obs > 1 ? P.n_obs : 1);
+    hipLaunchKernelGGL((forecast_kernel<double, true>), dim3((pairs + 255) / 256), dim3(256), 0, st, P, pairs, routes, n_routes,
+                       heads, ego_xyh, opp, opp_a, opp_route, opp_heading, plan_x, plan_u, has_plan, obs_pose, tv_sv);
     return hipGetLastError();
 }
 template <typename T>
@@ -926,8 +984,26 @@ hipError_t launch_forecast_scene(const KP& P, int E, const double* routes, int n
     const dim3 grid((n + 255) / 256), block(256);
 #define IGT_SCENE(m)                                                                                                       \
     case m:                                                                                                                \
-        hipLaunchKernelGGL((forecast_scene_kernel<T, m>), grid, block, 0, st, P, n, routes, n_routes, x, a_prev, route,    \
-                           plan_x, plan_u, has_plan, obs_xy, tv_sv);                                                       \
+        hipLaunchKernelGGL((forecast_scene_kernel<T, m, false>), grid, block, 0, st, P, n, routes, n_routes,               \
+                           (const double*)nullptr, x, a_prev, route, plan_x, plan_u, has_plan, obs_xy, tv_sv);             \
+        break;
+    switch (M) {
+        IGT_SCENE(2) IGT_SCENE(3) IGT_SCENE(4) IGT_SCENE(5)
+        default: return hipErrorInvalidValue;
+    }
+#undef IGT_SCENE
+    return hipGetLastError();
+}
+hipError_t launch_forecast_scene_pose(const KP& P, int E, const double* routes, int n_routes, const double* heads,
+                                      const double* x, const double* a_prev, const int32_t* route, const double* plan_x,
+                                      const double* plan_u, const int32_t* has_plan, double* obs_pose, double* tv_sv,
+                                      hipStream_t st) {
+    const int M = P.n_obs + 1, n = E * M;       // one lane per agent of every scene
+    const dim3 grid((n + 255) / 256), block(256);
+#define IGT_SCENE(m)                                                                                                       \
+    case m:                                                                                                                \
+        hipLaunchKernelGGL((forecast_scene_kernel<double, m, true>), grid, block, 0, st, P, n, routes, n_routes, heads, x, \
+                           a_prev, route, plan_x, plan_u, has_plan, obs_pose, tv_sv);                                      \
         break;
     switch (M) {
         IGT_SCENE(2) IGT_SCENE(3) IGT_SCENE(4) IGT_SCENE(5)

@@ -561,6 +561,16 @@ template <typename T>
 hipError_t launch_forecast_scene(const KP& P, int E, const double* routes, int n_routes, const T* x, const T* a_prev,
                                  const int32_t* route, const T* plan_x, const T* plan_u, const int32_t* has_plan, T* obs_xy,
                                  T* tv_sv, hipStream_t st);
+// igt_forecast_batch_pose_f64 / igt_forecast_scene_pose_f64: the two forecasts with a heading row behind x, y (obs_pose[..,3,N+1]);
+// heads[n_routes,3] = (h0, hN, abs) of igt_set_route_headings.  float64 only: the box solve that reads a pose has no float entry.
+hipError_t launch_forecast_pose(const KP& P, int B, const double* routes, int n_routes, const double* heads,
+                                const double* ego_xyh, const double* opp, const double* opp_a, const int32_t* opp_route,
+                                const double* opp_heading, const double* plan_x, const double* plan_u, const int32_t* has_plan,
+                                double* obs_pose, double* tv_sv, hipStream_t st);
+hipError_t launch_forecast_scene_pose(const KP& P, int E, const double* routes, int n_routes, const double* heads,
+                                      const double* x, const double* a_prev, const int32_t* route, const double* plan_x,
+                                      const double* plan_u, const int32_t* has_plan, double* obs_pose, double* tv_sv,
+                                      hipStream_t st);
 // ---- igt_loop_advance_*: the closed-loop step behind a solve (igt_kernels.hip loop_advance_kernel) ----
 // A workgroup of LOOP_THREADS lanes owns LOOP_AGENTS consecutive agents.  Its lanes 0 .. agents - 1 decide and step one agent each;
 // then all of its lanes walk the agents' rows of x_sol and of u_sol -- contiguous per agent, so one contiguous span per

@@ -86,6 +86,9 @@ SYMBOLS = {
     # obs_pose[B,n_obs,3,N+1] where the _ws entries take obs_xy; length, width, d_box behind u_ws
     'igt_solve_batch_box_f64': (_i, [_vp, _i32] + [_vp] * 8 + [C.c_double] * 3 + [_vp] * 5 + [_i, _vp]),
     'igt_rollout_batch_box_f64': (_i, [_vp, _i32] + [_vp] * 8 + [C.c_double] * 3 + [_vp] * 4 + [_i, _vp]),
+    'igt_set_route_headings': (_i, [_vp, _i32, _vp]),
+    'igt_forecast_scene_pose_f64': (_i, _FSCENE),         # obs_pose[E M,n_obs,3,N+1] where the scene forecast takes obs_xy
+    'igt_forecast_batch_pose_f64': (_i, [_vp, _i32] + [_vp] * 10 + [_i, _vp]),      # opp_heading behind opp_route
     'igt_loop_advance_f64': (_i, _LOOP),
     'igt_loop_advance_f32': (_i, _LOOP),
     'igt_set_profiling': (_i, [_vp, _i]),
@@ -96,7 +99,8 @@ SYMBOLS = {
 # added without a change of IGT_VERSION: a library of the same ABI from before them (IGT_LIB_PATH, tools/ab_lib.sh) lacks them
 OPTIONAL_SYMBOLS = ('igt_set_polish_gradient', 'igt_cost_gradient_f64', 'igt_terminal_value_f64', 'igt_cost_gradient_vn_f64',
                     'igt_set_polish_step', 'igt_set_value_polish', 'igt_solve_candidates_f64', 'igt_rollout_candidates_f64',
-                    'igt_loop_advance_f64', 'igt_loop_advance_f32', 'igt_solve_batch_box_f64', 'igt_rollout_batch_box_f64')
+                    'igt_loop_advance_f64', 'igt_loop_advance_f32', 'igt_solve_batch_box_f64', 'igt_rollout_batch_box_f64',
+                    'igt_set_route_headings', 'igt_forecast_scene_pose_f64', 'igt_forecast_batch_pose_f64')
 
 _libs = {}
 # IGT_DEV_FLAGS bits (csrc/igt_device.h DevFlag; the launch-time bits there are the library's own and not listed here)

@@ -71,7 +71,7 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
                     eval_mode='mpc', value_net=None, device_resident=False, warm_start=None, init=None,
                     terminal_set=True, feas_tol=None, limits=None, graph=False, a_min_policy=None, constant_speed=False,
                     v0=0.0, polish_iters=0, num_agents=2, polish_grad='fd', polish_step='gradient', value_polish_iters=0,
-                    value_polish_driver='host', step='torch', ca_type='circle', log_plans=False):
+                    value_polish_driver='host', step='torch', ca_type='circle', log_plans=False, pose_forecast='host'):
     """eval_mode 'mpc' (evaluate.py:370-639) or 'gt_mpc' (123-369: terminal value network in the cost;
     value_net = dict(layers=[(W,b),...][, Wn, mu_f, sigma_t, mu_t]), default: the network the reference ships for
     scenario sc -- its normalisation statistics are not shipped, identity unless given).  device_resident=True keeps every per-step array in HBM (torch tensors;
@@ -106,17 +106,26 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     M > 2: routes.scene_routes; init = (x[E,M,7], route tuples of length M).  eval_mode 'mpc' only beyond two (the value
     network's features are those of a two-vehicle scene, mpc.py:326-338).
     ca_type 'circle' (default; mpc.yaml:16) or 'obca' (mpc.py:42-43, 211-221): every vehicle a 4.47 x 2.0 m rectangle, d_min = 0,
-    solved through BatchSolver.solve_box.  The host loop only: device_resident=True or graph=True with 'obca' raises ValueError
-    (there is no device forecast of headings).  The obstacles' x, y stay the device forecast's; their headings come from the host
+    solved through BatchSolver.solve_box.  With pose_forecast='host' (the default) the host loop only: device_resident=True or
+    graph=True with 'obca' raises ValueError.  The obstacles' x, y stay the device forecast's; their headings come from the host
     predictor (igtmpc.predictor predict_arrays), or from the plan an agent shares (utils.py:339-352), |heading| for obstacles on
     routes '32', '41' (mpc.py:250-253), gathered per ego in ascending opponent order.
+    pose_forecast (ca_type 'obca'): where the obstacles' headings come from.  'host' (default): the paragraph above, the host loop
+    only.  'device': the whole pose [E M, n_obs, 3, N+1] from BatchSolver.forecast_scene_pose (igtmpc.h igt_forecast_scene_pose_f64)
+    in one call -- no host predictor, nothing concatenated -- and with it device_resident=True, graph=True and step='fused' run
+    with rectangles.  'device' with ca_type 'circle' raises ValueError (nothing reads a pose there).
     log_plans=True: a diagnostic for tests and probes, not part of the loop's interface (host loop only; the device-resident loops
     ignore it) -- the result carries 'plans', one dict(ok[E,M], x[E,M,7,N+1], obs[E M,n_obs,2 or 3,N+1]) per step: what every
     problem was solved against and what it answered.  Copies every step's arrays: leave it off when measuring."""
     if ca_type not in ('circle', 'obca'):
         raise ValueError(f"ca_type must be 'circle' or 'obca', not {ca_type!r}")
     obca = ca_type == 'obca'
-    if obca and (device_resident or graph):
+    if pose_forecast not in ('host', 'device'):
+        raise ValueError(f"pose_forecast must be 'host' or 'device', not {pose_forecast!r}")
+    pose_dev = pose_forecast == 'device'
+    if pose_dev and not obca:
+        raise ValueError("pose_forecast='device' needs ca_type='obca': the circle model reads no pose")
+    if obca and not pose_dev and (device_resident or graph):
         raise ValueError("ca_type='obca' runs in the host loop only (no device forecast of headings): not with device_resident=True "
                          'or graph=True')
     if obca and (dtype != 'f64' or polish_iters > 0 or value_polish_iters > 0):
@@ -194,7 +203,8 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
 
     if device_resident:
         out = _loop_device(solver, stepper, x, u_prev, kp, flags, rid, enc if gt else None, gt, E, M, N, M_sim, device, warm,
-                           graph=graph, a_min_policy=a_min_policy, constant_speed=constant_speed, fused=step == 'fused')
+                           graph=graph, a_min_policy=a_min_policy, constant_speed=constant_speed, fused=step == 'fused',
+                           obca=obca)
         solver.close()
         stepper.close()
         out['routes'] = pairs
@@ -207,7 +217,7 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     infeasible = np.zeros((E, M), dtype=np.int64)
     solve_ms = []
     plans = []
-    host_pred = ConstantAccelerationModel(N=N, dt=dt, constant_speed=constant_speed) if obca else None
+    host_pred = ConstantAccelerationModel(N=N, dt=dt, constant_speed=constant_speed) if obca and not pose_dev else None
     have_sol = np.zeros((E, M), dtype=bool)
     sol_x = np.zeros((E, M, 7, N + 1))
     sol_u = np.zeros((E, M, 2, N))
@@ -220,10 +230,11 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
             a_fc = np.tile(0.09 * (np.arange(M) + 1.0), (E, 1))
         if constant_speed:                                              # constant_acceleration_model.py:26-29
             a_fc = np.zeros((E, M))
-        obs, tv = solver.forecast_scene(x.astype(npdt), a_fc.astype(npdt), rid.astype(np.int32), sol_x.astype(npdt),
-                                         sol_u.astype(npdt), (have_sol & (t > 0)).astype(np.int32))
+        forecast = solver.forecast_scene_pose if pose_dev else solver.forecast_scene      # pose: x, y and heading in one call
+        obs, tv = forecast(x.astype(npdt), a_fc.astype(npdt), rid.astype(np.int32), sol_x.astype(npdt),
+                           sol_u.astype(npdt), (have_sol & (t > 0)).astype(np.int32))
         tv = tv.reshape(E * M, -1)                                      # (read by the gt_mpc cost only: M = 2, [E M, 2])
-        if obca:      # the forecast's x, y with the host predictor's (or the shared plan's) headings: pose [E M, n_obs, 3, N+1]
+        if obca and not pose_dev:      # x, y with the host predictor's (or the shared plan's) headings: pose [E M, n_obs, 3, N+1]
             head = obca_headings(host_pred, x, a_fc, rid, have_sol & (t > 0), sol_x, sol_u, absh)
             obs = np.concatenate([obs, gather_opponents(head)[:, :, None, :].astype(npdt)], axis=2)
         # --- solve every (episode, agent) problem at once (evaluate.py:470-482); an agent that solved the previous
@@ -315,14 +326,16 @@ def shift_controls(u):
 
 
 def _loop_device(solver, stepper, x, u_prev, kp, flags, rid, enc, gt, E, M, N, M_sim, device, warm, graph=False,
-                 a_min_policy=A_MIN_POLICY, constant_speed=False, fused=False):
+                 a_min_policy=A_MIN_POLICY, constant_speed=False, fused=False, obca=False):
     """The same time loop with every array resident in HBM (float64 state, solver-dtype views per call).
     graph=True: steps 0 and 1 run eagerly, then ONE step -- forecast, solve, fallback step and the ~40 small tensor
     operations between them -- is captured in a stream graph and replayed for the remaining steps (the state lives in
     fixed buffers that the captured step updates in place; the column of x_data / u_data it writes is a device-side
     counter).  The loop is launch-bound at a few hundred problems per step; the replay removes the launches.
     fused=True (run_closed_loop step='fused'): the tensor operations behind the solve and the stepper's model step are one
-    launch of igt_loop_advance_* on the solver's handle; `stepper` is not used."""
+    launch of igt_loop_advance_* on the solver's handle; `stepper` is not used.
+    obca=True (run_closed_loop ca_type='obca', pose_forecast='device'): the forecast is the pose forecast and the solve the
+    rectangle solve, both on device tensors; everything else is the same step."""
     import torch
     dev = torch.device('cuda', device)
     td = torch.float32 if solver.dtype == 'f32' else torch.float64
@@ -342,6 +355,12 @@ def _loop_device(solver, stepper, x, u_prev, kp, flags, rid, enc, gt, E, M, N, M
     sol_u = torch.zeros((E, M, 2, N), dtype=td, device=dev)
     col = torch.zeros(1, dtype=torch.int64, device=dev)            # the step the next call of step() computes
     a_fc0 = torch.as_tensor(0.09 * (np.arange(M) + 1.0), device=dev).expand(E, M) if gt else None
+    forecast = solver.forecast_scene_pose if obca else solver.forecast_scene
+    if obca:
+        def solve(x0, up, kpar, fl, obs, tv, en, u_ws=None):
+            return solver.solve_box(x0, up, kpar, fl, obs, tv, en, u_ws=u_ws, length=OBCA_LENGTH, width=OBCA_WIDTH, d_box=0.0)
+    else:
+        solve = solver.solve
 
     def step(first, warm_ok=True):
         # the forecast reads the scene where it lies (igt_forecast_scene_*): no gathered copy of any agent's state or plan
@@ -349,14 +368,14 @@ def _loop_device(solver, stepper, x, u_prev, kp, flags, rid, enc, gt, E, M, N, M
         if constant_speed:
             a_fc = torch.zeros_like(u_prev[..., 0])
         hp = (have_sol & (not first)).to(torch.int32)
-        obs, tv = solver.forecast_scene(x.to(td), a_fc.to(td).contiguous(), rid_t, sol_x, sol_u, hp)
+        obs, tv = forecast(x.to(td), a_fc.to(td).contiguous(), rid_t, sol_x, sol_u, hp)
         tv = tv.reshape(E * M, -1)
         fl, u_ws = flags_t, None
         if warm and not first and warm_ok:
             fl = flags_t | (have_sol.reshape(-1).to(torch.int32) * IGT_FLAG_WARM)
             u_ws = shift_controls(sol_u).reshape(E * M, 2, N).contiguous()
-        out = solver.solve(x.reshape(E * M, 7).to(td).contiguous(), u_prev.reshape(E * M, 2).to(td).contiguous(), kp_s,
-                           fl, obs, tv if gt else None, enc_t, u_ws=u_ws)
+        out = solve(x.reshape(E * M, 7).to(td).contiguous(), u_prev.reshape(E * M, 2).to(td).contiguous(), kp_s,
+                    fl, obs, tv if gt else None, enc_t, u_ws=u_ws)
         ok = (out['status'] == 0).reshape(E, M)
         xs = out['x'].reshape(E, M, 7, N + 1)
         us = out['u'].reshape(E, M, 2, N)
@@ -398,13 +417,13 @@ def _loop_device(solver, stepper, x, u_prev, kp, flags, rid, enc, gt, E, M, N, M
             a_fc = a_fc0 if (gt and first) else u_prev[..., 0]
             if constant_speed:
                 a_fc = torch.zeros_like(u_prev[..., 0])
-            obs, tv = solver.forecast_scene(x.to(td), a_fc.to(td).contiguous(), rid_t, sol_x, sol_u, have_i)
+            obs, tv = forecast(x.to(td), a_fc.to(td).contiguous(), rid_t, sol_x, sol_u, have_i)
             tv = tv.reshape(E * M, -1)
             fl, u_ws = flags_t, None
             if warm and not first and warm_ok:
                 fl, u_ws = adv['flags'], adv['u_ws']                     # the previous step's loop_advance left both
-            out = solver.solve(x_n.to(td).contiguous(), u_n.to(td).contiguous(), kp_s, fl, obs, tv if gt else None, enc_t,
-                               u_ws=u_ws)
+            out = solve(x_n.to(td).contiguous(), u_n.to(td).contiguous(), kp_s, fl, obs, tv if gt else None, enc_t,
+                        u_ws=u_ws)
             solver.loop_advance(x_n, u_n, kp_d, out['status'], out['x'], out['u'], a_min_policy, flags=flags_t,
                                 infeasible=infeasible_n, x_log=x_log, u_log=u_log, step=col, out=adv)
             col.add_(1)
@@ -559,7 +578,7 @@ def save_results(r, save_dir, eval_mode, sc, seed=2026, policy=None, timenow=Non
     return run
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description='batched closed-loop evaluation (counterpart of evaluate.py --eval_mode mpc)')
     ap.add_argument('--sc', type=int, default=1)
     ap.add_argument('--num_samples', type=int, default=1)
@@ -574,7 +593,11 @@ def main():
     ap.add_argument('--net_prefix', default='', help="key prefix inside the npz, e.g. 'sc1_'")
     ap.add_argument('--verbose', action='store_true')
     ap.add_argument('--ca_type', default='circle', choices=['circle', 'obca'],
-                    help="collision model: 'circle' (mpc.yaml:16) or 'obca', 4.47 x 2.0 m rectangles with d_min = 0 (host loop only)")
+                    help="collision model: 'circle' (mpc.yaml:16) or 'obca', 4.47 x 2.0 m rectangles with d_min = 0 (the host loop "
+                         "only, unless --pose_forecast device)")
+    ap.add_argument('--pose_forecast', default='host', choices=['host', 'device'],
+                    help="with --ca_type obca: the obstacles' headings from the host predictor (default) or the whole pose from the "
+                         "device (igt_forecast_scene_pose_f64), which also runs with --device_resident, --graph and --step fused")
     ap.add_argument('--device_resident', action='store_true', help='keep all per-step arrays in HBM (torch tensors)')
     ap.add_argument('--graph', action='store_true', help='with --device_resident: capture one step in a stream graph and replay it')
     ap.add_argument('--step', default='torch', choices=['torch', 'fused'],
@@ -593,7 +616,11 @@ def main():
                     help='step of the polish: along the gradient, or half of the trials along the Gauss-Newton (LQ) direction')
     ap.add_argument('--save_dir', default=None, help='write the run directory the reference\'s driver writes (cl_traj.pkl, u_cl.pkl, '
                     'stats csv, mpc.yaml; evaluate.py:646) under <save_dir><eval_mode>_sc<sc>_seed2026_<time>/')
-    a = ap.parse_args()
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     net = None
     if a.eval_mode == 'gt_mpc':
         if a.value_net:
@@ -612,7 +639,7 @@ def main():
                         value_net=net, device_resident=a.device_resident, cand_mode=a.cand_mode, dtype=a.dtype, graph=a.graph,
                         polish_iters=a.polish_iters, polish_grad=a.polish_grad, polish_step=a.polish_step,
                         value_polish_iters=a.value_polish_iters, value_polish_driver=a.value_polish_driver,
-                        num_agents=a.num_agents, step=a.step, ca_type=a.ca_type,
+                        num_agents=a.num_agents, step=a.step, ca_type=a.ca_type, pose_forecast=a.pose_forecast,
                         **kw)
     if a.save_dir is not None:
         policy = {'type': 'MPC', 'N': a.N, 'dt': kw.get('dt', 0.1), 'a_min': -4, 'a_max': 3, 'v_min': -1.0, 'v_max': 5,      # mpc.yaml's keys

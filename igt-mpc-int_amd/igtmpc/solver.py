@@ -97,6 +97,8 @@ class BatchSolver:
         self._fcast = getattr(self.lib, f'igt_forecast_batch_{dtype}')
         self._fscene = getattr(self.lib, f'igt_forecast_scene_{dtype}')
         self._routes_set = False
+        self._headings_set = False      # igt_set_route_headings, set lazily by the pose forecasts
+        self._n_routes = 0
         if polish_grad != 'fd':      # the default needs no call: a library from before the setter still serves it
             self._check(self.lib.igt_set_polish_gradient(self._h, L.IGT_GRAD_ADJOINT))
         if polish_step != 'gradient':      # likewise
@@ -630,6 +632,9 @@ class BatchSolver:
             raise ValueError('route table must be [n_routes, 12]')
         self._check(self.lib.igt_set_routes(self._h, len(table), table.ctypes.data))
         self._routes_set = True
+        if len(table) != self._n_routes:      # the library drops the headings of a table of another length
+            self._headings_set = False
+        self._n_routes = len(table)
 
     def forecast(self, ego_xyh, opp, opp_a, opp_route, plan_x=None, plan_u=None, has_plan=None, stream=None):
         """Opponent forecast + V2V sharing + filter_preds on the device (constant_acceleration_model.py:18-82,
@@ -677,6 +682,82 @@ class BatchSolver:
         dts = [dt, dt, np.int32, dt, dt, np.int32, dt, dt]
         mode, ptrs, keep = self._prep(arrs, shapes, dts)
         self._check(self._fscene(self._h, E, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        return obs, tv
+
+    # ------------------------------------------------------------------ pose forecast (x, y, heading: what solve_box reads)
+    def set_route_headings(self, table=None):
+        """Route headings for forecast_scene_pose() / forecast_pose() (igtmpc.h igt_set_route_headings): table[n_routes,3] =
+        (h0, hN, abs) per route of the set_routes table; default: those of igtmpc.routes.  The route table is set first if it is
+        not yet."""
+        self._check_pose('set_route_headings')
+        if not self._routes_set:
+            self.set_routes()
+        if table is None:
+            from . import routes as R
+            T = R.TABLES
+            table = np.column_stack([T['h0'], T['hN'], T['abs_heading'].astype(np.float64)])
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 2 or table.shape[1] != 3:
+            raise ValueError('route heading table must be [n_routes, 3]')
+        self._check(self._entry('igt_set_route_headings')(self._h, len(table), table.ctypes.data))
+        self._headings_set = True
+
+    def _check_pose(self, what):
+        """What the pose entries refuse before any library call."""
+        if self.dtype != 'f64':
+            raise ValueError(f"{what} needs dtype='f64' (the pose is read by solve_box, which has no float32 entry)")
+
+    def forecast_scene_pose(self, x, a_prev, route, plan_x=None, plan_u=None, has_plan=None, stream=None):
+        """forecast_scene() with the obstacles' headings (igtmpc.h igt_forecast_scene_pose_f64): the same arguments
+        -> (obs_pose[E M,n_obs,3,N+1], tv_sv[E M,n_obs,2]).  Rows 0, 1 and tv_sv are forecast_scene()'s, bit for bit; row 2 is
+        every other agent's heading along its forecast (node 0: its true heading x[e,j,6]; then the route's reference heading at
+        the forecast's arc length) or along the plan it shares (plan_x[e,j,6,1:], then the route heading one predicted step behind
+        the plan's end), |heading| on the routes that read it so -- not filtered: an agent behind the ego keeps its heading row.
+        float64 solvers; numpy arrays or tensors on the solver's GPU -- with tensors the call only enqueues and can be captured."""
+        self._check_pose('forecast_scene_pose')
+        if not self._headings_set:
+            self.set_route_headings()
+        fn = self._entry('igt_forecast_scene_pose_f64')
+        E, N, M = int(x.shape[0]), self.N, self.n_obs + 1
+        dt = self.np_dtype
+        if _is_torch(x):
+            import torch
+            obs = torch.empty((E * M, M - 1, 3, N + 1), dtype=x.dtype, device=x.device)
+            tv = torch.empty((E * M, M - 1, 2), dtype=x.dtype, device=x.device)
+        else:
+            obs, tv = np.empty((E * M, M - 1, 3, N + 1), dt), np.empty((E * M, M - 1, 2), dt)
+        arrs = [x, a_prev, route, plan_x, plan_u, has_plan, obs, tv]
+        shapes = [(E, M, 7), (E, M), (E, M), (E, M, 7, N + 1), (E, M, 2, N), (E, M), tuple(obs.shape), tuple(tv.shape)]
+        dts = [dt, dt, np.int32, dt, dt, np.int32, dt, dt]
+        mode, ptrs, keep = self._prep(arrs, shapes, dts)
+        self._check(fn(self._h, E, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        return obs, tv
+
+    def forecast_pose(self, ego_xyh, opp, opp_a, opp_route, opp_heading, plan_x=None, plan_u=None, has_plan=None, stream=None):
+        """forecast() with the obstacles' headings, per gathered problem (igtmpc.h igt_forecast_batch_pose_f64): forecast()'s
+        arguments plus opp_heading[B] ([B,n_obs] for n_obs > 1), every opponent's true heading
+        -> (obs_pose[B,n_obs,3,N+1], tv_sv[B,2] or [B,n_obs,2]).  forecast_scene_pose() equals it on the gathered inputs bit for
+        bit."""
+        self._check_pose('forecast_pose')
+        if not self._headings_set:
+            self.set_route_headings()
+        fn = self._entry('igt_forecast_batch_pose_f64')
+        B, N, M1 = int(ego_xyh.shape[0]), self.N, self.n_obs
+        dt = self.np_dtype
+        tv_shape = (B, 2) if M1 == 1 else (B, M1, 2)
+        if _is_torch(ego_xyh):
+            import torch
+            obs = torch.empty((B, M1, 3, N + 1), dtype=ego_xyh.dtype, device=ego_xyh.device)
+            tv = torch.empty(tv_shape, dtype=ego_xyh.dtype, device=ego_xyh.device)
+        else:
+            obs, tv = np.empty((B, M1, 3, N + 1), dt), np.empty(tv_shape, dt)
+        ax = () if M1 == 1 else (M1,)
+        arrs = [ego_xyh, opp, opp_a, opp_route, opp_heading, plan_x, plan_u, has_plan, obs, tv]
+        shapes = [(B, 3), (B, *ax, 4), (B, *ax), (B, *ax), (B, *ax), (B, *ax, 7, N + 1), (B, *ax, 2, N), (B, *ax),
+                  (B, M1, 3, N + 1), tv_shape]
+        dts = [dt, dt, dt, np.int32, dt, dt, dt, np.int32, dt, dt]
+        mode, ptrs, keep = self._prep(arrs, shapes, dts)
+        self._check(fn(self._h, B, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
         return obs, tv
 
     def frenet_step(self, x, u, kparams, stream=None):

@@ -311,6 +311,39 @@ int igt_forecast_scene_f64(igt_handle* h, int32_t E, const double* x, const doub
                            const double* plan_x, const double* plan_u, const int32_t* has_plan, double* obs_xy, double* tv_sv,
                            int mem, void* stream);
 
+/* ---- pose forecast: the obstacles' x, y AND heading, what igt_solve_batch_box_f64 reads ------------------------------
+ * Route headings for the pose entries below, a table of its own beside igt_set_routes (whose 12-double layout does not move):
+ * n_routes x 3 doubles per route, (h0, hN, abs) = the heading before the arc, the heading after it, and whether this route's
+ * headings are read as |heading| (non-zero: routes '32' and '41', mpc.py:250-253).  IGT_E_INVALID, with a message that names
+ * the cause, for a null handle or table, a handle without routes, n_routes different from the igt_set_routes table's, a
+ * non-finite h0 / hN.  A later igt_set_routes with another n_routes drops the headings. */
+int igt_set_route_headings(igt_handle* h, int32_t n_routes, const double* table);
+
+/* igt_forecast_scene_f64 with obs_pose [E M,n_obs,3,N+1] in place of obs_xy.  Rows 0 and 1 (x, y) and tv_sv are what
+ * igt_forecast_scene_f64 writes for the same inputs, bit for bit ((-20, -20) behind an ego included).  Row 2 is the heading of
+ * agent j's forecast as the reference's 'obca' ego reads it (utils.py:339-352, constant_acceleration_model.py:46-74); with s_k
+ * the forecast's own arc length at node k:
+ *   no shared plan   node 0: the true heading x[e,j,6]; node k >= 1: psi_ref(route, s_k);
+ *   shared plan      node k < N: plan_x[e,j,6,k+1]; node N: psi_ref(route, s_ext), s_ext one predicted step behind the plan's
+ *                    end (with the retry a = 0 above v = 5, as for x, y);
+ *   psi_ref(r, s)    h0 on a straight route, else h0 + w (hN - h0), w = (s - b0) / (b1 - b0) clamped to [0, 1];
+ *   abs flag set     the absolute value of all of the above.
+ * The heading is NOT filtered: an agent behind an ego keeps its heading row while its x, y become -20.  Where s is not finite, x
+ * and y are not finite either (the box verdict drops such a node) and the heading there is unspecified.
+ * IGT_MEM_DEVICE: one kernel enqueued on `stream`, no allocation, no host synchronisation (capturable).  IGT_E_INVALID where
+ * igt_forecast_scene_f64 says so, and for a handle without igt_set_route_headings.  _f64 only: the box solve has no float32
+ * entry.  (Added without a change of IGT_VERSION; callers probe the symbols.) */
+int igt_forecast_scene_pose_f64(igt_handle* h, int32_t E, const double* x, const double* a_prev, const int32_t* route,
+                                const double* plan_x, const double* plan_u, const int32_t* has_plan, double* obs_pose,
+                                double* tv_sv, int mem, void* stream);
+
+/* The per-problem counterpart: igt_forecast_batch_f64 plus opp_heading [B,n_obs], every opponent's true heading (node 0 without a
+ * shared plan), and obs_pose [B,n_obs,3,N+1] in place of obs_xy.  Same rules; igt_forecast_scene_pose_f64 equals this entry on
+ * the gathered inputs bit for bit. */
+int igt_forecast_batch_pose_f64(igt_handle* h, int32_t B, const double* ego_xyh, const double* opp, const double* opp_a,
+                                const int32_t* opp_route, const double* opp_heading, const double* plan_x, const double* plan_u,
+                                const int32_t* has_plan, double* obs_pose, double* tv_sv, int mem, void* stream);
+
 /* 4-state Cartesian forward-Euler bicycle (kinematic_bicycle_model.py:15-50), the
  * model ReferenceGen.py steps to lay out reference paths.
  *   z0 [n,4] = (x, y, psi, v)   u [n,2,T] (a, df)   z_out [n,4,T+1] */
@@ -514,9 +547,9 @@ int igt_rollout_candidates_f64(igt_handle* h, int32_t B, const double* x0, const
  * IGT_E_INVALID, with a message that names the cause, for a null handle, B < 0, a length or width that is not finite and
  * positive, a d_box that is not finite or below 0, a handle with polish_iters > 0 or igt_set_value_polish > 0 (the polish
  * kernels judge their trial plans with the circle) and with the developer kernels of IGT_DEV_FLAGS 32 / 1024 / 2048; B = 0 is a
- * no-op.  Out of scope, each refused or simply absent: _f32 entries, the two polishes, per-scenario candidate sets, a device
- * forecast of headings, the device-resident closed loop, the pooled search (a box solve runs every 64-candidate unit on a plain
- * grid).  (Added without a change of IGT_VERSION; callers probe the symbols.) */
+ * no-op.  Out of scope, each refused or simply absent: _f32 entries, the two polishes, per-scenario candidate sets, the
+ * pooled search (a box solve runs every 64-candidate unit on a plain grid).  obs_pose comes from igt_forecast_scene_pose_f64 /
+ * igt_forecast_batch_pose_f64 above.  (Added without a change of IGT_VERSION; callers probe the symbols.) */
 int igt_solve_batch_box_f64(igt_handle* h, int32_t B, const double* x0, const double* u_prev, const double* kparams,
                             const uint32_t* flags, const double* obs_pose, const double* tv_sv, const double* enc,
                             const double* u_ws, double length, double width, double d_box, double* x_out, double* u_out,
