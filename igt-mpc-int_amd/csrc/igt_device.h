@@ -456,7 +456,19 @@ __device__ __forceinline__ bool obstacles_out_of_reach(const KP& P, const Scenar
     return !__any(near);
 }
 
-
+// The winner rule, (J, c) lexicographic: the lower cost wins, of two equal costs the lower candidate index -- whatever order the
+// lanes, units or partials are visited in.  c < 0: no feasible candidate.  (igt_kernels_common.h best_partial: over the partials.)
+__device__ __forceinline__ bool beats(double oJ, int oC, double J, int c) {
+    return (oC >= 0) && (c < 0 || oJ < J || (oJ == J && oC < c));
+}
+__device__ __forceinline__ void wave_argmin(double& J, int& c) {      // the best (J, c) of a wave's 64 lanes, left on every lane
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double oJ = __shfl_xor(J, off, 64);
+        const int oC = __shfl_xor(c, off, 64);
+        if (beats(oJ, oC, J, c)) { J = oJ; c = oC; }
+    }
+}
 
 // ---- the incumbent bound of the tracking family's search (igt_fast64.h rollout_one has the derivation) ----
 constexpr unsigned VIOL_PRUNED = 128u;            // internal to the search pass: never reported

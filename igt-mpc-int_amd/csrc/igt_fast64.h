@@ -1015,7 +1015,7 @@ __device__ __forceinline__ void rollout_pool(const KP& P, const Scenario<double>
             for (int off = 32; off >= 1; off >>= 1) {
                 const double oJ = __shfl_xor(bJ, off, 64);
                 const int oC = __shfl_xor(bC, off, 64);
-                const bool take = (oC >= 0) && (bC < 0 || oJ < bJ || (oJ == bJ && oC < bC));
+                const bool take = (oC >= 0) && (bC < 0 || oJ < bJ || (oJ == bJ && oC < bC));      // wave_argmin (igt_device.h) written out
                 if (take) { bJ = oJ; bC = oC; }
             }
             bJ = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(bJ)), __builtin_amdgcn_readfirstlane(__double2loint(bJ)));

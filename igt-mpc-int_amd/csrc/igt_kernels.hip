@@ -15,8 +15,7 @@
 
 namespace igt {
 
-// partials [B, W] -> cost / argmin / status.  (J, c) is compared lexicographically: steering-ordered slices hold their
-// columns from the centre outwards, so a later slice can hold the LOWER candidate index of an exact tie
+// partials [B, W] -> cost / argmin / status (igt_kernels_common.h best_partial)
 template <typename T>
 __global__ __launch_bounds__(256) void reduce_partials_kernel(int B, int W, const double* __restrict__ part_J,
                                                               const int32_t* __restrict__ part_c,
@@ -24,16 +23,8 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(int B, int W, cons
                                                               int32_t* __restrict__ status_out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    double bestJ = 0.0;
-    int c = -1;
-    for (int w = 0; w < W; ++w) {
-        const int cw = part_c[(size_t)b * W + w];
-        const double Jw = part_J[(size_t)b * W + w];
-        if (cw >= 0 && (c < 0 || Jw < bestJ || (Jw == bestJ && cw < c))) { bestJ = Jw; c = cw; }
-    }
-    cost_out[b] = c >= 0 ? (T)bestJ : (T)INFINITY;
-    argmin_out[b] = c;
-    status_out[b] = c >= 0 ? 0 : 1;
+    const Winner win = best_partial(part_J, part_c, b, W);
+    write_verdict<T>(b, win.J, win.c, cost_out, argmin_out, status_out);
 }
 
 // Ramp-hold refinement: new centre OFFSET (relative to the base sequence: u_prev held, or the warm start) = the winner's
@@ -51,13 +42,7 @@ __global__ __launch_bounds__(256) void refine_targets_kernel(KP P, int B, int W,
     } else {
         ca = cpar[(size_t)b * 4 + 0]; cd = cpar[(size_t)b * 4 + 1]; sa = cpar[(size_t)b * 4 + 2]; sd = cpar[(size_t)b * 4 + 3];
     }
-    double bestJ = 0.0;
-    int c = -1;
-    for (int w = 0; w < W; ++w) {
-        const int cw = part_c[(size_t)b * W + w];
-        const double Jw = part_J[(size_t)b * W + w];
-        if (cw >= 0 && (c < 0 || Jw < bestJ || (Jw == bestJ && cw < c))) { bestJ = Jw; c = cw; }
-    }
+    const int c = best_partial(part_J, part_c, b, W).c;
     if (c >= 0) {
         const int G = P.G, i = c / G, j = c - i * G;
         const int ilo = i > 0 ? i - 1 : i, ihi = i < G - 1 ? i + 1 : i;
@@ -219,7 +204,7 @@ __device__ __forceinline__ void search_unit(const KP& P, int W, int b, int p, do
         if (ok && (bestC < 0 || Jq < bestJ || (Jq == bestJ && cidx[q] < bestC))) { bestJ = Jq; bestC = cidx[q]; }
     }
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
+    for (int off = 32; off >= 1; off >>= 1) {      // wave_argmin (igt_device.h) written out: it must agree with it
         const double oJ = __shfl_xor(bestJ, off, 64);
         const int oC = __shfl_xor(bestC, off, 64);
         const bool take = (oC >= 0) && (bestC < 0 || oJ < bestJ || (oJ == bestJ && oC < bestC));
@@ -289,7 +274,7 @@ __global__ __launch_bounds__(64) void emit_fast_kernel(KP P, int B, int W, const
                                                        float* __restrict__ u_out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    // final arg-min over the W slices, (J, c) lexicographic: ties -> lowest candidate index whatever the slice order
+    // final arg-min over the W slices: best_partial (igt_kernels_common.h) written out, it must agree with it
     double bestJ = 0.0;
     int c = -1;
     for (int w = 0; w < W; ++w) {
@@ -298,16 +283,10 @@ __global__ __launch_bounds__(64) void emit_fast_kernel(KP P, int B, int W, const
         if (cw >= 0 && (c < 0 || Jw < bestJ || (Jw == bestJ && cw < c))) { bestJ = Jw; c = cw; }
     }
     if (c >= 0 && inputs_refused<float>(P, b, x0, u_prev, flags, cpar)) c = -1;
-    cost_out[b] = c >= 0 ? (float)bestJ : INFINITY;
-    argmin_out[b] = c;
-    status_out[b] = c >= 0 ? 0 : 1;
+    write_verdict<float>(b, bestJ, c, cost_out, argmin_out, status_out);
     float* xo = x_out + (size_t)b * 7 * (P.N + 1);
     float* uo = u_out + (size_t)b * 2 * P.N;
-    if (c < 0) {  // is_opt False (mpc.py:402-406): no trajectory
-        for (int i = 0; i < 7 * (P.N + 1); ++i) xo[i] = NAN;
-        for (int i = 0; i < 2 * P.N; ++i) uo[i] = NAN;
-        return;
-    }
+    if (c < 0) { no_trajectory<float>(P, xo, uo); return; }
     Scenario<float> S;
     load_scenario<float>(S, P, b, x0, u_prev, kparams, flags, obs, cpar);
     // one candidate per lane (the unpacked build of the same arithmetic: a lone roll-out is latency, and half of
@@ -339,24 +318,13 @@ __global__ __launch_bounds__(64) void emit_seg_kernel(KP P, int B, int W, int Wk
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int b = t / parts, g = t - b * parts;
     if (b >= B) return;
-    double bestJ = 0.0;
-    int c = -1;
-    for (int w = 0; w < W; ++w) {
-        const int cw = part_c[(size_t)b * W + w];
-        const double Jw = part_J[(size_t)b * W + w];
-        if (cw >= 0 && (c < 0 || Jw < bestJ || (Jw == bestJ && cw < c))) { bestJ = Jw; c = cw; }
-    }
-    if (c >= 0 && inputs_refused<float>(P, b, x0, u_prev, flags, cpar)) c = -1;
+    const Winner win = best_partial(part_J, part_c, b, W);
+    const int c = (win.c >= 0 && inputs_refused<float>(P, b, x0, u_prev, flags, cpar)) ? -1 : win.c;
     float* xo = x_out + (size_t)b * 7 * (P.N + 1);
     float* uo = u_out + (size_t)b * 2 * P.N;
     if (g == 0) {
-        cost_out[b] = c >= 0 ? (float)bestJ : INFINITY;
-        argmin_out[b] = c;
-        status_out[b] = c >= 0 ? 0 : 1;
-        if (c < 0) {  // is_opt False (mpc.py:402-406): no trajectory
-            for (int i = 0; i < 7 * (P.N + 1); ++i) xo[i] = NAN;
-            for (int i = 0; i < 2 * P.N; ++i) uo[i] = NAN;
-        }
+        write_verdict<float>(b, win.J, c, cost_out, argmin_out, status_out);
+        if (c < 0) no_trajectory<float>(P, xo, uo);
     }
     if (c < 0) return;
     Scenario<float> S;

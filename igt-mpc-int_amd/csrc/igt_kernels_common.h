@@ -71,6 +71,35 @@ __device__ __forceinline__ bool inputs_refused(const KP& P, int b, const T* __re
     return bad;
 }
 
+// The best (J, c) a scenario's W units left and the unit w that held it, by the winner rule (igt_device.h beats): steering-ordered
+// units hold their columns from the centre outwards, so a later unit can hold the LOWER index of an exact tie.  c < 0: none.
+struct Winner { double J; int c, w; };
+__device__ __forceinline__ Winner best_partial(const double* __restrict__ part_J, const int32_t* __restrict__ part_c, int b, int W) {
+    Winner r{0.0, -1, 0};
+    for (int w = 0; w < W; ++w) {
+        const int cw = part_c[(size_t)b * W + w];
+        const double Jw = part_J[(size_t)b * W + w];
+        if (beats(Jw, cw, r.J, r.c)) { r.J = Jw; r.c = cw; r.w = w; }
+    }
+    return r;
+}
+template <typename T>      // what the solve answers for scenario b beside the trajectory (status 1: nothing feasible, or refused)
+__device__ __forceinline__ void write_verdict(int b, double J, int c, T* __restrict__ cost_out, int32_t* __restrict__ argmin_out,
+                                              int32_t* __restrict__ status_out) {
+    cost_out[b] = c >= 0 ? (T)J : (T)INFINITY;
+    argmin_out[b] = c;
+    status_out[b] = c >= 0 ? 0 : 1;
+}
+template <typename T>      // is_opt False (mpc.py:402-406): no trajectory -- NaN rows, written by one lane
+__device__ __forceinline__ void no_trajectory(const KP& P, T* __restrict__ xo, T* __restrict__ uo) {
+    for (int i = 0; i < 7 * (P.N + 1); ++i) xo[i] = (T)NAN;
+    for (int i = 0; i < 2 * P.N; ++i) uo[i] = (T)NAN;
+}
+// the candidate table scenario b rolls from: the shared one, or (own: per-scenario candidate sets, `table` is U[B,C,2,N]) its own
+__device__ __forceinline__ const double* scenario_table(const KP& P, const double* __restrict__ table, int b, bool own) {
+    return own ? table + (size_t)b * cand_table_doubles(P.C, P.N) : table;
+}
+
 template <typename T>
 struct StoreSink {
     static constexpr bool kKeepsStates = true;

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void search_kernel(KP P, int B, const T* __res
             if (ok && (bestC < 0 || Jq < bestJ)) { bestJ = Jq; bestC = cidx[q]; }
         }
     }
-    // wave butterfly arg-min, ties -> lowest candidate index
+    // wave butterfly arg-min, ties -> lowest candidate index: wave_argmin (igt_device.h) written out, it must agree with it
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
         const double oJ = __shfl_xor(bestJ, off, 64);
@@ -78,11 +78,7 @@ __global__ __launch_bounds__(256) void search_kernel(KP P, int B, const T* __res
         if (take) { bestJ = oJ; bestC = oC; }
     }
     if (VALUE) return;
-    if (lane == 0) {
-        cost_out[b] = bestC >= 0 ? (T)bestJ : (T)INFINITY;
-        argmin_out[b] = bestC;
-        status_out[b] = bestC >= 0 ? 0 : 1;
-    }
+    if (lane == 0) write_verdict<T>(b, bestJ, bestC, cost_out, argmin_out, status_out);
 }
 
 template <class Stepper, typename T>
@@ -98,12 +94,7 @@ __global__ __launch_bounds__(64) void emit_kernel(KP P, int B, const T* __restri
     T* xo = x_out + (size_t)b * 7 * (P.N + 1);
     T* uo = u_out + (size_t)b * 2 * P.N;
     const int c = argmin[b];
-    if (c < 0) {  // is_opt False (mpc.py:402-406): no trajectory
-        const T nan = (T)NAN;
-        for (int i = 0; i < 7 * (P.N + 1); ++i) xo[i] = nan;
-        for (int i = 0; i < 2 * P.N; ++i) uo[i] = nan;
-        return;
-    }
+    if (c < 0) { no_trajectory<T>(P, xo, uo); return; }
     Scenario<T> S;
     load_scenario<T>(S, P, b, x0, u_prev, kparams, flags, obs, cpar);
     StoreSink<T> sink{xo, uo, P.N};
@@ -406,7 +397,7 @@ __device__ __forceinline__ void search_unit64(const KP& P, int W, int b, int p, 
     double bestJ = Jq;
     int bestC = ((viol == 0) && finite_d(Jq)) ? c : -1;
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {                   // wave butterfly arg-min, ties -> lowest candidate index
+    for (int off = 32; off >= 1; off >>= 1) {                   // wave_argmin (igt_device.h) written out: it must agree with it
         const double oJ = __shfl_xor(bestJ, off, 64);
         const int oC = __shfl_xor(bestC, off, 64);
         const bool take = (oC >= 0) && (bestC < 0 || oJ < bestJ || (oJ == bestJ && oC < bestC));
@@ -599,13 +590,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const double Jq = J - (sN - S.x0[2]);                       // mpc.py:372
     double bestJ = Jq;
     int bestC = ((viol == 0) && finite_d(Jq)) ? c : -1;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {                   // wave butterfly arg-min, ties -> lowest candidate index
-        const double oJ = __shfl_xor(bestJ, off, 64);
-        const int oC = __shfl_xor(bestC, off, 64);
-        const bool take = (oC >= 0) && (bestC < 0 || oJ < bestJ || (oJ == bestJ && oC < bestC));
-        if (take) { bestJ = oJ; bestC = oC; }
-    }
+    wave_argmin(bestJ, bestC);
     if (lane == 0) { part_J[b * W + p] = bestJ; part_c[b * W + p] = bestC; }
 }
 // Direct (horizons whose slab does not fit; the value-network cost, whose units leave records): search_unit64 itself, its
@@ -614,7 +599,7 @@ template <bool HI, bool VALUE, int NRK>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_cand_direct_f64_kernel(IGT_SEARCH64_ARGS) {
     const int b = (int)(blockIdx.x / (unsigned)W), p = (int)(blockIdx.x % (unsigned)W);
     if (b >= B) return;
-    search_unit64<CAND_TABLE, HI, VALUE, NRK>(P, W, b, p, x0, u_prev, kparams, flags, obs, table + (size_t)b * cand_table_doubles(P.C, P.N),
+    search_unit64<CAND_TABLE, HI, VALUE, NRK>(P, W, b, p, x0, u_prev, kparams, flags, obs, scenario_table(P, table, b, true),
                                               cinf, cpar, part_J, part_c, rec_sN, rec_vN, rec_J, rec_viol, rec_count, rec_b, unit_seg);
 }
 // ---- the rectangle (OBCA) collision model (igt_solve_batch_box_f64; igt_launch.h plan_box64) ----
@@ -643,7 +628,7 @@ __global__ __launch_bounds__(64) void emit_gather_f64_kernel(KP P, int B, int W,
     const int b = blockIdx.x, lane = threadIdx.x;
     double bestJ = 0.0;
     int c = -1, pw = 0;
-    for (int w = 0; w < W; ++w) {      // (J, c) lexicographic, as emit_f64_kernel
+    for (int w = 0; w < W; ++w) {      // best_partial (igt_kernels_common.h) written out: it must agree with it
         const int cw = part_c[(size_t)b * W + w];
         const double Jw = part_J[(size_t)b * W + w];
         if (cw >= 0 && (c < 0 || Jw < bestJ || (Jw == bestJ && cw < c))) { bestJ = Jw; c = cw; pw = w; }
@@ -700,29 +685,22 @@ __global__ __launch_bounds__(64) void emit_f64_kernel(KP P, int B, int W, const 
     if (b >= B) return;
     double bestJ = 0.0;
     int c = -1;
-    for (int w = 0; w < W; ++w) {      // (J, c) lexicographic: ties -> lowest candidate index whatever the slice order
+    for (int w = 0; w < W; ++w) {      // best_partial (igt_kernels_common.h) written out: it must agree with it
         const int cw = part_c[(size_t)b * W + w];
         const double Jw = part_J[(size_t)b * W + w];
         if (cw >= 0 && (c < 0 || Jw < bestJ || (Jw == bestJ && cw < c))) { bestJ = Jw; c = cw; }
     }
     if (c >= 0 && inputs_refused<double>(P, b, x0, u_prev, flags, cpar)) c = -1;
-    cost_out[b] = c >= 0 ? bestJ : (double)INFINITY;
-    argmin_out[b] = c;
-    status_out[b] = c >= 0 ? 0 : 1;
+    write_verdict<double>(b, bestJ, c, cost_out, argmin_out, status_out);
     double* xo = x_out + (size_t)b * 7 * (P.N + 1);
     double* uo = u_out + (size_t)b * 2 * P.N;
-    if (c < 0) {  // is_opt False (mpc.py:402-406): no trajectory
-        for (int i = 0; i < 7 * (P.N + 1); ++i) xo[i] = (double)NAN;
-        for (int i = 0; i < 2 * P.N; ++i) uo[i] = (double)NAN;
-        return;
-    }
+    if (c < 0) { no_trajectory<double>(P, xo, uo); return; }
     Scenario<double> S;
     load_scenario<double>(S, P, b, x0, u_prev, kparams, flags, obs, cpar);
     StoreSink<double> sink{xo, uo, P.N};
     double J, sN, vN;
     unsigned viol;
-    f64::rollout_one<CAND, HI, ROLL_EMIT, NRK>(P, S, c, OWN ? table + (size_t)b * cand_table_doubles(P.C, P.N) : table, cinf, sink, J, viol,
-                                               sN, vN);
+    f64::rollout_one<CAND, HI, ROLL_EMIT, NRK>(P, S, c, scenario_table(P, table, b, OWN), cinf, sink, J, viol, sN, vN);
 }
 
 // ---- emit in pieces (batches that do not keep trajectories; progress cost) ----
@@ -775,16 +753,14 @@ __global__ __launch_bounds__(SEG_THREADS) void emit_seg_f64_kernel(KP P, int B, 
     double bestJ = 0.0;
     int c = -1, pw = 0;
     if (active) {
-        for (int w = 0; w < W; ++w) {      // (J, c) lexicographic: ties -> lowest candidate index whatever the slice order
+        for (int w = 0; w < W; ++w) {      // best_partial (igt_kernels_common.h) written out: it must agree with it
             const int cw = part_c[(size_t)b * W + w];
             const double Jw = part_J[(size_t)b * W + w];
             if (cw >= 0 && (c < 0 || Jw < bestJ || (Jw == bestJ && cw < c))) { bestJ = Jw; c = cw; pw = w; }
         }
         if (c >= 0 && inputs_refused<double>(P, b, x0, u_prev, flags, cpar)) c = -1;
         if (wave == 0) {
-            cost_out[b] = c >= 0 ? bestJ : (double)INFINITY;
-            argmin_out[b] = c;
-            status_out[b] = c >= 0 ? 0 : 1;
+            write_verdict<double>(b, bestJ, c, cost_out, argmin_out, status_out);
             win[lane] = c;
         }
     }
@@ -1333,7 +1309,7 @@ __global__ __launch_bounds__(256) void rollout_all_f64_kernel(KP P, int B, const
         StoreSink<double> sink{X_all ? X_all + bc * 7 * (P.N + 1) : nullptr, U_all ? U_all + bc * 2 * P.N : nullptr, P.N};
         double J, sN, vN;
         unsigned viol;
-        f64::rollout_one<CAND, HI, ROLL_ALL>(P, S, c, OWN ? table + (size_t)b * cand_table_doubles(P.C, P.N) : table, cinf, sink, J, viol, sN, vN);
+        f64::rollout_one<CAND, HI, ROLL_ALL>(P, S, c, scenario_table(P, table, b, OWN), cinf, sink, J, viol, sN, vN);
         if (rec_J) {   // value-net cost: value_kernel adds the terminal term and fills cost_all / viol_all
             rec_sN[bc] = sN; rec_vN[bc] = vN; rec_J[bc] = J; rec_viol[bc] = viol;
             continue;
@@ -1741,37 +1717,31 @@ hipError_t launch_cost_gradient_vn(const KP& P, int B, bool leave, const double*
 template <>
 hipError_t launch_rollout_all<double>(const KP& P, int B, const SolveArgs<double>& A, double* X_all, double* U_all,
                                       double* cost_all, uint32_t* viol_all, hipStream_t st) {
-#if IGT_DEV_KERNELS
-    if (P.dev & DEV_EXACT64) {     // developer switch: oracle-order kernels
-        hipLaunchKernelGGL((rollout_all_kernel<ExactStepper<double>, double>), dim3((B + 3) / 4), dim3(256), 0, st, P, B,
-                           A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), X_all, U_all, cost_all, viol_all,
-                           A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol);
+    // the arguments every roll-out of every candidate takes; model: what the rectangle kernel takes between them (A.box)
+    const auto launch = [&](auto kernel, dim3 grid, dim3 block, auto... model) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, P, B, A.x0, A.u_prev, A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(),
+                           model..., X_all, U_all, cost_all, viol_all, A.rec_sN, A.rec_vN, A.rec_J, A.rec_viol);
         return hipGetLastError();
-    }
+    };
+    const dim3 grid4((B + 3) / 4), block4(256);      // four scenarios per workgroup, a wave each
+#if IGT_DEV_KERNELS
+    if (P.dev & DEV_EXACT64)      // developer switch: oracle-order kernels
+        return launch(rollout_all_kernel<ExactStepper<double>, double>, grid4, block4);
 #endif
     if (A.box.h0 > 0.0) {           // the rectangle collision model: A.obs is the poses [B,n_obs,3,N+1]
         if (A.table_stride != 0) return hipErrorInvalidValue;
         return with_family(P.cand_mode, P.hi_order, [&](auto cand, auto hi) {
-            hipLaunchKernelGGL((rollout_all_box_f64_kernel<cand(), hi()>), dim3(B), dim3(64), 0, st, P, B, A.x0, A.u_prev, A.kparams, A.flags,
-                               A.obs, A.table, A.cinf, A.centre(), A.box, X_all, U_all, cost_all, viol_all, A.rec_sN, A.rec_vN, A.rec_J,
-                               A.rec_viol);
-            return hipGetLastError();
+            return launch(rollout_all_box_f64_kernel<cand(), hi()>, dim3(B), dim3(64), A.box);
         });
     }
     if (A.table_stride != 0) {      // per-scenario candidate sets: A.table is U[B,C,2,N]
         if (P.cand_mode != CAND_TABLE || A.table_stride != cand_table_doubles(P.C, P.N)) return hipErrorInvalidValue;
         return with_bool(P.hi_order != 0, [&](auto hi) {
-            hipLaunchKernelGGL((rollout_all_f64_kernel<CAND_TABLE, hi(), true>), dim3((B + 3) / 4), dim3(256), 0, st, P, B, A.x0, A.u_prev,
-                               A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), X_all, U_all, cost_all, viol_all, A.rec_sN,
-                               A.rec_vN, A.rec_J, A.rec_viol);
-            return hipGetLastError();
+            return launch(rollout_all_f64_kernel<CAND_TABLE, hi(), true>, grid4, block4);
         });
     }
     return with_family(P.cand_mode, P.hi_order, [&](auto cand, auto hi) {
-        hipLaunchKernelGGL((rollout_all_f64_kernel<cand(), hi()>), dim3((B + 3) / 4), dim3(256), 0, st, P, B, A.x0, A.u_prev,
-                           A.kparams, A.flags, A.obs, A.table, A.cinf, A.centre(), X_all, U_all, cost_all, viol_all, A.rec_sN, A.rec_vN,
-                           A.rec_J, A.rec_viol);
-        return hipGetLastError();
+        return launch(rollout_all_f64_kernel<cand(), hi()>, grid4, block4);
     });
 }
 

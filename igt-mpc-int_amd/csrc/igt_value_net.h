@@ -121,7 +121,7 @@ __global__ __launch_bounds__(64) void value_kernel(int B, int C, DevNet<T> net, 
     double bestJ = Jt;
     int bestC = (viol == 0 && fin) ? c : -1;
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
+    for (int off = 32; off >= 1; off >>= 1) {      // wave_argmin (igt_device.h) written out: it must agree with it
         const double oJ = __shfl_xor(bestJ, off, 64);
         const int oC = __shfl_xor(bestC, off, 64);
         const bool take = (oC >= 0) && (bestC < 0 || oJ < bestJ || (oJ == bestJ && oC < bestC));
@@ -155,7 +155,7 @@ __device__ __forceinline__ void value_finish(int gw, int c, size_t idx, float V,
     double bestJ = Jt;
     int bestC = (viol == 0 && fin) ? c : -1;
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
+    for (int off = 32; off >= 1; off >>= 1) {      // wave_argmin (igt_device.h) written out: it must agree with it
         const double oJ = __shfl_xor(bestJ, off, 64);
         const int oC = __shfl_xor(bestC, off, 64);
         const bool take = (oC >= 0) && (bestC < 0 || oJ < bestJ || (oJ == bestJ && oC < bestC));

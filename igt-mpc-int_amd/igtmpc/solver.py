@@ -232,6 +232,56 @@ class BatchSolver:
             ptr = 1
         return ptr or None
 
+    # ------------------------------------------------------------------ one path to the solve and roll-out entries
+    def _solve_inputs(self, B, x0, u_prev, kparams, flags, obs, tv_sv, enc, eighth, obs_rows=2):
+        """The eight (array, shape) pairs every solve and roll-out entry takes, in ABI order.  obs_rows: 2 (obs_xy) or 3 (obs_pose);
+        eighth: u_ws[B,2,N] or the per-scenario candidates U[B,C,2,N] with its shape."""
+        return [(x0, (B, 7)), (u_prev, (B, 2)), (kparams, (B, 3)), (flags, (B,)), (obs, (B, self.n_obs, obs_rows, self.N + 1)),
+                (tv_sv, (B, 2)), (enc, (B, 2)), eighth]
+
+    def _new_out(self, spec, like, skip=()):
+        """The dict an entry answers with, from spec = ((name, shape, dtype), ...): torch tensors beside `like` or numpy arrays, as
+        `like` is; the names in skip stay None."""
+        if _is_torch(like):
+            import torch
+            td = {np.float32: torch.float32, np.float64: torch.float64, np.int32: torch.int32}
+            return {k: None if k in skip else torch.empty(s, dtype=td[d], device=like.device) for k, s, d in spec}
+        return {k: None if k in skip else np.empty(s, d) for k, s, d in spec}
+
+    def _call(self, fn, B, inputs, spec, out, stream, scalars, refuse_copies):
+        """fn(handle, B, *inputs, *scalars, *outputs, mode, stream): inputs the eight pairs of _solve_inputs, the outputs out[name]
+        for spec's names in ABI order, scalars the doubles the box entries take between the two."""
+        n_in = len(inputs)
+        arrs = [a for a, _ in inputs] + [out[k] for k, _, _ in spec]
+        shapes = [s for _, s in inputs] + [s for _, s, _ in spec]
+        dts = [np.uint32 if i == 3 else self.np_dtype for i in range(n_in)] + [d for _, _, d in spec]      # 3: flags
+        mode, ptrs, keep = self._prep(arrs, shapes, dts)
+        if refuse_copies and mode == L.IGT_MEM_HOST:
+            for (k, _, _), ptr in zip(spec, ptrs[n_in:]):
+                if keep_is_copy(out[k], ptr):
+                    raise ValueError(f'out[{k!r}] must be a contiguous array of the solver dtype')
+        self._check(fn(self._h, B, *ptrs[:n_in], *(float(v) for v in scalars), *ptrs[n_in:], mode,
+                       self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        return out
+
+    def _call_solve(self, fn, B, inputs, out, stream, scalars=()):
+        """One solve entry -> dict(x, u, cost, argmin, status): allocated like x0 unless the caller brought it; an output the
+        marshalling had to copy is refused."""
+        dt, N = self.np_dtype, self.N
+        spec = (('x', (B, 7, N + 1), dt), ('u', (B, 2, N), dt), ('cost', (B,), dt), ('argmin', (B,), np.int32),
+                ('status', (B,), np.int32))
+        if out is None:
+            out = self._new_out(spec, inputs[0][0])
+        return self._call(fn, B, inputs, spec, out, stream, scalars, True)
+
+    def _call_rollout(self, fn, B, inputs, want_X, want_U, stream, scalars=()):
+        """One roll-out entry of every candidate -> dict(X | None, U | None, cost, viol), numpy: the public methods have refused
+        tensors."""
+        dt, N, Cn = self.np_dtype, self.N, self.C
+        spec = (('X', (B, Cn, 7, N + 1), dt), ('U', (B, Cn, 2, N), dt), ('cost', (B, Cn), dt), ('viol', (B, Cn), np.uint32))
+        out = self._new_out(spec, None, skip=('X',) * (not want_X) + ('U',) * (not want_U))
+        return self._call(fn, B, inputs, spec, out, stream, scalars, False)
+
     # ------------------------------------------------------------------ the solve
     def solve(self, x0, u_prev, kparams, flags, obs_xy=None, tv_sv=None, enc=None, out=None, stream=None, u_ws=None):
         """x0[B,7] u_prev[B,2] kparams[B,3] flags[B] obs_xy[B,n_obs,2,N+1]
@@ -239,36 +289,12 @@ class BatchSolver:
         u_ws[B,2,N]: warm start (previous solution shifted by one step, utils.py:354-363), read where
         flags & IGT_FLAG_WARM; ramp-hold candidates are then centred on it instead of on u_prev."""
         B = int(x0.shape[0])
-        dt, N, no = self.np_dtype, self.N, self.n_obs
-        torch_mode = _is_torch(x0)
         host_polish = self.value_polish_iters if self.value_polish_driver == 'host' else 0
-        if host_polish and torch_mode:
+        if host_polish and _is_torch(x0):
             raise TypeError('value_polish_iters > 0 is driven from the host: solve() takes numpy arrays then, not device tensors '
                             '(and cannot be captured in a stream graph); set_value_polish(0) for the device-resident solve')
-        if out is None:
-            if torch_mode:
-                import torch
-                td = torch.float32 if self.dtype == 'f32' else torch.float64
-                dev = x0.device
-                out = dict(x=torch.empty((B, 7, N + 1), dtype=td, device=dev),
-                           u=torch.empty((B, 2, N), dtype=td, device=dev),
-                           cost=torch.empty((B,), dtype=td, device=dev),
-                           argmin=torch.empty((B,), dtype=torch.int32, device=dev),
-                           status=torch.empty((B,), dtype=torch.int32, device=dev))
-            else:
-                out = dict(x=np.empty((B, 7, N + 1), dt), u=np.empty((B, 2, N), dt), cost=np.empty((B,), dt),
-                           argmin=np.empty((B,), np.int32), status=np.empty((B,), np.int32))
-        arrs = [x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, u_ws,
-                out['x'], out['u'], out['cost'], out['argmin'], out['status']]
-        shapes = [(B, 7), (B, 2), (B, 3), (B,), (B, no, 2, N + 1), (B, 2), (B, 2), (B, 2, N),
-                  (B, 7, N + 1), (B, 2, N), (B,), (B,), (B,)]
-        dts = [dt, dt, dt, np.uint32, dt, dt, dt, dt, dt, dt, dt, np.int32, np.int32]
-        mode, ptrs, keep = self._prep(arrs, shapes, dts)
-        if mode == L.IGT_MEM_HOST:
-            for k, i in (('x', 8), ('u', 9), ('cost', 10), ('argmin', 11), ('status', 12)):
-                if keep_is_copy(out[k], ptrs[i]):
-                    raise ValueError(f'out[{k!r}] must be a contiguous array of the solver dtype')
-        self._check(self._solve(self._h, B, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        inputs = self._solve_inputs(B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, (u_ws, (B, 2, self.N)))
+        out = self._call_solve(self._solve, B, inputs, out, stream)
         if host_polish:      # (host arrays: the solve above has synchronised)
             self._value_polish_host(x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, out, host_polish)
         return out
@@ -278,20 +304,10 @@ class BatchSolver:
         """Every candidate of every scenario (parity/debug):
         -> dict(X[B,C,7,N+1] | None, U[B,C,2,N] | None, cost[B,C], viol[B,C])."""
         B = int(x0.shape[0])
-        dt, N, no, Cn = self.np_dtype, self.N, self.n_obs, self.C
         if _is_torch(x0):
             raise TypeError('rollout_all is a host-mode debug entry (numpy buffers)')
-        X = np.empty((B, Cn, 7, N + 1), dt) if want_X else None
-        U = np.empty((B, Cn, 2, N), dt) if want_U else None
-        cost = np.empty((B, Cn), dt)
-        viol = np.empty((B, Cn), np.uint32)
-        arrs = [x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, u_ws, X, U, cost, viol]
-        shapes = [(B, 7), (B, 2), (B, 3), (B,), (B, no, 2, N + 1), (B, 2), (B, 2), (B, 2, N),
-                  (B, Cn, 7, N + 1), (B, Cn, 2, N), (B, Cn), (B, Cn)]
-        dts = [dt, dt, dt, np.uint32, dt, dt, dt, dt, dt, dt, dt, np.uint32]
-        mode, ptrs, keep = self._prep(arrs, shapes, dts)
-        self._check(self._rollout(self._h, B, *ptrs, mode, self._stream_ptr(stream, False)))
-        return dict(X=X, U=U, cost=cost, viol=viol)
+        inputs = self._solve_inputs(B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, (u_ws, (B, 2, self.N)))
+        return self._call_rollout(self._rollout, B, inputs, want_X, want_U, stream)
 
     # ------------------------------------------------------------------ per-scenario candidate sets
     def _check_candidates(self, what, x0, U):
@@ -318,30 +334,8 @@ class BatchSolver:
             raise TypeError("value_polish_iters > 0 under value_polish_driver='host' is solve()'s loop: "
                             "set_value_polish_driver('device') takes the steps inside solve_candidates, set_value_polish(0) none")
         fn = self._entry('igt_solve_candidates_f64')
-        dt, N, no, Cn = self.np_dtype, self.N, self.n_obs, self.C
-        if out is None:
-            if _is_torch(x0):
-                import torch
-                dev = x0.device
-                out = dict(x=torch.empty((B, 7, N + 1), dtype=torch.float64, device=dev),
-                           u=torch.empty((B, 2, N), dtype=torch.float64, device=dev),
-                           cost=torch.empty((B,), dtype=torch.float64, device=dev),
-                           argmin=torch.empty((B,), dtype=torch.int32, device=dev),
-                           status=torch.empty((B,), dtype=torch.int32, device=dev))
-            else:
-                out = dict(x=np.empty((B, 7, N + 1), dt), u=np.empty((B, 2, N), dt), cost=np.empty((B,), dt),
-                           argmin=np.empty((B,), np.int32), status=np.empty((B,), np.int32))
-        arrs = [x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, U, out['x'], out['u'], out['cost'], out['argmin'], out['status']]
-        shapes = [(B, 7), (B, 2), (B, 3), (B,), (B, no, 2, N + 1), (B, 2), (B, 2), (B, Cn, 2, N),
-                  (B, 7, N + 1), (B, 2, N), (B,), (B,), (B,)]
-        dts = [dt, dt, dt, np.uint32, dt, dt, dt, dt, dt, dt, dt, np.int32, np.int32]
-        mode, ptrs, keep = self._prep(arrs, shapes, dts)
-        if mode == L.IGT_MEM_HOST:
-            for k, i in (('x', 8), ('u', 9), ('cost', 10), ('argmin', 11), ('status', 12)):
-                if keep_is_copy(out[k], ptrs[i]):
-                    raise ValueError(f'out[{k!r}] must be a contiguous array of the solver dtype')
-        self._check(fn(self._h, B, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
-        return out
+        inputs = self._solve_inputs(B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, (U, (B, self.C, 2, self.N)))
+        return self._call_solve(fn, B, inputs, out, stream)
 
     def rollout_candidates(self, x0, u_prev, kparams, flags, U, obs_xy=None, tv_sv=None, enc=None, want_X=True, want_U=True,
                            stream=None):
@@ -351,18 +345,8 @@ class BatchSolver:
         if _is_torch(x0) or _is_torch(U):
             raise TypeError('rollout_candidates is a host-mode entry (numpy buffers), like rollout_all')
         fn = self._entry('igt_rollout_candidates_f64')
-        dt, N, no, Cn = self.np_dtype, self.N, self.n_obs, self.C
-        X = np.empty((B, Cn, 7, N + 1), dt) if want_X else None
-        Uo = np.empty((B, Cn, 2, N), dt) if want_U else None
-        cost = np.empty((B, Cn), dt)
-        viol = np.empty((B, Cn), np.uint32)
-        arrs = [x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, U, X, Uo, cost, viol]
-        shapes = [(B, 7), (B, 2), (B, 3), (B,), (B, no, 2, N + 1), (B, 2), (B, 2), (B, Cn, 2, N),
-                  (B, Cn, 7, N + 1), (B, Cn, 2, N), (B, Cn), (B, Cn)]
-        dts = [dt, dt, dt, np.uint32, dt, dt, dt, dt, dt, dt, dt, np.uint32]
-        mode, ptrs, keep = self._prep(arrs, shapes, dts)
-        self._check(fn(self._h, B, *ptrs, mode, self._stream_ptr(stream, False)))
-        return dict(X=X, U=Uo, cost=cost, viol=viol)
+        inputs = self._solve_inputs(B, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, (U, (B, self.C, 2, self.N)))
+        return self._call_rollout(fn, B, inputs, want_X, want_U, stream)
 
     # ------------------------------------------------------------------ rectangle (OBCA) collision model
     def _check_box(self, what, x0):
@@ -384,31 +368,8 @@ class BatchSolver:
         are refused."""
         B = self._check_box('solve_box', x0)
         fn = self._entry('igt_solve_batch_box_f64')
-        dt, N, no = self.np_dtype, self.N, self.n_obs
-        if out is None:
-            if _is_torch(x0):
-                import torch
-                dev = x0.device
-                out = dict(x=torch.empty((B, 7, N + 1), dtype=torch.float64, device=dev),
-                           u=torch.empty((B, 2, N), dtype=torch.float64, device=dev),
-                           cost=torch.empty((B,), dtype=torch.float64, device=dev),
-                           argmin=torch.empty((B,), dtype=torch.int32, device=dev),
-                           status=torch.empty((B,), dtype=torch.int32, device=dev))
-            else:
-                out = dict(x=np.empty((B, 7, N + 1), dt), u=np.empty((B, 2, N), dt), cost=np.empty((B,), dt),
-                           argmin=np.empty((B,), np.int32), status=np.empty((B,), np.int32))
-        arrs = [x0, u_prev, kparams, flags, obs_pose, tv_sv, enc, u_ws, out['x'], out['u'], out['cost'], out['argmin'], out['status']]
-        shapes = [(B, 7), (B, 2), (B, 3), (B,), (B, no, 3, N + 1), (B, 2), (B, 2), (B, 2, N),
-                  (B, 7, N + 1), (B, 2, N), (B,), (B,), (B,)]
-        dts = [dt, dt, dt, np.uint32, dt, dt, dt, dt, dt, dt, dt, np.int32, np.int32]
-        mode, ptrs, keep = self._prep(arrs, shapes, dts)
-        if mode == L.IGT_MEM_HOST:
-            for k, i in (('x', 8), ('u', 9), ('cost', 10), ('argmin', 11), ('status', 12)):
-                if keep_is_copy(out[k], ptrs[i]):
-                    raise ValueError(f'out[{k!r}] must be a contiguous array of the solver dtype')
-        self._check(fn(self._h, B, *ptrs[:8], float(length), float(width), float(d_box), *ptrs[8:], mode,
-                       self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
-        return out
+        inputs = self._solve_inputs(B, x0, u_prev, kparams, flags, obs_pose, tv_sv, enc, (u_ws, (B, 2, self.N)), obs_rows=3)
+        return self._call_solve(fn, B, inputs, out, stream, scalars=(length, width, d_box))
 
     def rollout_all_box(self, x0, u_prev, kparams, flags, obs_pose, tv_sv=None, enc=None, want_X=True, want_U=True,
                         stream=None, u_ws=None, length=4.47, width=2.0, d_box=0.0):
@@ -419,19 +380,8 @@ class BatchSolver:
         if _is_torch(x0):
             raise TypeError('rollout_all_box is a host-mode entry (numpy buffers), like rollout_all')
         fn = self._entry('igt_rollout_batch_box_f64')
-        dt, N, no, Cn = self.np_dtype, self.N, self.n_obs, self.C
-        X = np.empty((B, Cn, 7, N + 1), dt) if want_X else None
-        U = np.empty((B, Cn, 2, N), dt) if want_U else None
-        cost = np.empty((B, Cn), dt)
-        viol = np.empty((B, Cn), np.uint32)
-        arrs = [x0, u_prev, kparams, flags, obs_pose, tv_sv, enc, u_ws, X, U, cost, viol]
-        shapes = [(B, 7), (B, 2), (B, 3), (B,), (B, no, 3, N + 1), (B, 2), (B, 2), (B, 2, N),
-                  (B, Cn, 7, N + 1), (B, Cn, 2, N), (B, Cn), (B, Cn)]
-        dts = [dt, dt, dt, np.uint32, dt, dt, dt, dt, dt, dt, dt, np.uint32]
-        mode, ptrs, keep = self._prep(arrs, shapes, dts)
-        self._check(fn(self._h, B, *ptrs[:8], float(length), float(width), float(d_box), *ptrs[8:], mode,
-                       self._stream_ptr(stream, False)))
-        return dict(X=X, U=U, cost=cost, viol=viol)
+        inputs = self._solve_inputs(B, x0, u_prev, kparams, flags, obs_pose, tv_sv, enc, (u_ws, (B, 2, self.N)), obs_rows=3)
+        return self._call_rollout(fn, B, inputs, want_X, want_U, stream, scalars=(length, width, d_box))
 
     # ------------------------------------------------------------------ polish under the value-network cost
     def _drop_vp_table(self):
@@ -644,22 +594,34 @@ class BatchSolver:
         tv_sv[B,n_obs,2] (the last raw prediction of every other vehicle, mpc.py:263-276)."""
         if not self._routes_set:
             self.set_routes()
-        B, N, M1 = int(ego_xyh.shape[0]), self.N, self.n_obs
+        return self._forecast_gathered(self._fcast, 2, ego_xyh, opp, opp_a, opp_route, (), plan_x, plan_u, has_plan, stream)
+
+    def _call_forecast(self, fn, count, inputs, obs_shape, tv_shape, stream):
+        """One forecast entry: fn(handle, count, *inputs, obs, tv, mode, stream) with inputs = (array, shape, dtype) in ABI order
+        -> (obs, tv), allocated like the first input."""
         dt = self.np_dtype
-        tv_shape = (B, 2) if M1 == 1 else (B, M1, 2)
-        if _is_torch(ego_xyh):
-            import torch
-            obs = torch.empty((B, M1, 2, N + 1), dtype=ego_xyh.dtype, device=ego_xyh.device)
-            tv = torch.empty(tv_shape, dtype=ego_xyh.dtype, device=ego_xyh.device)
-        else:
-            obs, tv = np.empty((B, M1, 2, N + 1), dt), np.empty(tv_shape, dt)
-        ax = () if M1 == 1 else (M1,)
-        arrs = [ego_xyh, opp, opp_a, opp_route, plan_x, plan_u, has_plan, obs, tv]
-        shapes = [(B, 3), (B, *ax, 4), (B, *ax), (B, *ax), (B, *ax, 7, N + 1), (B, *ax, 2, N), (B, *ax), (B, M1, 2, N + 1), tv_shape]
-        dts = [dt, dt, dt, np.int32, dt, dt, np.int32, dt, dt]
+        spec = (('obs', obs_shape, dt), ('tv', tv_shape, dt))
+        out = self._new_out(spec, inputs[0][0])
+        arrs, shapes, dts = zip(*inputs, *((out[k], s, d) for k, s, d in spec))
         mode, ptrs, keep = self._prep(arrs, shapes, dts)
-        self._check(self._fcast(self._h, B, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
-        return obs, tv
+        self._check(fn(self._h, count, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
+        return out['obs'], out['tv']
+
+    def _forecast_gathered(self, fn, rows, ego_xyh, opp, opp_a, opp_route, heading, plan_x, plan_u, has_plan, stream):
+        """forecast (rows = 2, heading = ()) and forecast_pose (rows = 3, heading = (opp_heading,)): one problem per ego."""
+        B, N, M1, dt = int(ego_xyh.shape[0]), self.N, self.n_obs, self.np_dtype
+        ax = () if M1 == 1 else (M1,)
+        inputs = [(ego_xyh, (B, 3), dt), (opp, (B, *ax, 4), dt), (opp_a, (B, *ax), dt), (opp_route, (B, *ax), np.int32),
+                  *((h, (B, *ax), dt) for h in heading),
+                  (plan_x, (B, *ax, 7, N + 1), dt), (plan_u, (B, *ax, 2, N), dt), (has_plan, (B, *ax), np.int32)]
+        return self._call_forecast(fn, B, inputs, (B, M1, rows, N + 1), (B, *ax, 2), stream)
+
+    def _forecast_scenes(self, fn, rows, x, a_prev, route, plan_x, plan_u, has_plan, stream):
+        """forecast_scene (rows = 2) and forecast_scene_pose (rows = 3): E scenes of M agents, one row per agent."""
+        E, N, M, dt = int(x.shape[0]), self.N, self.n_obs + 1, self.np_dtype
+        inputs = [(x, (E, M, 7), dt), (a_prev, (E, M), dt), (route, (E, M), np.int32), (plan_x, (E, M, 7, N + 1), dt),
+                  (plan_u, (E, M, 2, N), dt), (has_plan, (E, M), np.int32)]
+        return self._call_forecast(fn, E, inputs, (E * M, M - 1, rows, N + 1), (E * M, M - 1, 2), stream)
 
     def forecast_scene(self, x, a_prev, route, plan_x=None, plan_u=None, has_plan=None, stream=None):
         """forecast() for E whole scenes of M = n_obs + 1 agents, scene-major, nothing gathered (igt_forecast_scene_*):
@@ -669,20 +631,7 @@ class BatchSolver:
         inputs bit for bit."""
         if not self._routes_set:
             self.set_routes()
-        E, N, M = int(x.shape[0]), self.N, self.n_obs + 1
-        dt = self.np_dtype
-        if _is_torch(x):
-            import torch
-            obs = torch.empty((E * M, M - 1, 2, N + 1), dtype=x.dtype, device=x.device)
-            tv = torch.empty((E * M, M - 1, 2), dtype=x.dtype, device=x.device)
-        else:
-            obs, tv = np.empty((E * M, M - 1, 2, N + 1), dt), np.empty((E * M, M - 1, 2), dt)
-        arrs = [x, a_prev, route, plan_x, plan_u, has_plan, obs, tv]
-        shapes = [(E, M, 7), (E, M), (E, M), (E, M, 7, N + 1), (E, M, 2, N), (E, M), tuple(obs.shape), tuple(tv.shape)]
-        dts = [dt, dt, np.int32, dt, dt, np.int32, dt, dt]
-        mode, ptrs, keep = self._prep(arrs, shapes, dts)
-        self._check(self._fscene(self._h, E, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
-        return obs, tv
+        return self._forecast_scenes(self._fscene, 2, x, a_prev, route, plan_x, plan_u, has_plan, stream)
 
     # ------------------------------------------------------------------ pose forecast (x, y, heading: what solve_box reads)
     def set_route_headings(self, table=None):
@@ -718,20 +667,7 @@ class BatchSolver:
         if not self._headings_set:
             self.set_route_headings()
         fn = self._entry('igt_forecast_scene_pose_f64')
-        E, N, M = int(x.shape[0]), self.N, self.n_obs + 1
-        dt = self.np_dtype
-        if _is_torch(x):
-            import torch
-            obs = torch.empty((E * M, M - 1, 3, N + 1), dtype=x.dtype, device=x.device)
-            tv = torch.empty((E * M, M - 1, 2), dtype=x.dtype, device=x.device)
-        else:
-            obs, tv = np.empty((E * M, M - 1, 3, N + 1), dt), np.empty((E * M, M - 1, 2), dt)
-        arrs = [x, a_prev, route, plan_x, plan_u, has_plan, obs, tv]
-        shapes = [(E, M, 7), (E, M), (E, M), (E, M, 7, N + 1), (E, M, 2, N), (E, M), tuple(obs.shape), tuple(tv.shape)]
-        dts = [dt, dt, np.int32, dt, dt, np.int32, dt, dt]
-        mode, ptrs, keep = self._prep(arrs, shapes, dts)
-        self._check(fn(self._h, E, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
-        return obs, tv
+        return self._forecast_scenes(fn, 3, x, a_prev, route, plan_x, plan_u, has_plan, stream)
 
     def forecast_pose(self, ego_xyh, opp, opp_a, opp_route, opp_heading, plan_x=None, plan_u=None, has_plan=None, stream=None):
         """forecast() with the obstacles' headings, per gathered problem (igtmpc.h igt_forecast_batch_pose_f64): forecast()'s
@@ -742,23 +678,7 @@ class BatchSolver:
         if not self._headings_set:
             self.set_route_headings()
         fn = self._entry('igt_forecast_batch_pose_f64')
-        B, N, M1 = int(ego_xyh.shape[0]), self.N, self.n_obs
-        dt = self.np_dtype
-        tv_shape = (B, 2) if M1 == 1 else (B, M1, 2)
-        if _is_torch(ego_xyh):
-            import torch
-            obs = torch.empty((B, M1, 3, N + 1), dtype=ego_xyh.dtype, device=ego_xyh.device)
-            tv = torch.empty(tv_shape, dtype=ego_xyh.dtype, device=ego_xyh.device)
-        else:
-            obs, tv = np.empty((B, M1, 3, N + 1), dt), np.empty(tv_shape, dt)
-        ax = () if M1 == 1 else (M1,)
-        arrs = [ego_xyh, opp, opp_a, opp_route, opp_heading, plan_x, plan_u, has_plan, obs, tv]
-        shapes = [(B, 3), (B, *ax, 4), (B, *ax), (B, *ax), (B, *ax), (B, *ax, 7, N + 1), (B, *ax, 2, N), (B, *ax),
-                  (B, M1, 3, N + 1), tv_shape]
-        dts = [dt, dt, dt, np.int32, dt, dt, dt, np.int32, dt, dt]
-        mode, ptrs, keep = self._prep(arrs, shapes, dts)
-        self._check(fn(self._h, B, *ptrs, mode, self._stream_ptr(stream, mode == L.IGT_MEM_DEVICE)))
-        return obs, tv
+        return self._forecast_gathered(fn, 3, ego_xyh, opp, opp_a, opp_route, (opp_heading,), plan_x, plan_u, has_plan, stream)
 
     def frenet_step(self, x, u, kparams, stream=None):
         """One control step of the RK4 Frenet model for n states: x[n,7], u[n,2], kparams[n,3]
