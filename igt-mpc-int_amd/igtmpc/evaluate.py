@@ -20,6 +20,8 @@ import argparse
 import json
 import os
 import time
+from functools import partial
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -117,43 +119,11 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
     log_plans=True: a diagnostic for tests and probes, not part of the loop's interface (host loop only; the device-resident loops
     ignore it) -- the result carries 'plans', one dict(ok[E,M], x[E,M,7,N+1], obs[E M,n_obs,2 or 3,N+1]) per step: what every
     problem was solved against and what it answered.  Copies every step's arrays: leave it off when measuring."""
-    if ca_type not in ('circle', 'obca'):
-        raise ValueError(f"ca_type must be 'circle' or 'obca', not {ca_type!r}")
-    obca = ca_type == 'obca'
-    if pose_forecast not in ('host', 'device'):
-        raise ValueError(f"pose_forecast must be 'host' or 'device', not {pose_forecast!r}")
-    pose_dev = pose_forecast == 'device'
-    if pose_dev and not obca:
-        raise ValueError("pose_forecast='device' needs ca_type='obca': the circle model reads no pose")
-    if obca and not pose_dev and (device_resident or graph):
-        raise ValueError("ca_type='obca' runs in the host loop only (no device forecast of headings): not with device_resident=True "
-                         'or graph=True')
-    if obca and (dtype != 'f64' or polish_iters > 0 or value_polish_iters > 0):
-        raise ValueError("ca_type='obca' needs dtype='f64' and takes neither polish_iters nor value_polish_iters (the polish judges "
-                         'its trial plans with the circle)')
-    if step not in ('torch', 'fused'):
-        raise ValueError(f"step must be 'torch' or 'fused', not {step!r}")
-    if step == 'fused' and not device_resident:
-        raise ValueError("step='fused' is the device-resident loop's step (igt_loop_advance_*): it needs device_resident=True")
-    M = int(num_agents)
-    if not 2 <= M <= 4:
-        raise ValueError(f'num_agents = {num_agents}: a scene has 2, 3 or 4 vehicles (one per approach lane)')
-    if eval_mode == 'gt_mpc' and M > 2:
-        raise ValueError("eval_mode='gt_mpc' needs num_agents = 2: the value network's features are those of a two-vehicle "
-                         'scene (mpc.py:326-338)')
-    a_min_policy = A_MIN_POLICY if a_min_policy is None else float(a_min_policy)
-    gt = eval_mode == 'gt_mpc'
-    check_value_polish(value_polish_iters, dtype if gt else 'f64', 'value_net')      # the range in every mode; the dtype where it is read
-    check_value_polish_driver(value_polish_driver)
-    vp_iters = value_polish_iters if gt else 0
-    if vp_iters and value_polish_driver == 'device' and graph:
-        raise ValueError("value_polish_iters > 0 with value_polish_driver='device' is refused under stream capture (igtmpc.h "
-                         'igt_set_value_polish): not with graph=True')
-    if vp_iters and value_polish_driver == 'host' and device_resident:
-        raise ValueError('value_polish_iters > 0 is driven from the host today: not with device_resident=True / graph=True')
+    obca, pose_dev, gt, vp_iters, M, a_min_policy = _check_options(
+        ca_type=ca_type, pose_forecast=pose_forecast, device_resident=device_resident, graph=graph, dtype=dtype,
+        polish_iters=polish_iters, value_polish_iters=value_polish_iters, value_polish_driver=value_polish_driver, step=step,
+        num_agents=num_agents, eval_mode=eval_mode, a_min_policy=a_min_policy, needs_value_net=value_net is None and init is not None)
     if gt and value_net is None:
-        if init is not None:
-            raise ValueError("eval_mode='gt_mpc' with init= needs value_net (the shipped networks are per scenario)")
         value_net = shipped_value_net(sc)                               # sc{n}_config.yaml:2 model_path
     rng = np.random.default_rng(seed)                                   # evaluate.py:35, 56
     M_sim = int(round(T_sim / dt))                                      # evaluate.py:83-84
@@ -178,7 +148,6 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
         limits['track_env'] = auto_track_env(N, dt)                     # (not applied with the gt_mpc cost: igtmpc.h)
     kp = R.kparams(rid)                                                 # [E,M,3]
     absh = R.TABLES['abs_heading'][rid]
-    flags = absh.astype(np.uint32).reshape(-1)
     u_prev = np.tile(np.array([0.0 if gt else 0.1, 0.0]), (E, M, 1))    # evaluate.py:419 (mpc) / 171 (gt_mpc)
     solver = BatchSolver(N=N, dt=dt, n_rk4=n_rk4, C=C, n_obs=M - 1, device=device, dtype=dtype, cand_mode=cand_mode,
                          refine_iters=refine_iters if cand_mode in ('ramp_hold', 'track') else 0,
@@ -186,6 +155,7 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
                          polish_step=polish_step, value_polish_iters=vp_iters,
                          value_polish_driver=value_polish_driver if gt else 'host',
                          **dict({} if feas_tol is None else {'feas_tol': feas_tol}, **dict({'d_min': 0.0} if obca else {}, **limits)))
+    enc = None
     if gt:
         solver.set_value_net(**value_net)
         # scenario encodings (mpc.py:336-337, utils.py:84-169): (e_ego, e_other) per problem
@@ -199,92 +169,32 @@ def run_closed_loop(sc=1, num_samples=1, N=40, dt=0.1, T_sim=15.0, seed=2026, C=
         solver.set_cinf(*cinf_halfplanes(dt=dt, jerk=solver.params.jerk_limit))
     stepper = BatchSolver(N=1, dt=dt, n_rk4=n_rk4, C=64, n_obs=0, device=device, dtype='f64',
                           **{k: v for k, v in limits.items() if k in ('l_r', 'l_f')})      # the same vehicle
-    npdt = solver.np_dtype
 
-    if device_resident:
-        out = _loop_device(solver, stepper, x, u_prev, kp, flags, rid, enc if gt else None, gt, E, M, N, M_sim, device, warm,
-                           graph=graph, a_min_policy=a_min_policy, constant_speed=constant_speed, fused=step == 'fused',
-                           obca=obca)
-        solver.close()
-        stepper.close()
-        out['routes'] = pairs
-        out['track_env'] = limits.get('track_env')
-        return out
-
-    x_data = np.zeros((E, 7 * M, M_sim + 1))
-    u_data = np.zeros((E, 2 * M, M_sim))
-    x_data[:, :, 0] = x.reshape(E, 7 * M)
-    infeasible = np.zeros((E, M), dtype=np.int64)
-    solve_ms = []
-    plans = []
-    host_pred = ConstantAccelerationModel(N=N, dt=dt, constant_speed=constant_speed) if obca and not pose_dev else None
-    have_sol = np.zeros((E, M), dtype=bool)
-    sol_x = np.zeros((E, M, 7, N + 1))
-    sol_u = np.zeros((E, M, 2, N))
-
-    for t in range(M_sim):
-        # --- forecast of every other agent for every (episode, ego) problem, on the device, from the scene as it lies:
-        #     predict (evaluate.py:455) -> share motion forecasts (458-460) -> filter_preds (474)
-        a_fc = u_prev[:, :, 0]
-        if gt and t == 0:                                               # evaluate.py:207-210: a = 0.09 (k+1) for agent k
-            a_fc = np.tile(0.09 * (np.arange(M) + 1.0), (E, 1))
-        if constant_speed:                                              # constant_acceleration_model.py:26-29
-            a_fc = np.zeros((E, M))
-        forecast = solver.forecast_scene_pose if pose_dev else solver.forecast_scene      # pose: x, y and heading in one call
-        obs, tv = forecast(x.astype(npdt), a_fc.astype(npdt), rid.astype(np.int32), sol_x.astype(npdt),
-                           sol_u.astype(npdt), (have_sol & (t > 0)).astype(np.int32))
-        tv = tv.reshape(E * M, -1)                                      # (read by the gt_mpc cost only: M = 2, [E M, 2])
-        if obca and not pose_dev:      # x, y with the host predictor's (or the shared plan's) headings: pose [E M, n_obs, 3, N+1]
-            head = obca_headings(host_pred, x, a_fc, rid, have_sol & (t > 0), sol_x, sol_u, absh)
-            obs = np.concatenate([obs, gather_opponents(head)[:, :, None, :].astype(npdt)], axis=2)
-        # --- solve every (episode, agent) problem at once (evaluate.py:470-482); an agent that solved the previous
-        #     step passes that solution, shifted by one step, as its warm start (evaluate.py:478-481)
-        t0 = time.perf_counter()
-        fl, u_ws = flags, None
-        if warm and t > (1 if gt else 0):                              # evaluate.py:478 (mpc: t >= 1) / :232 (gt_mpc: t > 1)
-            fl = flags | np.where(have_sol.reshape(-1), IGT_FLAG_WARM, 0).astype(np.uint32)
-            u_ws = shift_controls(sol_u).reshape(E * M, 2, N).astype(npdt)
-        if obca:
-            out = solver.solve_box(x.reshape(E * M, 7).astype(npdt), u_prev.reshape(E * M, 2).astype(npdt),
-                                   kp.reshape(E * M, 3).astype(npdt), fl, obs, tv if gt else None,
-                                   enc.astype(npdt) if gt else None, u_ws=u_ws, length=OBCA_LENGTH, width=OBCA_WIDTH, d_box=0.0)
-        else:
-            out = solver.solve(x.reshape(E * M, 7).astype(npdt), u_prev.reshape(E * M, 2).astype(npdt),
-                               kp.reshape(E * M, 3).astype(npdt), fl, obs,
-                               tv if gt else None, enc.astype(npdt) if gt else None, u_ws=u_ws)
-        solve_ms.append((time.perf_counter() - t0) * 1e3)
-        ok = (out['status'] == 0).reshape(E, M)
-        xs = out['x'].reshape(E, M, 7, N + 1).astype(np.float64)
-        us = out['u'].reshape(E, M, 2, N).astype(np.float64)
-        if log_plans:
-            plans.append(dict(ok=ok.copy(), x=xs.copy(), obs=np.array(obs, dtype=np.float64)))
-        # --- infeasible: brake fallback (evaluate.py:511-545)
-        v_now = x[..., 5]
-        a_fb = np.where(v_now > 0, a_min_policy, 0.0)
-        u_fb = np.stack([a_fb, u_prev[..., 1]], axis=-1)
-        nxt_fb = stepper.frenet_step(x.reshape(E * M, 7), u_fb.reshape(E * M, 2), kp.reshape(E * M, 3)).reshape(E, M, 7)
-        neg = v_now < 0                                                 # evaluate.py:523-526: instantaneous stop
-        stop = x.copy()
-        stop[..., 5] = 0.0
-        nxt_fb = np.where(neg[..., None], stop, nxt_fb)
-        u_fb[..., 0] = np.where(neg, 0.0, u_fb[..., 0])
-        x_next = np.where(ok[..., None], xs[:, :, :, 1], nxt_fb)
-        u_app = np.where(ok[..., None], us[:, :, :, 0], u_fb)
-        infeasible += ~ok
-        x, u_prev = x_next, u_app
-        have_sol, sol_x, sol_u = ok, np.nan_to_num(xs), np.nan_to_num(us)
-        x_data[:, :, t + 1] = x.reshape(E, 7 * M)
-        u_data[:, :, t] = u_app.reshape(E, 2 * M)
-        if verbose and t % 10 == 0:
-            print(f't={t:3d} s={x[0, :, 2].round(2)} v={x[0, :, 5].round(2)} ok={ok[0]}', flush=True)
-
-    deadlock = (x_data[:, 2::7, -1] <= 30).sum(axis=1) >= 2             # evaluate.py:566-569
+    S = _loop_state(x, u_prev, kp, absh.astype(np.uint32).reshape(-1), rid, enc, N, M_sim, solver.np_dtype, warm,
+                    a_first=np.tile(0.09 * (np.arange(M) + 1.0), (E, 1)) if gt else None,      # evaluate.py:207-210
+                    a_fixed=np.zeros((E, M)) if constant_speed else None,                      # constant_acceleration_model.py:26-29
+                    device=device if device_resident else None)
+    do = SimpleNamespace(forecast=solver.forecast_scene_pose if pose_dev else solver.forecast_scene,      # pose: x, y, heading in one call
+                         solve=partial(solver.solve_box, length=OBCA_LENGTH, width=OBCA_WIDTH, d_box=0.0) if obca else solver.solve,
+                         advance=(partial(_advance_fused, solver=solver, a_brake=a_min_policy) if step == 'fused' else
+                                  partial(_advance_torch if device_resident else _advance_numpy, stepper=stepper, a_brake=a_min_policy)),
+                         headings=None, solve_ms=[], plans=[] if log_plans and not device_resident else None)
+    if obca and not pose_dev:      # x, y from the device with the host predictor's (or the shared plan's) headings
+        host_pred = ConstantAccelerationModel(N=N, dt=dt, constant_speed=constant_speed)
+        do.headings = lambda a_fc: obca_headings(host_pred, S.x, a_fc, S.rid, S.has_plan, S.plan_x, S.plan_u, absh)
+    wall = _drive(S, do, M_sim, gt, device=device if device_resident else None, graph=graph, verbose=verbose)
     solver.close()
     stepper.close()
-    res = dict(x_data=x_data, u_data=u_data, infeasible_ratio=infeasible / M_sim, deadlock=deadlock,
-               routes=pairs, solve_ms=np.array(solve_ms), track_env=limits.get('track_env'))
-    if log_plans:
-        res['plans'] = plans
+
+    host = (lambda a: a.cpu().numpy()) if device_resident else (lambda a: a)
+    x_data = host(S.x_data)
+    res = dict(x_data=x_data, u_data=host(S.u_data), infeasible_ratio=host(S.infeasible) / M_sim,
+               deadlock=(x_data[:, 2::7, -1] <= 30).sum(axis=1) >= 2,      # evaluate.py:566-569
+               routes=pairs, solve_ms=np.array(do.solve_ms), track_env=limits.get('track_env'))
+    if device_resident:
+        res.update(solve_ms=np.full(M_sim, wall / M_sim * 1e3), wall_s=wall)
+    if do.plans is not None:
+        res['plans'] = do.plans
     return res
 
 
@@ -317,146 +227,213 @@ def gather_opponents(a):
     return a[:, idx].reshape((E * M, M - 1) + a.shape[2:])
 
 
-def shift_controls(u):
-    """Control part of utils.py:354-363 augment_prev_sol: u[...,2,N] -> [u[..., 1:], u[..., -1:]] (numpy or torch)."""
+def shift_controls(u, out=None):
+    """Control part of utils.py:354-363 augment_prev_sol: u[...,2,N] -> [u[..., 1:], u[..., -1:]] (numpy or torch; written into
+    `out` where one is given)."""
     if isinstance(u, np.ndarray):
-        return np.concatenate([u[..., 1:], u[..., -1:]], axis=-1)
+        return np.concatenate([u[..., 1:], u[..., -1:]], axis=-1, out=out)
     import torch
-    return torch.cat([u[..., 1:], u[..., -1:]], dim=-1)
+    return torch.cat([u[..., 1:], u[..., -1:]], dim=-1, out=out)
 
 
-def _loop_device(solver, stepper, x, u_prev, kp, flags, rid, enc, gt, E, M, N, M_sim, device, warm, graph=False,
-                 a_min_policy=A_MIN_POLICY, constant_speed=False, fused=False, obca=False):
-    """The same time loop with every array resident in HBM (float64 state, solver-dtype views per call).
-    graph=True: steps 0 and 1 run eagerly, then ONE step -- forecast, solve, fallback step and the ~40 small tensor
-    operations between them -- is captured in a stream graph and replayed for the remaining steps (the state lives in
-    fixed buffers that the captured step updates in place; the column of x_data / u_data it writes is a device-side
-    counter).  The loop is launch-bound at a few hundred problems per step; the replay removes the launches.
-    fused=True (run_closed_loop step='fused'): the tensor operations behind the solve and the stepper's model step are one
-    launch of igt_loop_advance_* on the solver's handle; `stepper` is not used.
-    obca=True (run_closed_loop ca_type='obca', pose_forecast='device'): the forecast is the pose forecast and the solve the
-    rectangle solve, both on device tensors; everything else is the same step."""
+def _check_options(ca_type, pose_forecast, device_resident, graph, dtype, polish_iters, value_polish_iters, value_polish_driver,
+                   step, num_agents, eval_mode, a_min_policy, needs_value_net):
+    """Every refusal run_closed_loop makes of its options, in the order callers rely on, before anything is set up
+    -> the derived switches (obca, pose_dev, gt, vp_iters, M, a_min_policy).  needs_value_net: init= without value_net=."""
+    if ca_type not in ('circle', 'obca'):
+        raise ValueError(f"ca_type must be 'circle' or 'obca', not {ca_type!r}")
+    obca = ca_type == 'obca'
+    if pose_forecast not in ('host', 'device'):
+        raise ValueError(f"pose_forecast must be 'host' or 'device', not {pose_forecast!r}")
+    pose_dev = pose_forecast == 'device'
+    if pose_dev and not obca:
+        raise ValueError("pose_forecast='device' needs ca_type='obca': the circle model reads no pose")
+    if obca and not pose_dev and (device_resident or graph):
+        raise ValueError("ca_type='obca' runs in the host loop only (no device forecast of headings): not with device_resident=True "
+                         'or graph=True')
+    if obca and (dtype != 'f64' or polish_iters > 0 or value_polish_iters > 0):
+        raise ValueError("ca_type='obca' needs dtype='f64' and takes neither polish_iters nor value_polish_iters (the polish judges "
+                         'its trial plans with the circle)')
+    if step not in ('torch', 'fused'):
+        raise ValueError(f"step must be 'torch' or 'fused', not {step!r}")
+    if step == 'fused' and not device_resident:
+        raise ValueError("step='fused' is the device-resident loop's step (igt_loop_advance_*): it needs device_resident=True")
+    M = int(num_agents)
+    if not 2 <= M <= 4:
+        raise ValueError(f'num_agents = {num_agents}: a scene has 2, 3 or 4 vehicles (one per approach lane)')
+    gt = eval_mode == 'gt_mpc'
+    if gt and M > 2:
+        raise ValueError("eval_mode='gt_mpc' needs num_agents = 2: the value network's features are those of a two-vehicle "
+                         'scene (mpc.py:326-338)')
+    check_value_polish(value_polish_iters, dtype if gt else 'f64', 'value_net')      # the range in every mode; the dtype where it is read
+    check_value_polish_driver(value_polish_driver)
+    vp_iters = value_polish_iters if gt else 0
+    if vp_iters and value_polish_driver == 'device' and graph:
+        raise ValueError("value_polish_iters > 0 with value_polish_driver='device' is refused under stream capture (igtmpc.h "
+                         'igt_set_value_polish): not with graph=True')
+    if vp_iters and value_polish_driver == 'host' and device_resident:
+        raise ValueError('value_polish_iters > 0 is driven from the host today: not with device_resident=True / graph=True')
+    if gt and needs_value_net:
+        raise ValueError("eval_mode='gt_mpc' with init= needs value_net (the shipped networks are per scenario)")
+    return obca, pose_dev, gt, vp_iters, M, A_MIN_POLICY if a_min_policy is None else float(a_min_policy)
+
+
+def _loop_state(x, u_prev, kp, flags, rid, enc, N, M_sim, npdt, warm, a_first=None, a_fixed=None, device=None):
+    """Everything a step reads and the advance leaves, as one object: numpy arrays (device=None, the host loop) or tensors in HBM.
+    State, float64: x[E,M,7], u_prev[E,M,2]; what the next forecast reads: has_plan[E,M] (int32, zeros until a step has run),
+    plan_x[E,M,7,N+1], plan_u[E,M,2,N] (solver dtype, nan_to_num of the last answer); what the next solve reads when it is warm-
+    started: flags_ws[n] (flags | IGT_FLAG_WARM where solved), u_ws[n,2,N] (plan_u shifted); infeasible[E,M], the logs
+    x_data[E,7M,T+1], u_data[E,2M,T] and col, the column the next advance writes.  Constants: kp (float64) / kp_s (solver dtype)
+    [n,3], flags[n], rid[E,M], enc[n,2] | None, a_first / a_fixed [E,M] | None (the forecast's acceleration at step 0 / at every
+    step), warm.  cast(a): a as the solver's dtype, contiguous.  The device loops update every array in place, so a captured
+    step replays on the same buffers."""
+    (E, M), n = x.shape[:2], x.shape[0] * x.shape[1]
+    as_s = lambda a: None if a is None else np.asarray(a).astype(npdt)
+    S = SimpleNamespace(
+        x=x.astype(np.float64), u_prev=u_prev.astype(np.float64), has_plan=np.zeros((E, M), np.int32),
+        plan_x=np.zeros((E, M, 7, N + 1), npdt), plan_u=np.zeros((E, M, 2, N), npdt), flags_ws=np.zeros(n, np.uint32),
+        u_ws=np.zeros((n, 2, N), npdt), infeasible=np.zeros((E, M), np.int64), x_data=np.zeros((E, 7 * M, M_sim + 1)),
+        u_data=np.zeros((E, 2 * M, M_sim)), col=np.zeros(1, np.int64), kp=kp.reshape(n, 3).astype(np.float64), kp_s=as_s(kp.reshape(n, 3)),
+        flags=flags, rid=rid.astype(np.int32), enc=as_s(enc), a_first=a_first, a_fixed=a_fixed)
+    S.x_data[:, :, 0] = x.reshape(E, 7 * M)
+    S.warm, S.cast = warm, lambda a: a.astype(npdt)
+    if device is not None:
+        import torch
+        td = torch.float32 if npdt == np.float32 else torch.float64
+        for k, a in list(vars(S).items()):
+            if isinstance(a, np.ndarray):      # flag words travel as int32: the same bits
+                setattr(S, k, torch.as_tensor(np.ascontiguousarray(a.view(np.int32) if a.dtype == np.uint32 else a),
+                                              device=torch.device('cuda', device)))
+        S.cast = lambda a: a.to(td).contiguous()
+    return S
+
+
+def _step(S, do, first, warm):
+    """One time step, host or device: forecast acceleration -> forecast -> warm-start inputs -> solve -> advance.  first: step 0
+    (gt_mpc's forecast acceleration); warm: this solve takes the warm start the last advance left."""
+    n = S.kp.shape[0]
+    # forecast of every other agent for every (episode, ego) problem, from the scene where it lies: predict (evaluate.py:455)
+    # -> share motion forecasts (458-460) -> filter_preds (474)
+    a_fc = S.a_fixed if S.a_fixed is not None else S.a_first if first and S.a_first is not None else S.u_prev[..., 0]
+    obs, tv = do.forecast(S.cast(S.x), S.cast(a_fc), S.rid, S.plan_x, S.plan_u, S.has_plan)
+    if do.headings is not None:                                         # pose [E M, n_obs, 3, N+1]
+        obs = np.concatenate([obs, gather_opponents(do.headings(a_fc))[:, :, None, :].astype(obs.dtype)], axis=2)
+    # solve every (episode, agent) problem at once (evaluate.py:470-482); an agent that solved the previous step passes that
+    # solution, shifted by one step, as its warm start (evaluate.py:478-481)
+    fl, u_ws = (S.flags_ws, S.u_ws) if warm else (S.flags, None)
+    gt = S.enc is not None                                              # (tv is read by the gt_mpc cost only: M = 2, [E M, 2])
+    t0 = time.perf_counter()
+    out = do.solve(S.cast(S.x.reshape(n, 7)), S.cast(S.u_prev.reshape(n, 2)), S.kp_s, fl, obs, tv.reshape(n, -1) if gt else None,
+                   S.enc, u_ws=u_ws)
+    do.solve_ms.append((time.perf_counter() - t0) * 1e3)
+    if do.plans is not None:
+        do.plans.append(dict(ok=(out['status'] == 0).reshape(S.has_plan.shape), x=out['x'].reshape(S.plan_x.shape).astype(np.float64),
+                             obs=np.array(obs, dtype=np.float64)))
+    do.advance(S, out)
+
+
+# The advance, three times with one contract: (S, the solve's answer) -> S holds the next step's state, has_plan, plans and -- when
+# S.warm -- flags_ws and u_ws, the counters and the two log columns; col moves on.  Solved: next state = x*[:,1], applied input =
+# u*[:,0] (evaluate.py:491-510); infeasible: brake fallback, a_brake if v > 0 else 0, one model step, v < 0 -> stop (511-545).
+def _advance_numpy(S, out, stepper, a_brake):
+    (E, M), N = S.has_plan.shape, S.plan_u.shape[-1]
+    x, u_prev = S.x, S.u_prev
+    ok = (out['status'] == 0).reshape(E, M)
+    xs, us = out['x'].reshape(E, M, 7, N + 1), out['u'].reshape(E, M, 2, N)
+    v_now = x[..., 5]
+    a_fb = np.where(v_now > 0, a_brake, 0.0)
+    u_fb = np.stack([a_fb, u_prev[..., 1]], axis=-1)
+    nxt_fb = stepper.frenet_step(x.reshape(E * M, 7), u_fb.reshape(E * M, 2), S.kp).reshape(E, M, 7)
+    neg = v_now < 0                                                     # evaluate.py:523-526: instantaneous stop
+    stop = x.copy()
+    stop[..., 5] = 0.0
+    nxt_fb = np.where(neg[..., None], stop, nxt_fb)
+    u_fb[..., 0] = np.where(neg, 0.0, u_fb[..., 0])
+    S.x = np.where(ok[..., None], xs[:, :, :, 1], nxt_fb)
+    S.u_prev = np.where(ok[..., None], us[:, :, :, 0], u_fb)
+    S.infeasible += ~ok
+    S.has_plan, S.plan_x, S.plan_u = ok.astype(np.int32), np.nan_to_num(xs), np.nan_to_num(us)
+    if S.warm:
+        S.flags_ws = S.flags | np.where(ok.reshape(-1), IGT_FLAG_WARM, 0).astype(np.uint32)
+        S.u_ws = shift_controls(S.plan_u).reshape(E * M, 2, N)
+    S.u_data[:, :, S.col[0]] = S.u_prev.reshape(E, 2 * M)
+    S.col += 1
+    S.x_data[:, :, S.col[0]] = S.x.reshape(E, 7 * M)
+
+
+def _advance_torch(S, out, stepper, a_brake):
+    """About 40 tensor operations and the stepper handle's model step, every one in place on S's buffers."""
     import torch
-    dev = torch.device('cuda', device)
-    td = torch.float32 if solver.dtype == 'f32' else torch.float64
-    T = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
-    x, u_prev, kp = T(x).clone(), T(u_prev).clone(), T(kp)
-    kp_s = kp.reshape(E * M, 3).to(td).contiguous()
-    kp_d = kp.reshape(E * M, 3).contiguous()
-    flags_t = torch.as_tensor(flags.astype(np.int32), device=dev)
-    rid_t = torch.as_tensor(rid.astype(np.int32), device=dev)
-    enc_t = T(enc, td) if gt else None
-    x_data = torch.zeros((E, 7 * M, M_sim + 1), dtype=torch.float64, device=dev)
-    u_data = torch.zeros((E, 2 * M, M_sim), dtype=torch.float64, device=dev)
-    x_data[:, :, 0] = x.reshape(E, 7 * M)
-    infeasible = torch.zeros((E, M), dtype=torch.int64, device=dev)
-    have_sol = torch.zeros((E, M), dtype=torch.bool, device=dev)
-    sol_x = torch.zeros((E, M, 7, N + 1), dtype=td, device=dev)
-    sol_u = torch.zeros((E, M, 2, N), dtype=td, device=dev)
-    col = torch.zeros(1, dtype=torch.int64, device=dev)            # the step the next call of step() computes
-    a_fc0 = torch.as_tensor(0.09 * (np.arange(M) + 1.0), device=dev).expand(E, M) if gt else None
-    forecast = solver.forecast_scene_pose if obca else solver.forecast_scene
-    if obca:
-        def solve(x0, up, kpar, fl, obs, tv, en, u_ws=None):
-            return solver.solve_box(x0, up, kpar, fl, obs, tv, en, u_ws=u_ws, length=OBCA_LENGTH, width=OBCA_WIDTH, d_box=0.0)
-    else:
-        solve = solver.solve
+    (E, M), N = S.has_plan.shape, S.plan_u.shape[-1]
+    x, u_prev = S.x, S.u_prev
+    ok = (out['status'] == 0).reshape(E, M)
+    xs, us = out['x'].reshape(E, M, 7, N + 1), out['u'].reshape(E, M, 2, N)
+    v_now = x[..., 5]
+    a_fb = torch.where(v_now > 0, torch.full_like(v_now, a_brake), torch.zeros_like(v_now))
+    neg = v_now < 0
+    u_fb = torch.stack([torch.where(neg, torch.zeros_like(a_fb), a_fb), u_prev[..., 1]], dim=-1)
+    u_step = torch.stack([a_fb, u_prev[..., 1]], dim=-1)
+    nxt_fb = stepper.frenet_step(x.reshape(E * M, 7).contiguous(), u_step.reshape(E * M, 2).contiguous(), S.kp).reshape(E, M, 7)
+    stop = x.clone()
+    stop[..., 5] = 0.0
+    nxt_fb = torch.where(neg[..., None], stop, nxt_fb)
+    x.copy_(torch.where(ok[..., None], xs[:, :, :, 1].to(torch.float64), nxt_fb))
+    u_prev.copy_(torch.where(ok[..., None], us[:, :, :, 0].to(torch.float64), u_fb))
+    S.infeasible.add_((~ok).to(torch.int64))
+    S.has_plan.copy_(ok)
+    S.plan_x.copy_(torch.nan_to_num(xs))
+    S.plan_u.copy_(torch.nan_to_num(us))
+    if S.warm:
+        torch.bitwise_or(S.flags, S.has_plan.reshape(-1) * IGT_FLAG_WARM, out=S.flags_ws)
+        shift_controls(S.plan_u, out=S.u_ws.view(E, M, 2, N))
+    S.u_data.index_copy_(2, S.col, u_prev.reshape(E, 2 * M, 1))
+    S.col.add_(1)
+    S.x_data.index_copy_(2, S.col, x.reshape(E, 7 * M, 1))
 
-    def step(first, warm_ok=True):
-        # the forecast reads the scene where it lies (igt_forecast_scene_*): no gathered copy of any agent's state or plan
-        a_fc = a_fc0 if (gt and first) else u_prev[..., 0]
-        if constant_speed:
-            a_fc = torch.zeros_like(u_prev[..., 0])
-        hp = (have_sol & (not first)).to(torch.int32)
-        obs, tv = forecast(x.to(td), a_fc.to(td).contiguous(), rid_t, sol_x, sol_u, hp)
-        tv = tv.reshape(E * M, -1)
-        fl, u_ws = flags_t, None
-        if warm and not first and warm_ok:
-            fl = flags_t | (have_sol.reshape(-1).to(torch.int32) * IGT_FLAG_WARM)
-            u_ws = shift_controls(sol_u).reshape(E * M, 2, N).contiguous()
-        out = solve(x.reshape(E * M, 7).to(td).contiguous(), u_prev.reshape(E * M, 2).to(td).contiguous(), kp_s,
-                    fl, obs, tv if gt else None, enc_t, u_ws=u_ws)
-        ok = (out['status'] == 0).reshape(E, M)
-        xs = out['x'].reshape(E, M, 7, N + 1)
-        us = out['u'].reshape(E, M, 2, N)
-        v_now = x[..., 5]
-        a_fb = torch.where(v_now > 0, torch.full_like(v_now, a_min_policy), torch.zeros_like(v_now))
-        neg = v_now < 0
-        u_fb = torch.stack([torch.where(neg, torch.zeros_like(a_fb), a_fb), u_prev[..., 1]], dim=-1)
-        u_step = torch.stack([a_fb, u_prev[..., 1]], dim=-1)
-        nxt_fb = stepper.frenet_step(x.reshape(E * M, 7).contiguous(), u_step.reshape(E * M, 2).contiguous(),
-                                     kp_d).reshape(E, M, 7)
-        stop = x.clone()
-        stop[..., 5] = 0.0
-        nxt_fb = torch.where(neg[..., None], stop, nxt_fb)
-        x_new = torch.where(ok[..., None], xs[:, :, :, 1].to(torch.float64), nxt_fb)
-        u_new = torch.where(ok[..., None], us[:, :, :, 0].to(torch.float64), u_fb)
-        x.copy_(x_new)
-        u_prev.copy_(u_new)
-        infeasible.add_((~ok).to(torch.int64))
-        have_sol.copy_(ok)
-        sol_x.copy_(torch.nan_to_num(xs))
-        sol_u.copy_(torch.nan_to_num(us))
-        u_data.index_copy_(2, col, u_prev.reshape(E, 2 * M, 1))
-        col.add_(1)
-        x_data.index_copy_(2, col, x.reshape(E, 7 * M, 1))
 
-    if fused:
-        # step='fused': everything behind the solve is ONE kernel (igtmpc.h igt_loop_advance_*) on the solver's own handle.  It
-        # updates x and u_prev in place and writes the shared plans, the warm start, the flag words, the counter and the two
-        # log columns into the same buffers every step, so the captured step replays as it is.
-        n = E * M
-        x_n, u_n = x.reshape(n, 7), u_prev.reshape(n, 2)                  # views: the forecast reads what the kernel wrote
-        have_i = torch.zeros((E, M), dtype=torch.int32, device=dev)       # zeros until the first step has run
-        adv = dict(has_plan=have_i.reshape(n), plan_x=sol_x.reshape(n, 7, N + 1), plan_u=sol_u.reshape(n, 2, N),
-                   u_ws=torch.zeros((n, 2, N), dtype=td, device=dev), flags=torch.zeros_like(flags_t))
-        x_log, u_log = x_data.reshape(n, 7, M_sim + 1), u_data.reshape(n, 2, M_sim)      # [E,7M,T+1] agent-major: the same bytes
-        infeasible_n = infeasible.reshape(n)
+def _advance_fused(S, out, solver, a_brake):
+    """step='fused': everything behind the solve is ONE kernel (igtmpc.h igt_loop_advance_*) on the solver's own handle, writing
+    into S's buffers ([E,M,...] and [n,...] are the same bytes, the logs agent-major)."""
+    n, N, T = S.kp.shape[0], S.plan_u.shape[-1], S.u_data.shape[-1]
+    solver.loop_advance(S.x.view(n, 7), S.u_prev.view(n, 2), S.kp, out['status'], out['x'], out['u'], a_brake, flags=S.flags,
+                        infeasible=S.infeasible.view(n), x_log=S.x_data.view(n, 7, T + 1), u_log=S.u_data.view(n, 2, T), step=S.col,
+                        out=dict(has_plan=S.has_plan.view(n), plan_x=S.plan_x.view(n, 7, N + 1), plan_u=S.plan_u.view(n, 2, N),
+                                 u_ws=S.u_ws, flags=S.flags_ws))
+    S.col.add_(1)
 
-        def step(first, warm_ok=True):      # noqa: F811 -- replaces the torch step above
-            a_fc = a_fc0 if (gt and first) else u_prev[..., 0]
-            if constant_speed:
-                a_fc = torch.zeros_like(u_prev[..., 0])
-            obs, tv = forecast(x.to(td), a_fc.to(td).contiguous(), rid_t, sol_x, sol_u, have_i)
-            tv = tv.reshape(E * M, -1)
-            fl, u_ws = flags_t, None
-            if warm and not first and warm_ok:
-                fl, u_ws = adv['flags'], adv['u_ws']                     # the previous step's loop_advance left both
-            out = solve(x_n.to(td).contiguous(), u_n.to(td).contiguous(), kp_s, fl, obs, tv if gt else None, enc_t,
-                        u_ws=u_ws)
-            solver.loop_advance(x_n, u_n, kp_d, out['status'], out['x'], out['u'], a_min_policy, flags=flags_t,
-                                infeasible=infeasible_n, x_log=x_log, u_log=u_log, step=col, out=adv)
-            col.add_(1)
 
-    torch.cuda.synchronize(dev)
+def _drive(S, do, M_sim, gt, device=None, graph=False, verbose=False):
+    """The time loop over _step: owns `first` (step 0), the warm-start delay (evaluate.py:478: mpc passes it from t = 1; :232:
+    gt_mpc for t > 1 only) and, with graph=True and M_sim > 3, the graph protocol -- steps 0 and 1 run eagerly, step 1 on the
+    capture stream, then ONE step (forecast, solve, advance: every launch between them) is captured in a stream graph and
+    replayed for the remaining steps; the loop is launch-bound at a few hundred problems per step, the replay removes the
+    launches.  -> wall seconds between the two synchronisations (device) or of the loop (host)."""
+    run = lambda t: _step(S, do, first=t == 0, warm=S.warm and t > (1 if gt else 0))
+    if device is not None:
+        import torch
+        dev = torch.device('cuda', device)
+        torch.cuda.synchronize(dev)
     t_start = time.perf_counter()
-    step(True)
-    t = 1
-    use_graph = graph and M_sim > 3
-    if gt and not use_graph and M_sim > 1:
-        step(False, warm_ok=False)             # evaluate.py:232: the gt_mpc loop passes its warm start for t > 1 only
-        t = 2
-    if use_graph:
+    if device is not None and graph and M_sim > 3:
+        run(0)
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            step(False, warm_ok=not gt)        # step 1, eagerly, on the capture stream (gt_mpc: no warm start yet, :232)
+            run(1)
         torch.cuda.current_stream(dev).wait_stream(side)
-        t = 2
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=side):
-            step(False)
-        for _ in range(t, M_sim):
+            run(2)
+        for _ in range(2, M_sim):
             g.replay()
-        t = M_sim
-    for _ in range(t, M_sim):
-        step(False)
-    torch.cuda.synchronize(dev)
-    wall = time.perf_counter() - t_start
-    xd = x_data.cpu().numpy()
-    return dict(x_data=xd, u_data=u_data.cpu().numpy(), infeasible_ratio=infeasible.cpu().numpy() / M_sim,
-                deadlock=(xd[:, 2::7, -1] <= 30).sum(axis=1) >= 2, solve_ms=np.full(M_sim, wall / M_sim * 1e3),
-                wall_s=wall)
+    else:
+        for t in range(M_sim):
+            run(t)
+            if verbose and device is None and t % 10 == 0:
+                print(f't={t:3d} s={S.x[0, :, 2].round(2)} v={S.x[0, :, 5].round(2)} ok={S.has_plan[0] != 0}', flush=True)
+    if device is not None:
+        torch.cuda.synchronize(dev)
+    return time.perf_counter() - t_start
 
 
 def load_reference_configs(policy_yaml=None, env_yaml=None):
@@ -635,12 +612,9 @@ def main(argv=None):
         kw['N'] = a.N
     kw.setdefault('N', 40)
     a.N = kw['N']
-    r = run_closed_loop(sc=a.sc, num_samples=a.num_samples, C=a.C, verbose=a.verbose, eval_mode=a.eval_mode,
-                        value_net=net, device_resident=a.device_resident, cand_mode=a.cand_mode, dtype=a.dtype, graph=a.graph,
-                        polish_iters=a.polish_iters, polish_grad=a.polish_grad, polish_step=a.polish_step,
-                        value_polish_iters=a.value_polish_iters, value_polish_driver=a.value_polish_driver,
-                        num_agents=a.num_agents, step=a.step, ca_type=a.ca_type, pose_forecast=a.pose_forecast,
-                        **kw)
+    shared = ('sc', 'num_samples', 'C', 'verbose', 'eval_mode', 'device_resident', 'cand_mode', 'dtype', 'graph', 'polish_iters',
+              'polish_grad', 'polish_step', 'value_polish_iters', 'value_polish_driver', 'num_agents', 'step', 'ca_type', 'pose_forecast')
+    r = run_closed_loop(value_net=net, **{k: getattr(a, k) for k in shared}, **kw)      # the parser's names are the keywords
     if a.save_dir is not None:
         policy = {'type': 'MPC', 'N': a.N, 'dt': kw.get('dt', 0.1), 'a_min': -4, 'a_max': 3, 'v_min': -1.0, 'v_max': 5,      # mpc.yaml's keys
                   'prediction_type': 'constant_acceleration', 'collision_avoidance_type': 'circle', **policy_file,

@@ -111,7 +111,11 @@ def _run(name, **extra):
 
 
 def _run_captured_on_own_stream(name, monkeypatch):
-    """run_closed_loop(graph=True) captures on `torch.cuda.Stream(dev)`, a stream of torch's pool, which lives -- and keeps its
+    return _captured_on_own_stream(monkeypatch, lambda: _run(name, step='fused', graph=True))
+
+
+def _captured_on_own_stream(monkeypatch, run):
+    """run(): a run_closed_loop(graph=True).  It captures on `torch.cuda.Stream(dev)`, a stream of torch's pool, which lives -- and keeps its
     hardware queue -- as long as the process: one more of them here and two lanes of tests/test_gpu_overlap.py share a queue
     later in the same process (tests/test_gpu_candidates.py _side_stream has the story).  So for this run
     the driver's request for a new stream is answered with a stream of the test's own, destroyed at the end; every other use
@@ -126,9 +130,33 @@ def _run_captured_on_own_stream(name, monkeypatch):
             return pool_stream(*a, **k) if ('stream_id' in k or 'stream_ptr' in k) else own
         monkeypatch.setattr(torch.cuda, 'Stream', stream)
         try:
-            return _run(name, step='fused', graph=True)
+            return run()
         finally:
             monkeypatch.setattr(torch.cuda, 'Stream', pool_stream)
+
+
+CROSS_CASES = {
+    'gt_mpc_warm': dict(eval_mode='gt_mpc', cand_mode='track', warm_start=True),      # sc 1's shipped network; warm start from t = 2
+    'mpc_constant_speed_ramp_hold': dict(eval_mode='mpc', constant_speed=True, cand_mode='ramp_hold'),
+}
+
+
+@pytest.mark.parametrize('name', list(CROSS_CASES))
+def test_host_torch_fused_and_captured_loops_agree_bytewise(name, monkeypatch):
+    """The one step of run_closed_loop in its four forms -- the host loop, device-resident with step='torch', with step='fused',
+    and step='torch' replayed from a captured graph -- on two option sets no other test crosses: x_data, u_data,
+    infeasible_ratio and deadlock byte-equal.  Four sampled episodes of scenario 1, N = 20, six steps (t = 0, 1, 2 eagerly or
+    captured, three replays), f64."""
+    from igtmpc.evaluate import run_closed_loop
+    kw = dict(sc=1, num_samples=4, N=20, T_sim=0.6, dtype='f64', **CROSS_CASES[name])
+    host = run_closed_loop(**kw)
+    runs = {'torch': run_closed_loop(device_resident=True, step='torch', **kw),
+            'fused': run_closed_loop(device_resident=True, step='fused', **kw),
+            'graph': _captured_on_own_stream(monkeypatch, lambda: run_closed_loop(device_resident=True, step='torch', graph=True, **kw))}
+    assert host['x_data'].shape == (4, 14, 7) and np.isfinite(host['x_data']).all() and (host['x_data'][:, :, -1] != host['x_data'][:, :, 0]).any()
+    for form, got in runs.items():
+        for k in ('x_data', 'u_data', 'infeasible_ratio', 'deadlock'):
+            assert _same_bytes(got[k], host[k]), (name, form, k)
 
 
 @pytest.mark.parametrize('name', list(LR.LOOP_CASES))

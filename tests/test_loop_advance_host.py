@@ -71,8 +71,12 @@ class _ScriptedSolver:
 
     def forecast_scene(self, x, a_prev, route, plan_x, plan_u, has_plan):
         E, M = a_prev.shape
-        _ScriptedSolver.calls.append(dict(kind='forecast', x=x.copy(), plan_x=plan_x.copy(), plan_u=plan_u.copy(), has_plan=has_plan.copy()))
+        _ScriptedSolver.calls.append(dict(kind='forecast', x=x.copy(), a_prev=a_prev.copy(), plan_x=plan_x.copy(), plan_u=plan_u.copy(),
+                                          has_plan=has_plan.copy()))
         return np.zeros((E * M, M - 1, 2, self.N + 1)), np.zeros((E * M, M - 1, 2))
+
+    def set_value_net(self, **net):
+        pass
 
     def solve(self, x0, u_prev, kparams, flags, obs_xy, tv_sv, enc, u_ws=None):
         t = sum(c['kind'] == 'solve' for c in _ScriptedSolver.calls)
@@ -134,6 +138,68 @@ def test_restatement_is_the_host_loops_step(monkeypatch):
     r3 = LR.loop_advance_restated(x0, a['u_prev'], kp, a['status'], a['x_sol'], a['u_sol'], a_brake, model, x_log=x_log,
                                   u_log=u_log, step=2, want_ws=False)
     assert same(r3['x_log'], x_log) and same(r3['u_log'], u_log) and r3['u_ws'] is None and r3['flags'] is None
+
+
+def _scripted_run(monkeypatch, steps, **kw):
+    """run_closed_loop's host loop on E = 2 scenes of M = 2, N = 5, with _ScriptedSolver answering `steps` solves: the agents that
+    fall back and the ones that solve swap every step.  -> (result, forecast calls, solve calls, scripted answers, flags0)."""
+    from igtmpc import evaluate as EV, routes as R
+    E, M, N = 2, 2, 5
+    n = E * M
+    pairs = [R.SCENARIO_ROUTES[0][0], R.SCENARIO_ROUTES[0][1]]
+    rid = np.array([[R.ROUTE_ID[r] for r in p] for p in pairs])
+    script = [LR.branch_inputs(n, N, np.float64, seed=10 + t) for t in range(steps)]
+    rng = np.random.default_rng(4)
+    for t, s in enumerate(script):
+        s['status'] = (np.arange(n) % 2 == t % 2).astype(np.int32)
+        s['x_sol'], s['u_sol'] = rng.normal(0, 5.0, (n, 7, N + 1)), rng.uniform(-1, 1, (n, 2, N))
+        s['x_sol'][s['status'] != 0], s['u_sol'][s['status'] != 0] = np.nan, np.nan
+    monkeypatch.setattr(EV, 'BatchSolver', _ScriptedSolver)
+    _ScriptedSolver.script, _ScriptedSolver.calls = script, []
+    got = EV.run_closed_loop(N=N, T_sim=steps * 0.1, dtype='f64', cand_mode='track', warm_start=True, terminal_set=False,
+                             init=(script[0]['x'].reshape(E, M, 7), pairs), **kw)
+    fc = [c for c in _ScriptedSolver.calls if c['kind'] == 'forecast']
+    sv = [c for c in _ScriptedSolver.calls if c['kind'] == 'solve']
+    assert len(fc) == steps and len(sv) == steps
+    return got, fc, sv, script, R.TABLES['abs_heading'][rid].astype(np.uint32).reshape(-1)
+
+
+def test_gt_mpc_first_forecast_and_warm_start_delay(monkeypatch):
+    """eval_mode='gt_mpc' (evaluate.py:171, 207-210, 232): the previous inputs start at (0, 0), the first forecast takes
+    a = 0.09 (k + 1) for agent k and the later ones the applied acceleration, and the warm start is passed for t > 1 only -- solve 2
+    gets the plan of the agents that solved step 1, shifted, with IGT_FLAG_WARM on exactly those."""
+    got, fc, sv, script, flags0 = _scripted_run(monkeypatch, 4, eval_mode='gt_mpc', value_net=dict(layers=[]))
+    same = lambda p, q: np.array_equal(p, q, equal_nan=True)
+    assert same(fc[0]['a_prev'], np.tile([0.09, 0.18], (2, 1)))
+    assert same(sv[0]['u_prev'], np.zeros((4, 2)))
+    assert same(fc[1]['a_prev'].reshape(-1), sv[1]['u_prev'][:, 0]) and same(sv[1]['u_prev'], got['u_data'][:, :, 0].reshape(4, 2))
+    for t in (0, 1):
+        assert sv[t]['u_ws'] is None and same(sv[t]['flags'], flags0)
+    for t in (2, 3):
+        ok = script[t - 1]['status'] == 0
+        u = np.nan_to_num(script[t - 1]['u_sol'])
+        assert ok.any() and not ok.all()
+        assert same(sv[t]['flags'], flags0 | np.where(ok, LR.IGT_FLAG_WARM, 0).astype(np.uint32))
+        assert same(sv[t]['u_ws'], np.concatenate([u[:, :, 1:], u[:, :, -1:]], axis=2))
+        assert same(fc[t]['has_plan'].reshape(-1), ok) and same(fc[t]['plan_u'].reshape(u.shape), u)
+
+
+def test_constant_speed_forecast_keeps_the_brake_fallbacks_inputs(monkeypatch):
+    """constant_speed=True (mpc): every forecast takes a = 0 (constant_acceleration_model.py:26-29) while the brake fallback goes
+    on reading u_prev -- the agents that solved step 0 and fall back in step 1 keep step 0's steering, and the warm start is
+    passed from t = 1 (evaluate.py:478)."""
+    got, fc, sv, script, flags0 = _scripted_run(monkeypatch, 3, constant_speed=True, a_min_policy=-3.5)
+    same = lambda p, q: np.array_equal(p, q, equal_nan=True)
+    for c in fc:
+        assert c['a_prev'].shape == (2, 2) and not c['a_prev'].any()
+    assert same(sv[0]['u_prev'], np.tile([0.1, 0.0], (4, 1))) and sv[0]['u_ws'] is None
+    ok0 = script[0]['status'] == 0
+    assert same(sv[1]['u_prev'][ok0], script[0]['u_sol'][ok0, :, 0]) and sv[1]['u_prev'][ok0, 0].all()
+    assert same(sv[1]['flags'], flags0 | np.where(ok0, LR.IGT_FLAG_WARM, 0).astype(np.uint32)) and sv[1]['u_ws'] is not None
+    u1 = got['u_data'][:, :, 1].reshape(4, 2)                         # step 1: the agents that solved step 0 fall back
+    assert same(u1[ok0, 1], script[0]['u_sol'][ok0, 1, 0]) and same(sv[2]['u_prev'], u1)
+    v = sv[1]['x0'][ok0, 5]
+    assert same(u1[ok0, 0], np.where(v > 0, -3.5, 0.0))
 
 
 def test_launch_shape(tmp_path):
